@@ -18,14 +18,22 @@ is split into P contiguous, cost-balanced row blocks (strong scaling).
 1000 -> 8000 by incremental Cholesky appends, 512x512 grid, 1 GPU): a step is
 one append + one tick.
 
-At N = 1 the same JSON line also carries two regimes measured in the same
-run (``regimes``): the C4 sweep with tile skipping off (executed work = the
+With --full at N = 1 the same JSON line also carries regimes measured in the
+same run (``regimes``): the C4 sweep with tile skipping off (executed work = the
 dense N^2 M of SURVEY.md 8(d)) and the lpsc.yaml stress box
 ([0, 1] x [0, 2.5], config/lpsc.yaml:32-33) where almost nothing can be
 skipped -- so the algorithmic speed-up (skipping) and the hardware speed-up
 (GPU vs the dense CPU path) are reported apart.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5]
+A plain run does what the headline needs and no more: set-up (warm-up, fit,
+warm refit), W warm-up ticks, K timed ticks, the result line.  Everything else
+-- the warm RBF fill roofline, the subgoal timing, the fitted-state broadcast,
+the CPU comparator and the regimes above -- runs only with --full.
+--dump-outputs DIR writes what the last timed tick returned (mu, sd, lo, hi,
+safe and the argmax key) as DIR/<name>.npy; the inputs are seeded, so two
+builds can be compared output for output.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5] [--full] [--dump-outputs DIR]
   (--gpus N > 1 without WORLD_SIZE launches N ranks itself through
    torch.distributed.run on 127.0.0.1; the driver's own
    python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
@@ -74,13 +82,19 @@ def parse():
                         "-- RCCL exercised on a one-GPU box")
     p.add_argument("--sharding", default="cost", choices=["cost", "equal"],
                    help="strong scaling: cost-balanced contiguous row blocks (default) or equal point counts")
-    p.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget (rank 0, N=1)")
-    p.add_argument("--no-cpu", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: the warm RBF fill roofline, the subgoal "
+                        "timing, the fitted-state broadcast (N > 1 or --force-pg), the CPU baseline and the regimes")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32/float64)")
+    p.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: CPU baseline budget (rank 0, N=1)")
+    p.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     p.add_argument("--no-warmup", action="store_true", help="no sbo_warmup before the first fit (cold first fit)")
     p.add_argument("--cpu-child", default=None, help=argparse.SUPPRESS)
     p.add_argument("--no-outputs", action="store_true", help="skip writing mu/sd/lo/hi/S (argmax only)")
     p.add_argument("--no-regimes", action="store_true",
-                   help="N = 1: skip the dense (no tile skipping) and lpsc stress-box measurements")
+                   help="--full at N = 1 without the dense (no tile skipping), append1 and lpsc stress-box "
+                        "measurements")
     p.add_argument("--regime-steps", type=int, default=2, help="timed ticks per regime (after one warmup)")
     p.add_argument("--launch-check", action="store_true",
                    help="CPU rehearsal of the multi-rank path (gloo): launcher, shard cut broadcast, key all-gather")
@@ -348,7 +362,7 @@ def run_sweep(a, dev, world, rank):
     # SURVEY.md 8(e) alternative: rank 0 fits, the packed predictive state is
     # broadcast (RCCL) and imported elsewhere -- timed beside the replicated fit
     fit_bcast = None
-    if a.pg:
+    if a.pg and a.full:
         dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -403,18 +417,20 @@ def run_sweep(a, dev, world, rank):
     cutoff, row_l1, alpha_l1 = gm.skip_info()
     prec = gm.precision()
 
-    # ---- RBF fill (a1) alone, warm (the fill inside fit also paid the code-object load)
-    Kbuf = torch.empty(n * n, dtype=torch.float32, device=dev)
-    fill_args = (gm.ctx.handle, ctypes.c_void_p(X.data_ptr()), ctypes.c_void_p(Y.data_ptr()), n,
-                 _to_hyper(wl.hyper), ctypes.c_void_p(Kbuf.data_ptr()), N.SBO_DEVICE_PTRS | N.SBO_ASYNC)
-    gm.ctx.check(lib.sbo_rbf_fill(*fill_args))
-    prof.reset()
-    for _ in range(3):
-        gm.ctx.check(lib.sbo_rbf_fill(*fill_args))
-    pr = prof.read()
-    fill_ms = pr["fill_ms"] / max(pr["fill_launches"], 1)
+    # ---- RBF fill (a1) alone, warm (the fill inside fit also paid the code-object load); --full only
+    fill_ms = None
     fill_bytes = 4.0 * n * n + 8.0 * n
-    del Kbuf
+    if a.full:
+        Kbuf = torch.empty(n * n, dtype=torch.float32, device=dev)
+        fill_args = (gm.ctx.handle, ctypes.c_void_p(X.data_ptr()), ctypes.c_void_p(Y.data_ptr()), n,
+                     _to_hyper(wl.hyper), ctypes.c_void_p(Kbuf.data_ptr()), N.SBO_DEVICE_PTRS | N.SBO_ASYNC)
+        gm.ctx.check(lib.sbo_rbf_fill(*fill_args))
+        prof.reset()
+        for _ in range(3):
+            gm.ctx.check(lib.sbo_rbf_fill(*fill_args))
+        pr = prof.read()
+        fill_ms = pr["fill_ms"] / max(pr["fill_launches"], 1)
+        del Kbuf
 
     best_key = torch.empty(2, dtype=torch.int64, device=dev)
 
@@ -446,13 +462,16 @@ def run_sweep(a, dev, world, rank):
     elapsed = time.perf_counter() - t0
     pr = prof.read()
     prof.reset(False)
+    if a.dump_outputs:
+        # before anything below reuses the output buffers
+        dump_outputs(a.dump_outputs, dict(outs, argmax=np.array(best, np.float64)), rank, world)
     pred_ms = pr["predict_ms"] / max(pr["predict_launches"], 1)
     exec_flops_launch = pr["predict_flops"] / max(pr["predict_launches"], 1)
     mfma_flops_launch = pr["mfma_flops"] / max(pr["predict_launches"], 1)
     levels_launch = [x / max(pr["predict_launches"], 1) for x in pr["tiles_by_level"]]
     elapsed, pred_ms_max, fit_ms_max = _max_over_ranks([elapsed, pred_ms, fit_ms], dev, world, a.backend)
     subgoal_sharded = None
-    if a.pg and not a.no_outputs and a.scaling == "strong":
+    if a.full and a.pg and not a.no_outputs and a.scaling == "strong":
         # the node-parity frontier needs the whole grid: lo / hi / S of every
         # rank all-gathered (17 B per point, SURVEY.md 8(e) optional exchange),
         # then GetNextSubgoal on every rank -- timed apart from the tick
@@ -492,11 +511,11 @@ def run_sweep(a, dev, world, rank):
     #  is reported beside it as a throughput equivalent.
     dense_flops_launch = float(n) * float(n) * m
     achieved = exec_flops_launch / (pred_ms * 1e-3) / 1e12
-    fill_gbs = fill_bytes / (fill_ms * 1e-3) / 1e9 if fill_ms > 0 else None
+    fill_gbs = fill_bytes / (fill_ms * 1e-3) / 1e9 if fill_ms else None
     # node-side selection on the tick's device outputs (8(f)1): frontier of S,
     # nearest quarter to the goal, widest interval -- GetNextSubgoal
     subgoal = None
-    if world == 1 and not a.no_outputs and subgoal_sharded is None:
+    if a.full and world == 1 and not a.no_outputs and subgoal_sharded is None:
         Dx = torch.as_tensor(wl.qx, dtype=torch.float64, device=dev)
         Dy = torch.as_tensor(wl.qy, dtype=torch.float64, device=dev)
         goal = (float(wl.qx.mean()), float(wl.qy.mean()))
@@ -511,10 +530,10 @@ def run_sweep(a, dev, world, rank):
                    "how": "sbo_subgoal: device raster/owner map, host border follow of the w x h image"}
     else:
         subgoal = subgoal_sharded
-    cpu = cpu_baseline(gm, wl, a.cpu_seconds) if world == 1 and not a.no_cpu else None
+    cpu = cpu_baseline(gm, wl, a.cpu_seconds) if a.full and world == 1 and not a.no_cpu else None
     traffic, traffic_src = pmc_traffic(a.config, n, m_total, m)
     regimes = None
-    if world == 1 and not a.no_regimes:
+    if a.full and world == 1 and not a.no_regimes:
         regimes = {"dense": run_regime_dense(a, gm, prof, step, n, m)}
         regimes["append1"] = run_regime_append1(a, gm, dev, wl, qx, qy, outs, key, fit_ms, ms_per_step)
         regimes["lpsc_stress_box"] = run_regime_stress(a, gm, prof, dev, n, gw, gh)
@@ -544,7 +563,7 @@ def run_sweep(a, dev, world, rank):
     return {
         "metric": METRIC, "value": value, "unit": "grid-points/s", "n_gpus": world, "steps": a.steps,
         "warmup": a.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": a.scaling,
-        "vs_baseline": None, "dtype": "f64" if prec[0] else dtype_of(a.variant), "data": DATA,
+        "vs_baseline": None, "dtype": "f64" if prec[0] else dtype_of(a.variant), "data": DATA, "full": a.full,
         "world_size": winfo["world_size"], "backend": winfo["backend"], "collective": winfo["collective"],
         "config": {"workload": a.config, "n_train": n, "grid": [gw, gh], "M": m_total, "M_per_rank": m,
                    "beta": wl.beta, "f_min": round(wl.f_min, 6),
@@ -576,6 +595,37 @@ def run_sweep(a, dev, world, rank):
         "cpu_baseline": cpu,
         "regimes": regimes,
     }
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, rank, world):
+    """--dump-outputs DIR: what the last timed step returned to its caller, one
+    DIR/<name>.npy per array (<name>_rank<r>.npy when N > 1), float64 kept,
+    everything else as float32.  Past 64 MB in all, every array is cut to the
+    same fixed, seeded sample of its elements (sorted indices, so the order of
+    the grid is kept)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, v in arrays.items():
+        v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        host[name] = np.ascontiguousarray(v, np.float64 if v.dtype == np.float64 else np.float32)
+    total = sum(v.nbytes for v in host.values())
+    if total > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES / total
+        rng = np.random.default_rng(20240607)
+        picks = {}
+        for name, v in host.items():
+            k = int(v.size * keep)
+            if v.size <= 4096:      # the argmax key and the like: whole
+                continue
+            if v.size not in picks:
+                picks[v.size] = np.sort(rng.choice(v.size, size=k, replace=False))
+            host[name] = v.reshape(-1)[picks[v.size]]
+    for name, v in host.items():
+        np.save(os.path.join(path, f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"), v)
 
 
 def end_to_end(m, fit_ms, tick_ms):
@@ -875,7 +925,9 @@ def run_streaming(a, dev, world, rank):
     mflops = pr["mfma_flops"] / max(pr["predict_launches"], 1)
     levels = [x / max(pr["predict_launches"], 1) for x in pr["tiles_by_level"]]
     (s, i), = key_tensor_to_pairs(last)
-    cpu = cpu_baseline_streaming(gm, wl, chunks, a.cpu_seconds) if not a.no_cpu else None
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, dict(outs, argmax=np.array([s, i], np.float64)), rank, world)
+    cpu = cpu_baseline_streaming(gm, wl, chunks, a.cpu_seconds) if a.full and not a.no_cpu else None
     value = m * steps / elapsed
     if cpu is not None:
         cpu["gpu_over_cpu"] = value / cpu["value"]
@@ -883,7 +935,7 @@ def run_streaming(a, dev, world, rank):
     return {
         "metric": METRIC, "value": value, "unit": "grid-points/s", "n_gpus": 1, "steps": steps,
         "warmup": a.warmup, "ms_per_step": elapsed * 1e3 / steps, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": dtype_of(a.variant), "data": DATA,
+        "vs_baseline": None, "dtype": dtype_of(a.variant), "data": DATA, "full": a.full,
         "config": {"workload": "C5", "n_train": [n0, n_end], "iterations": iters, "grid": [g, g], "M": m,
                    "parallelism": "single", "resort_pct": a.resort,
                    "step": "sbo_append (block Cholesky update; a k-d re-sort + refactor when the points appended "

@@ -10,15 +10,15 @@ if [ "$1" = A ]; then
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 step pmc_c4 600 bash tools/collect_pmc.sh C4 r6
 cp profiles/r6_pmc_C4.json $O/r6_pmc_C4.json
-step bench_c4 500 python bench.py
-step prof_c4 500 rocprofv3 --kernel-trace --stats -d $O/prof_c4 -o run --output-format csv -- python bench.py --no-cpu --no-regimes --steps 20
+step bench_c4 500 python bench.py --full
+step prof_c4 500 rocprofv3 --kernel-trace --stats -d $O/prof_c4 -o run --output-format csv -- python bench.py --full --no-cpu --no-regimes --steps 20
 elif [ "$1" = T ]; then
 step gpu_tests 1000 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
-step bench_c4 500 python bench.py --no-cpu
+step bench_c4 500 python bench.py --full --no-cpu
 else
-step bench_c2 300 python bench.py --config C2
-step bench_c3 400 python bench.py --config C3
-step bench_c5 400 python bench.py --config C5
+step bench_c2 300 python bench.py --full --config C2
+step bench_c3 400 python bench.py --full --config C3
+step bench_c5 400 python bench.py --full --config C5
 step shards 300 python tools/shard_emulate.py --config C4 --balance 0
 fi
 echo done

@@ -5,4 +5,4 @@ step() { local name=$1 lim=$2; shift 2; echo "== $name $(date +%T)"; timeout -k 
 
 step cost 300 python tools/dump_c4_cost.py
 step fit_outer 400 python tools/fit_timing.py --n 2048 8192 16384 --outer 512 1024 --reps 4
-step bench_c4 400 python bench.py
+step bench_c4 400 python bench.py --full

@@ -13,11 +13,11 @@ step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 # PMC traffic first: bench.py reads the summaries for roofline.traffic
 step pmc_c4 900 bash tools/collect_pmc.sh C4 $TAG
 step pmc_c3 900 bash tools/collect_pmc.sh C3 $TAG
-step bench_c4 600 python bench.py
-step bench_c3 600 python bench.py --config C3
-step bench_c2 300 python bench.py --config C2
-step bench_c5 600 python bench.py --config C5
-step prof_c4 600 rocprofv3 --kernel-trace --stats -d $O/prof_c4 -o run --output-format csv -- python bench.py --no-cpu --steps 3
+step bench_c4 600 python bench.py --full
+step bench_c3 600 python bench.py --full --config C3
+step bench_c2 300 python bench.py --full --config C2
+step bench_c5 600 python bench.py --full --config C5
+step prof_c4 600 rocprofv3 --kernel-trace --stats -d $O/prof_c4 -o run --output-format csv -- python bench.py --full --no-cpu --steps 3
 step clock_c4 900 bash tools/pmc_clock.sh c4 --config C4 --ticks 2
 [ -x tools/mfma_probe.bin ] || hipcc -O3 --offload-arch=gfx950 tools/mfma_probe.hip -o tools/mfma_probe.bin
 step shards 300 python tools/shard_emulate.py --config C4 --balance 0
