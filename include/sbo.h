@@ -619,6 +619,43 @@ SBO_API sbo_status sbo_profile_mfma(sbo_ctx *ctx, double *mfma_flops, int64_t *t
  * product(s), half-steps at six / three / one product(s); then reset. */
 SBO_API sbo_status sbo_debug_x3_stamps(sbo_ctx *ctx, double *cycles, int n);
 
+/* Test accessors: the int8-sliced GEMM under the fit (csrc/ozgemm.hip), run
+ * alone on the context's stream so that tests/test_gpu_ozgemm.py can hold the
+ * product's object code bit for bit to an integer model (tests/oz_model.py).
+ * C (m x n) = alpha op(A) op(B) (+ C), HOST pointers, column-major; op(A) is
+ * m x K (A itself K x m with SBO_GZ_TRANS_A), op(B) K x n (B itself n x K with
+ * SBO_GZ_TRANS_B).  Each row of op(A) and each column of op(B) is scaled by a
+ * power of two above 1.01 times its largest magnitude, rounded to an integer
+ * of 8 nd - 1 bits and cut into nd balanced base-256 digits; digit products of
+ * level s + u < nd are summed exactly.  K in [1, 16384]; m == 0 or n == 0 is
+ * SBO_OK and writes nothing; bad sizes, digits or flag combinations are
+ * SBO_E_INVAL.  No inf, NaN or subnormal inside the logical operands. */
+#define SBO_GZ_TRI_A 1u        /* op(A) lower triangular: a_ik = 0 for k > i; the zero part is not read */
+#define SBO_GZ_TRANS_A 2u
+#define SBO_GZ_TRI_B_LOWER 4u  /* op(B) lower triangular: b_kj = 0 for k < j; the zero part is not read */
+#define SBO_GZ_TRI_B_UPPER 8u  /* op(B) upper triangular: b_kj = 0 for k > j; the zero part is not read */
+#define SBO_GZ_TRANS_B 16u
+#define SBO_GZ_TRANS_C 32u     /* C^T is stored: C points at n x m storage, ldc its leading dimension */
+#define SBO_GZ_BETA1 64u       /* C += instead of C = */
+#define SBO_GZ_LOWER_C 128u    /* (f32 only, not with SBO_GZ_TRANS_C) 128 x 128 tiles wholly above C's diagonal
+                                  are left alone; tiles that meet the diagonal are written whole */
+/* The f64 form (is_f32 == 0: double operands, nd 4, 5 or 6 -- the L^-1
+ * recursion's) or the f32 form (is_f32 != 0: float operands, nd 4 or 5).  The
+ * whole lda x a_cols, ldb x b_cols and ldc x c_cols buffers go to the device
+ * and the whole C buffer comes back, padding included. */
+SBO_API sbo_status sbo_debug_gz_gemm(sbo_ctx *ctx, int nd, int is_f32, const void *A, int64_t lda, int64_t a_cols,
+                                     const void *B, int64_t ldb, int64_t b_cols, int64_t m, int64_t n, int64_t K,
+                                     double alpha, void *C, int64_t ldc, int64_t c_cols, uint32_t flags);
+/* The Cholesky's form: the mpack x K f32 panel P (leading dimension ld) is cut
+ * into digits once, then C (m x n f32) = alpha P[a0 .. a0 + m) P[b0 .. b0 + n)^T
+ * (+ C) is read from that pack.  nd 4 or 5; a0 and b0 multiples of 128, both
+ * row ranges inside the pack; flags: SBO_GZ_BETA1, SBO_GZ_LOWER_C.  A
+ * 16-byte-aligned C with ldc % 4 == 0 takes the vector epilogue, any other the
+ * scalar one; the whole ld x K and ldc x c_cols buffers travel as above. */
+SBO_API sbo_status sbo_debug_gz_gemm_packed(sbo_ctx *ctx, int nd, const float *P, int64_t ld, int64_t mpack,
+                                            int64_t K, int64_t a0, int64_t m, int64_t b0, int64_t n, double alpha,
+                                            float *C, int64_t ldc, int64_t c_cols, uint32_t flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1181,8 +1181,10 @@ sbo_status refresh_operand(sbo_ctx *ctx, int64_t n_old = 0) {
     // The precision probe before the guard's reading (round 6): the guard's
     // three products on chk_stream run beside the probe's sweeps instead of
     // ahead of them (C4: the guard finished ~0.7 ms after the tail's last
-    // kernel).  If the guard then fires, the fit's inverse is redone and the
-    // probe with it.
+    // kernel).  If the guard then fires, the fit's inverse is redone, and the
+    // probe with it only because the fallback below resets probe_n first (as
+    // fill_and_factor does for new data): probe_precision has just set it to
+    // n, and probe_due() would keep the rejected inverse's readings.
     ctx->fitted = true;
     const sbo_status pst = probe_precision(ctx);
     if (pst != SBO_OK) return pst;   // (the drain waits for the guard)
@@ -1207,6 +1209,7 @@ sbo_status refresh_operand(sbo_ctx *ctx, int64_t n_old = 0) {
                 ctx->inv_oz_cur = ctx->inv_oz;
             else
                 ctx->inv_oz_off = true;
+            ctx->probe_n = 0;   // the probe above read the rejected inverse: measure the kept one
             const sbo_status st = refresh_operand(ctx, 0);
             ctx->inv_oz_off = false;
             const sbo_inv_check f = ctx->chk_res;
@@ -2491,6 +2494,84 @@ SBO_API sbo_status sbo_debug_x3_stamps(sbo_ctx *ctx, double *cycles, int n) {
     SBO_HIP(hipStreamSynchronize(ctx->stream));
     SBO_HIP(sbo::read_x3_stamps(cycles, n));
     return SBO_OK;
+}
+
+namespace {
+static_assert(SBO_GZ_TRI_A == sbo::kGzTriA && SBO_GZ_TRANS_A == sbo::kGzTransA &&
+                  SBO_GZ_TRI_B_LOWER == sbo::kGzTriBLower && SBO_GZ_TRI_B_UPPER == sbo::kGzTriBUpper &&
+                  SBO_GZ_TRANS_B == sbo::kGzTransB && SBO_GZ_TRANS_C == sbo::kGzTransC &&
+                  SBO_GZ_BETA1 == sbo::kGzBeta1 && SBO_GZ_LOWER_C == sbo::kGzLowerC,
+              "include/sbo.h documents the sliced GEMM's flags");
+// the sliced GEMM's own argument errors (hipErrorInvalidValue) are the caller's
+sbo_status gz_status(sbo_ctx *ctx, hipError_t e, const char *what) {
+    if (e == hipSuccess) return SBO_OK;
+    ctx->err = std::string(what) + ": " + hipGetErrorString(e);
+    return e == hipErrorInvalidValue ? SBO_E_INVAL : e == hipErrorOutOfMemory ? SBO_E_OOM : SBO_E_DEVICE;
+}
+}  // namespace
+
+SBO_API sbo_status sbo_debug_gz_gemm(sbo_ctx *ctx, int nd, int is_f32, const void *A, int64_t lda, int64_t a_cols,
+                                     const void *B, int64_t ldb, int64_t b_cols, int64_t m, int64_t n, int64_t K,
+                                     double alpha, void *C, int64_t ldc, int64_t c_cols, uint32_t flags) {
+    if (!ctx) return SBO_E_INVAL;
+    SBO_CHECK(A && B && C, SBO_E_INVAL, "sbo_debug_gz_gemm: null operand");
+    SBO_CHECK(m >= 0 && n >= 0 && K >= 0 && lda >= 1 && ldb >= 1 && ldc >= 1 && a_cols >= 1 && b_cols >= 1 &&
+                  c_cols >= 1,
+              SBO_E_INVAL, "sbo_debug_gz_gemm: negative size or empty buffer");
+    SBO_CHECK((flags & ~255u) == 0, SBO_E_INVAL, "sbo_debug_gz_gemm: unknown flag");
+    // the logical operands lie inside the buffers given (A is K x m with
+    // kGzTransA, B n x K with kGzTransB, C n x m with kGzTransC)
+    const bool tA = flags & sbo::kGzTransA, tB = flags & sbo::kGzTransB, tC = flags & sbo::kGzTransC;
+    SBO_CHECK((tA ? K : m) <= lda && (tA ? m : K) <= a_cols && (tB ? n : K) <= ldb && (tB ? K : n) <= b_cols &&
+                  (tC ? n : m) <= ldc && (tC ? m : n) <= c_cols,
+              SBO_E_INVAL, "sbo_debug_gz_gemm: operand larger than its buffer");
+    SBO_HIP(hipSetDevice(ctx->device));
+    const size_t es = is_f32 ? sizeof(float) : sizeof(double);
+    const size_t ab = es * (size_t)lda * (size_t)a_cols, bb = es * (size_t)ldb * (size_t)b_cols,
+                 cb = es * (size_t)ldc * (size_t)c_cols;
+    DevBuf dA, dB, dC, ws;
+    SBO_HIP(dA.reserve(ab));
+    SBO_HIP(dB.reserve(bb));
+    SBO_HIP(dC.reserve(cb));
+    SBO_HIP(ws.reserve(sbo::gz_workspace_bytes(std::max<int64_t>(m, 1), std::max<int64_t>(n, 1),
+                                               std::max<int64_t>(K, 1), std::min(std::max(nd, 4), 6))));
+    SBO_HIP(hipMemcpyAsync(dA.as<void>(), A, ab, hipMemcpyHostToDevice, ctx->stream));
+    SBO_HIP(hipMemcpyAsync(dB.as<void>(), B, bb, hipMemcpyHostToDevice, ctx->stream));
+    SBO_HIP(hipMemcpyAsync(dC.as<void>(), C, cb, hipMemcpyHostToDevice, ctx->stream));
+    const hipError_t e =
+        is_f32 ? sbo::launch_gz_gemm_f32(ctx->stream, nd, dA.as<float>(), lda, dB.as<float>(), ldb, m, n, K, alpha,
+                                         dC.as<float>(), ldc, flags, ws.as<char>())
+               : sbo::launch_gz_gemm(ctx->stream, nd, dA.as<double>(), lda, dB.as<double>(), ldb, m, n, K, alpha,
+                                     dC.as<double>(), ldc, flags, ws.as<char>());
+    if (e == hipSuccess) SBO_HIP(hipMemcpyAsync(C, dC.as<void>(), cb, hipMemcpyDeviceToHost, ctx->stream));
+    SBO_HIP(hipStreamSynchronize(ctx->stream));
+    return gz_status(ctx, e, "sbo_debug_gz_gemm");
+}
+
+SBO_API sbo_status sbo_debug_gz_gemm_packed(sbo_ctx *ctx, int nd, const float *P, int64_t ld, int64_t mpack,
+                                            int64_t K, int64_t a0, int64_t m, int64_t b0, int64_t n, double alpha,
+                                            float *C, int64_t ldc, int64_t c_cols, uint32_t flags) {
+    if (!ctx) return SBO_E_INVAL;
+    SBO_CHECK(P && C, SBO_E_INVAL, "sbo_debug_gz_gemm_packed: null operand");
+    SBO_CHECK(mpack >= 1 && K >= 1 && ld >= mpack && a0 >= 0 && b0 >= 0 && m >= 0 && n >= 0 && ldc >= 1 &&
+                  c_cols >= 1 && m <= ldc && n <= c_cols,
+              SBO_E_INVAL, "sbo_debug_gz_gemm_packed: size out of range or C larger than its buffer");
+    SBO_CHECK((flags & ~255u) == 0, SBO_E_INVAL, "sbo_debug_gz_gemm_packed: unknown flag");
+    SBO_HIP(hipSetDevice(ctx->device));
+    const size_t pb = sizeof(float) * (size_t)ld * (size_t)K, cb = sizeof(float) * (size_t)ldc * (size_t)c_cols;
+    DevBuf dP, dC, pack;
+    SBO_HIP(dP.reserve(pb));
+    SBO_HIP(dC.reserve(cb));
+    SBO_HIP(pack.reserve(sbo::gz_pack_bytes(mpack, K, std::min(std::max(nd, 4), 5))));
+    SBO_HIP(hipMemcpyAsync(dP.as<void>(), P, pb, hipMemcpyHostToDevice, ctx->stream));
+    SBO_HIP(hipMemcpyAsync(dC.as<void>(), C, cb, hipMemcpyHostToDevice, ctx->stream));
+    hipError_t e = sbo::launch_gz_pack_f32(ctx->stream, nd, dP.as<float>(), ld, mpack, K, pack.as<char>());
+    if (e == hipSuccess)
+        e = sbo::launch_gz_gemm_packed_f32(ctx->stream, nd, pack.as<char>(), mpack, K, a0, m, b0, n, alpha,
+                                           dC.as<float>(), ldc, flags);
+    if (e == hipSuccess) SBO_HIP(hipMemcpyAsync(C, dC.as<void>(), cb, hipMemcpyDeviceToHost, ctx->stream));
+    SBO_HIP(hipStreamSynchronize(ctx->stream));
+    return gz_status(ctx, e, "sbo_debug_gz_gemm_packed");
 }
 
 SBO_API sbo_status sbo_profile_mfma(sbo_ctx *ctx, double *mfma_flops, int64_t *tiles_by_level) {

@@ -44,6 +44,8 @@ def test_null_context_is_rejected_without_device():
     lib = N.lib()
     assert lib.sbo_fit(None, None, None, None, 0, N.sbo_hyper(0.4, 1, 0.1, 0), 0) == 1
     assert lib.sbo_tick(None, None, None, 0, 2.0, 0.0, 0, 0, None, None, None, None, None, None, 0) == 1
+    assert lib.sbo_debug_gz_gemm(None, 4, 0, None, 1, 1, None, 1, 1, 1, 1, 1, 1.0, None, 1, 1, 0) == 1
+    assert lib.sbo_debug_gz_gemm_packed(None, 4, None, 1, 1, 1, 0, 1, 0, 1, 1.0, None, 1, 1, 0) == 1
 
 
 def test_cpp_node_driver_builds_and_links():

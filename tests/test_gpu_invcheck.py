@@ -115,7 +115,20 @@ def test_guard_fires_on_five_digits(mapper):
     3.7e-6 in round 4 (profiles/r4_inv_oz_ab.log): the guard must see it, redo
     the inverse with dgemm products (err_fallback: that inverse's own measure,
     orders below), and the posterior must then meet the contract; with the
-    guard off the five-digit inverse stays and the posterior moves."""
+    guard off the five-digit inverse stays and the posterior moves.
+
+    The precision probe after the fallback (first item): the probe
+    runs before the guard is read, so when the guard fires it has measured the
+    REJECTED inverse; the fallback must measure again, on the inverse it
+    keeps.  probe_info() in three states -- A: the guard off (the five-digit
+    inverse kept), B: the guard fired, C: SBO_OPT_INV_OZ = 0 (the dgemm
+    inverse the fallback keeps).  A and C differ on err (another inverse,
+    another reading); B's readings must be C's: bitwise where the fallback's
+    posterior is C's bit for bit, else B != A and B.err within a tenth of
+    |A.err - C.err| of C.err.  Before the fix (probe_n not reset ahead of the
+    fallback's refresh_operand) B equalled A in every field.  Found on the
+    MI355X: see the printed line -- the fallback's mu and sd equal the
+    SBO_OPT_INV_OZ = 0 fit's bit for bit, and so do the probe's readings."""
     wl = workload(16384, True, Hyper())
     gm = TerrainMapper(0, wl.hyper, ctx=mapper.ctx)
     try:
@@ -131,6 +144,7 @@ def test_guard_fires_on_five_digits(mapper):
         assert chk["err"] > CHECK_TOL and chk["fired"] == 1
         assert 0.0 <= chk["err_fallback"] < CHECK_TOL / 10
         assert emu < REL_TOL and evar < REL_TOL
+        probe_b = gm.probe_info()
         # the guard off: the five-digit inverse is kept (and is visibly worse)
         gm.set_option(N.SBO_OPT_INV_CHECK, 0)
         gm.fit(wl.x, wl.y, wl.obs)
@@ -140,6 +154,24 @@ def test_guard_fires_on_five_digits(mapper):
         evar5 = nrel(sd5.astype(np.float64) ** 2, ovar)
         print(f"five digits, guard off: var {evar5:.2e}")
         assert evar5 > evar
+        probe_a = gm.probe_info()
+        # the inverse the fallback keeps, fitted directly
+        gm.set_option(N.SBO_OPT_INV_CHECK, 1)
+        gm.set_option(N.SBO_OPT_INV_OZ, 0)
+        gm.fit(wl.x, wl.y, wl.obs)
+        probe_c = gm.probe_info()
+        muc, sdc = gm.predict(wl.qx, wl.qy)
+        same = bool(np.array_equal(mu, muc) and np.array_equal(sd, sdc))
+        keys = ("precise", "err", "err_grid", "err_train", "var_min", "var_max", "var_max_grid", "var_max_train")
+        print(f"probe err: guard off {probe_a['err']!r} fired {probe_b['err']!r} dgemm {probe_c['err']!r}; "
+              f"fallback posterior bitwise the dgemm fit's: {same}")
+        assert probe_a["n_at_probe"] == probe_b["n_at_probe"] == probe_c["n_at_probe"] == 16384
+        assert probe_a["err"] != probe_c["err"]
+        if same:
+            assert {k: probe_b[k] for k in keys} == {k: probe_c[k] for k in keys}
+        else:
+            assert {k: probe_b[k] for k in keys} != {k: probe_a[k] for k in keys}
+            assert abs(probe_b["err"] - probe_c["err"]) <= abs(probe_a["err"] - probe_c["err"]) / 10
     finally:
         gm.set_option(N.SBO_OPT_INV_OZ, 6)
         gm.set_option(N.SBO_OPT_INV_CHECK, 1)
