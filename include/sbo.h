@@ -88,13 +88,21 @@ SBO_API const char *sbo_last_error(const sbo_ctx *ctx);
  * the library's blocked Cholesky (SBO_OPT_CHOLESKY), L^-1 in f64 by its block
  * recursion (SBO_OPT_INVERSE), alpha = L^-T L^-1 (y - m0) from that inverse,
  * the packed predictive operand and its tile bounds, and the precision probe
- * (SBO_OPT_PRECISION).  Replaces the mapper's fit behind the service. */
+ * (SBO_OPT_PRECISION).  Replaces the mapper's fit behind the service.
+ * Rejected arguments (SBO_E_INVAL, SBO_E_EMPTY) leave a fitted context as it
+ * was.  Any error after argument validation (SBO_E_NOT_SPD included) leaves
+ * the context unfitted: sbo_num_train is 0, and it accepts a new sbo_fit,
+ * sbo_import_state or option calls only (everything else: SBO_E_STATE). */
 SBO_API sbo_status sbo_fit(sbo_ctx *ctx, const float *x, const float *y, const float *obs,
                            int64_t n, sbo_hyper hyper, uint32_t flags);
 
 /* Streaming update (C5): append b measurements with a block Cholesky update
  * (L21 = K21 L11^-T, L22 = chol(K22 - L21 L21^T)), then re-solve alpha.
- * Replaces a full re-fit on each spatial_data_size change (:552-566). */
+ * Replaces a full re-fit on each spatial_data_size change (:552-566).
+ * Rejected arguments leave the fitted context as it was.  Any error after
+ * argument validation (SBO_E_NOT_SPD of the updated block included, in the
+ * block update and in the SBO_OPT_RESORT re-sort alike) leaves the context
+ * unfitted, as a failed sbo_fit does: refit all the points. */
 SBO_API sbo_status sbo_append(sbo_ctx *ctx, const float *x, const float *y, const float *obs,
                               int64_t b, uint32_t flags);
 
@@ -232,7 +240,10 @@ SBO_API sbo_status sbo_get_jitter(const sbo_ctx *ctx, double *jitter);
  * identical sweeps) but holds no factor: sbo_append / sbo_get_factor return
  * SBO_E_STATE until the next sbo_fit.  sbo_import_state rejects
  * (SBO_E_INVAL) a blob whose magic, size, section offsets, header fields
- * or training order do not match what (n, npad) implies. */
+ * or training order do not match what (n, npad) implies.  A rejected buffer
+ * or header leaves a fitted context as it was; any error after the header is
+ * accepted (a failed copy, a training order that is no permutation) leaves
+ * the context unfitted, as a failed sbo_fit does. */
 SBO_API sbo_status sbo_state_bytes(sbo_ctx *ctx, int64_t *bytes);
 SBO_API sbo_status sbo_export_state(sbo_ctx *ctx, void *dev_buf, int64_t cap);
 SBO_API sbo_status sbo_import_state(sbo_ctx *ctx, const void *dev_buf, int64_t bytes);
@@ -305,13 +316,11 @@ SBO_API sbo_status sbo_kd_order(const float *x, const float *y, int64_t n, int64
  * to the same error budget as the skipped tiles (SBO_OPT_SKIP_BUDGET);
  * 22 = variant 3 with every kept tile at six products (f32-accurate:
  * variance error vs a host f64 sweep 5.07e-6 at N = 16384 against 5.00e-6
- * for variant 0); 2 = variant 22 with four waves of 32 queries; 0 = f32
- * MFMA (16x16x4) with an f32 cross-tile accumulator; 1 = variant 0 with an
- * f64 one; 9, 10 = variant 22 with the A stage issued in one burst per
- * step, resp. A fragments read one row block ahead; 13 = the 32x32x16
- * shape.  Any other value: SBO_E_INVAL.  (The timing diagnostics -- some
- * leave parts of the work out -- exist only in the diagnostic build
- * lib/libsbo_diag.so, never in this library.) */
+ * for variant 0); 0 = f32 MFMA (16x16x4) with an f32 cross-tile
+ * accumulator; 1 = variant 0 with an f64 one.  Any other value: SBO_E_INVAL.
+ * (The other shapes and the timing diagnostics -- some leave parts of the
+ * work out -- exist only in the diagnostic build lib/libsbo_diag.so, never
+ * in this library.) */
 #define SBO_OPT_KERNEL_VARIANT 5
 /* SBO_OPT_SWEEP_GROUPS: workgroups of the persistent predictive sweep, each
  * walking one tile-balanced range of the tick's plan; 0 = default (one per

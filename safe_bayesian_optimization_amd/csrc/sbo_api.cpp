@@ -127,21 +127,30 @@ int inverse_base_cases(int64_t n, int64_t base) {
     return inverse_base_cases(h, base) + inverse_base_cases(n - h, base);
 }
 
+// How one inverse runs its recursion: the digits of its int8-sliced products
+// (0: every product a dgemm), and whether its base cases are already inverted
+// (inverse_leaves ran: the recursion then only counts their info slots).
+struct InvMode {
+    int digits = 0;
+    bool leaves_done = false;
+};
 sbo_status inverse_lower_f64(sbo_ctx *ctx, rocblas_handle hb, double *Li, int64_t n, int64_t ld, double *S,
-                             int &slot, sbo::DevBuf *ozws = nullptr);
+                             int &slot, InvMode mode, sbo::DevBuf *ozws = nullptr);
 // SBO_OPT_INV_OZ: a level of the recursion whose split is at least
 // SBO_OPT_INV_OZ_MIN runs its two products as the sliced GEMM (K <= 16384);
 // the levels below keep dgemms.  Automatic (0, default): 2048 in the inverses
 // of N >= 12288 (C4: fit 42.0 -> 41.3 ms, profiles/r5_inv_oz_min_gz16.log),
 // else 4096 (below that the 2048 level's products are too small to pay for
 // their packs, and a sliced inverse brings the guard's check)
-bool oz_level(const sbo_ctx *ctx, int64_t h, int64_t m) {
+bool oz_level(const sbo_ctx *ctx, int digits, int64_t h, int64_t m) {
     const int64_t mn = ctx->inv_oz_min > 0 ? ctx->inv_oz_min : (ctx->n >= 12288 ? 2048 : 4096);
-    return ctx->inv_oz != 0 && !ctx->inv_oz_off && h >= mn && h <= 16384 && m <= 16384;
+    return digits != 0 && h >= mn && h <= 16384 && m <= 16384;
 }
 // The digits of the current fit's sliced products (SBO_OPT_INV_OZ_ADAPT:
-// chosen per fit by choose_inv_digits)
-int inv_digits(const sbo_ctx *ctx) { return ctx->inv_oz_cur > 0 ? ctx->inv_oz_cur : ctx->inv_oz; }
+// chosen per fit by choose_inv_digits; 0 with SBO_OPT_INV_OZ 0)
+int inv_digits(const sbo_ctx *ctx) {
+    return ctx->inv_oz == 0 ? 0 : ctx->inv_oz_cur > 0 ? ctx->inv_oz_cur : ctx->inv_oz;
+}
 // SBO_OPT_INV_OZ_ADAPT: the guard's readings of a sliced inverse (its
 // effect on the variance and on the mean at 31 queries) grow ~256x per digit
 // dropped -- the digits' truncation and the dropped digit products are 2^-8
@@ -234,10 +243,10 @@ void record_inv_digits(sbo_ctx *ctx, const sbo_inv_check &r) {
 // down only when the top split slices (the levels below slice with them
 // where oz_level allows; with the top split over 16384 it is all dgemm), and
 // only on the two-stream path.
-bool inverse_sliced(const sbo_ctx *ctx, int64_t n) {
+bool inverse_sliced(const sbo_ctx *ctx, int digits, int64_t n) {
     if (n <= ctx->inv_base || !ctx->blas_aux || !ctx->aux_stream || !ctx->ev_panel) return false;
     const int64_t h = inverse_split(n, ctx->inv_base);
-    return ctx->inv_oz != 0 && oz_level(ctx, h, n - h);
+    return oz_level(ctx, digits, h, n - h);
 }
 
 // A^-1 (recursion scratch scr), then S = B A^-1
@@ -253,15 +262,16 @@ int64_t inverse_panel(const sbo_ctx *ctx, int64_t h) {
 }
 
 sbo_status inverse_first_half(sbo_ctx *ctx, rocblas_handle hb, double *Li, int64_t n, int64_t ld, double *S,
-                              double *scr, int &slot, bool a_done = false, sbo::DevBuf *ozws = nullptr) {
+                              double *scr, int &slot, InvMode mode, bool a_done = false,
+                              sbo::DevBuf *ozws = nullptr) {
     const int64_t h = inverse_split(n, ctx->inv_base), m = n - h;
     if (!a_done)
-        if (sbo_status st = inverse_lower_f64(ctx, hb, Li, h, ld, scr, slot, ozws); st != SBO_OK) return st;
-    if (ozws && oz_level(ctx, h, m)) {   // S = L21 A^-1 in one sliced GEMM (A^-1 lower triangular)
+        if (sbo_status st = inverse_lower_f64(ctx, hb, Li, h, ld, scr, slot, mode, ozws); st != SBO_OK) return st;
+    if (ozws && oz_level(ctx, mode.digits, h, m)) {   // S = L21 A^-1 in one sliced GEMM (A^-1 lower triangular)
         hipStream_t st;
         SBO_BLAS(rocblas_get_stream(hb, &st));
-        SBO_HIP(ozws->reserve(sbo::gz_workspace_bytes(m, h, h, inv_digits(ctx))));
-        SBO_HIP(sbo::launch_gz_gemm(st, inv_digits(ctx), Li + h, ld, Li, ld, m, h, h, 1.0, S, m, sbo::kGzTriBLower,
+        SBO_HIP(ozws->reserve(sbo::gz_workspace_bytes(m, h, h, mode.digits)));
+        SBO_HIP(sbo::launch_gz_gemm(st, mode.digits, Li + h, ld, Li, ld, m, h, h, 1.0, S, m, sbo::kGzTriBLower,
                                     ozws->as<char>()));
         return SBO_OK;
     }
@@ -279,20 +289,21 @@ sbo_status inverse_first_half(sbo_ctx *ctx, rocblas_handle hb, double *Li, int64
 
 // C^-1 (recursion scratch scr; skipped when c_done), then X21 = -C^-1 S
 sbo_status inverse_second_half(sbo_ctx *ctx, rocblas_handle hb, double *Li, int64_t n, int64_t ld, double *S,
-                               double *scr, int &slot, bool c_done = false, sbo::DevBuf *ozws = nullptr) {
+                               double *scr, int &slot, InvMode mode, bool c_done = false,
+                               sbo::DevBuf *ozws = nullptr) {
     const int64_t h = inverse_split(n, ctx->inv_base), m = n - h;
     double *B = Li + h, *C = Li + h + h * ld;
     if (!c_done)
-        if (sbo_status st = inverse_lower_f64(ctx, hb, C, m, ld, scr, slot, ozws); st != SBO_OK) return st;
-    if (ozws && oz_level(ctx, h, m)) {
+        if (sbo_status st = inverse_lower_f64(ctx, hb, C, m, ld, scr, slot, mode, ozws); st != SBO_OK) return st;
+    if (ozws && oz_level(ctx, mode.digits, h, m)) {
         // X21 = -C^-1 S in one sliced GEMM, as X21^T = -S^T C^-T: the
         // triangular operand then bounds the k loop per column tile, so the
         // workgroups of one column run in step as in S = L21 A^-1 (the direct
         // form, C^-1 as a lower-triangular op(A): 7.4 vs 5.x ms at C4)
         hipStream_t st;
         SBO_BLAS(rocblas_get_stream(hb, &st));
-        SBO_HIP(ozws->reserve(sbo::gz_workspace_bytes(h, m, m, inv_digits(ctx))));
-        SBO_HIP(sbo::launch_gz_gemm(st, inv_digits(ctx), S, m, C, ld, h, m, m, -1.0, B, ld,
+        SBO_HIP(ozws->reserve(sbo::gz_workspace_bytes(h, m, m, mode.digits)));
+        SBO_HIP(sbo::launch_gz_gemm(st, mode.digits, S, m, C, ld, h, m, m, -1.0, B, ld,
                                     sbo::kGzTransA | sbo::kGzTransB | sbo::kGzTriBUpper | sbo::kGzTransC,
                                     ozws->as<char>()));
         return SBO_OK;
@@ -310,18 +321,18 @@ sbo_status inverse_second_half(sbo_ctx *ctx, rocblas_handle hb, double *Li, int6
 }
 
 sbo_status inverse_lower_f64(sbo_ctx *ctx, rocblas_handle hb, double *Li, int64_t n, int64_t ld, double *S,
-                             int &slot, sbo::DevBuf *ozws) {
+                             int &slot, InvMode mode, sbo::DevBuf *ozws) {
     if (n <= ctx->inv_base) {
         rocblas_int *info = ctx->info.as<rocblas_int>() + 1 + slot++;
-        if (!ctx->inv_leaves_done)
+        if (!mode.leaves_done)
             SBO_BLAS(rocsolver_dtrtri(hb, rocblas_fill_lower, rocblas_diagonal_non_unit, (rocblas_int)n, Li,
                                       (rocblas_int)ld, info));
         return SBO_OK;
     }
     const int64_t h = inverse_split(n, ctx->inv_base), m = n - h;
-    if (sbo_status st = inverse_first_half(ctx, hb, Li, n, ld, S, S + h * m, slot, false, ozws); st != SBO_OK)
+    if (sbo_status st = inverse_first_half(ctx, hb, Li, n, ld, S, S + h * m, slot, mode, false, ozws); st != SBO_OK)
         return st;
-    return inverse_second_half(ctx, hb, Li, n, ld, S, S + h * m, slot, false, ozws);
+    return inverse_second_half(ctx, hb, Li, n, ld, S, S + h * m, slot, mode, false, ozws);
 }
 
 // Every base case of the recursion over the n columns at Li -- the b x b
@@ -411,10 +422,12 @@ sbo_status inverse_leaves(sbo_ctx *ctx, rocblas_handle hb, double *Li, int64_t n
 // those 3 ms; profiles/r3_fit_timeline_invorder.txt).  Scratch:
 // inverse_scratch_par(n); info slots as the sequential recursion's (C's base
 // cases after A's).
-sbo_status inverse_lower_f64_par(sbo_ctx *ctx, double *Li, int64_t n, int64_t ld, double *S) {
+// mode.digits != 0: the top split slices (inverse_sliced; the refresh plan
+// decides it once).
+sbo_status inverse_lower_f64_par(sbo_ctx *ctx, double *Li, int64_t n, int64_t ld, double *S, InvMode mode) {
     int slot = 0;
     if (n <= ctx->inv_base || !ctx->blas_aux || !ctx->aux_stream || !ctx->ev_panel)
-        return inverse_lower_f64(ctx, ctx->blas, Li, n, ld, S, slot);
+        return inverse_lower_f64(ctx, ctx->blas, Li, n, ld, S, slot, mode);
     const int64_t h = inverse_split(n, ctx->inv_base), m = n - h;
     double *scrA = S + h * m, *scrC = scrA + inverse_scratch(h, ctx->inv_base);
     int slotC = inverse_base_cases(h, ctx->inv_base);
@@ -422,29 +435,29 @@ sbo_status inverse_lower_f64_par(sbo_ctx *ctx, double *Li, int64_t n, int64_t ld
     // int8 matrix cores (oz_level), one workspace per stream, sized up front
     // (a reserve that reallocates mid-fit would wait for the device)
     sbo::DevBuf *ozA = nullptr, *ozC = nullptr;
-    if (inverse_sliced(ctx, n)) {
-        SBO_HIP(ctx->gzws.reserve(std::max(sbo::gz_workspace_bytes(m, h, h, inv_digits(ctx)),
-                                           sbo::gz_workspace_bytes(h, m, m, inv_digits(ctx)))));
-        SBO_HIP(ctx->gzws_aux.reserve(sbo::gz_workspace_bytes(m, m, m, inv_digits(ctx))));
+    if (mode.digits != 0) {
+        SBO_HIP(ctx->gzws.reserve(std::max(sbo::gz_workspace_bytes(m, h, h, mode.digits),
+                                           sbo::gz_workspace_bytes(h, m, m, mode.digits))));
+        SBO_HIP(ctx->gzws_aux.reserve(sbo::gz_workspace_bytes(m, m, m, mode.digits)));
         ozA = &ctx->gzws;
         ozC = &ctx->gzws_aux;
     }
     SBO_HIP(hipEventRecord(ctx->ev_panel, ctx->stream));            // Li widened
-    if (sbo_status st = inverse_lower_f64(ctx, ctx->blas, Li, h, ld, scrA, slot, ozA); st != SBO_OK) return st;
+    if (sbo_status st = inverse_lower_f64(ctx, ctx->blas, Li, h, ld, scrA, slot, mode, ozA); st != SBO_OK) return st;
     SBO_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_panel, 0));
     SBO_BLAS(rocblas_set_pointer_mode(ctx->blas_aux, rocblas_pointer_mode_host));
-    if (sbo_status st = inverse_lower_f64(ctx, ctx->blas_aux, Li + h + h * ld, m, ld, scrC, slotC, ozC);
+    if (sbo_status st = inverse_lower_f64(ctx, ctx->blas_aux, Li + h + h * ld, m, ld, scrC, slotC, mode, ozC);
         st != SBO_OK) {
         (void)hipStreamSynchronize(ctx->aux_stream);
         return st;
     }
     SBO_HIP(hipEventRecord(ctx->ev_trail, ctx->aux_stream));
-    if (sbo_status st = inverse_first_half(ctx, ctx->blas, Li, n, ld, S, scrA, slot, true, ozA); st != SBO_OK) {
+    if (sbo_status st = inverse_first_half(ctx, ctx->blas, Li, n, ld, S, scrA, slot, mode, true, ozA); st != SBO_OK) {
         (void)hipStreamSynchronize(ctx->aux_stream);
         return st;
     }
     SBO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_trail, 0));
-    return inverse_second_half(ctx, ctx->blas, Li, n, ld, S, nullptr, slot, true, ozA);
+    return inverse_second_half(ctx, ctx->blas, Li, n, ld, S, nullptr, slot, mode, true, ozA);
 }
 
 sbo_status check_hyper(sbo_ctx *ctx, const sbo_hyper &h) {
@@ -679,9 +692,17 @@ hipError_t grow_keep(sbo_ctx *ctx, DevBuf &buf, size_t bytes, size_t keep) {
 // split sweep, 1 the precise f64 sweep under its budget, 2 the precise sweep
 // under a 2^-kProbeRefBits budget relative to the probe's largest variance (the probe's reference)
 constexpr int kSweepCtx = -1, kSweepFast = 0, kSweepPrecise = 1, kSweepPreciseDense = 2;
+// The Morton order of one query set (pointers into qwork, valid while qwork
+// is untouched): a tick given an empty one fills it, a tick given a filled
+// one sweeps in that order instead of sorting again (the probe's two sweeps).
+struct QueryOrder {
+    int32_t *perm = nullptr;
+    float *sx = nullptr, *sy = nullptr;
+};
 sbo_status run_tick(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, double beta, double f_min,
                     int score_kind, int64_t index_offset, float *mu, float *sd, double *lo, double *hi,
-                    uint8_t *safe, sbo_key *key_dev, float *cost = nullptr, int sweep = kSweepCtx);
+                    uint8_t *safe, sbo_key *key_dev, float *cost = nullptr, int sweep = kSweepCtx,
+                    QueryOrder *order = nullptr);
 sbo_status probe_precision(sbo_ctx *ctx);
 // the precision probe runs on this refresh (probe_precision): on a fresh fit,
 // and on appends once N has grown by SBO_OPT_REPROBE % (default a quarter)
@@ -701,6 +722,38 @@ sbo_status drain_poz(sbo_ctx *ctx) {
     return SBO_OK;
 }
 
+// Wait (host) for an accuracy guard still running on chk_stream: it reads L,
+// L^-1, x/y/obs and ctx->chk, so whoever abandons a refresh waits for it
+// before those buffers are regrown, freed or rewritten.
+void drain_guard(sbo_ctx *ctx) {
+    if (ctx->chk_stream) (void)hipStreamSynchronize(ctx->chk_stream);
+}
+
+// The one commit point of the calls that rebuild the model (sbo_fit,
+// sbo_append, sbo_import_state), armed once their arguments are accepted and
+// drain_poz has run.  From then on the context counts as fitted only through
+// commit(): every other way out -- an error return of any stage, the probe
+// and the guard's reading included -- leaves it unfitted with no inverse to
+// extend and no guard in flight, so that it accepts a new sbo_fit, an import
+// or option calls and nothing else.
+struct FitCommit {
+    sbo_ctx *ctx;
+    bool committed = false;
+    explicit FitCommit(sbo_ctx *c) : ctx(c) {}
+    sbo_status commit(sbo_status st) {
+        if (st != SBO_OK) return st;
+        ctx->fitted = true;
+        committed = true;
+        return SBO_OK;
+    }
+    ~FitCommit() {
+        if (committed) return;
+        ctx->fitted = false;
+        ctx->linv_n = 0;
+        drain_guard(ctx);
+    }
+};
+
 // The precise operand's buffers for npad rows, keeping the row blocks below
 // I0 (grow_keep copies on `stream` and waits for it: the fit reserves them
 // before it forks work onto aux_stream, so that the fork is not serialised).
@@ -719,21 +772,16 @@ sbo_status reserve_precise(sbo_ctx *ctx, int64_t npad, int64_t I0) {
 
 // The precise sweep's operand (SBO_OPT_PRECISE_KERNEL: f64 tiles or int8
 // digit tiles) for row blocks >= I0 of npad rows, from the f64 inverse and
-// alpha64, on stream s (the buffers grow keeping the row blocks below I0).
+// alpha64, on stream s (the buffers grow as in reserve_precise).
 sbo_status pack_precise(sbo_ctx *ctx, hipStream_t s, int64_t npad, int64_t I0) {
-    if (sbo_status st = drain_poz(ctx)) return st;
+    if (sbo_status st = reserve_precise(ctx, npad, I0)) return st;
     const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
     if (ctx->precise_kernel >= 1) {
-        SBO_HIP(grow_keep(ctx, ctx->aoz, sbo::oz_operand_bytes(npad), sbo::oz_operand_bytes(I0 * sbo::kBM)));
-        SBO_HIP(grow_keep(ctx, ctx->eoz, sbo::oz_exp_bytes(npad), sbo::oz_exp_bytes(I0 * sbo::kBM)));
-        SBO_HIP(ctx->koz.reserve(sbo::oz_coord_bytes(npad)));
         SBO_HIP(sbo::launch_pack_oz(s, ctx->Linv.as<double>(), ctx->cap, ctx->n, npad, I0, sf2, ctx->x.as<float>(),
                                     ctx->y.as<float>(), ctx->alpha64.as<double>(), ctx->aoz.as<char>(),
                                     ctx->eoz.as<int>(), ctx->koz.as<char>(),
                                     ctx->precise_kernel == 4 || ctx->precise_kernel == 10));
     } else {
-        SBO_HIP(grow_keep(ctx, ctx->a64, sbo::f64_operand_bytes(npad), sbo::f64_operand_bytes(I0 * sbo::kBM)));
-        SBO_HIP(ctx->kc64.reserve(sbo::f64_coord_bytes(npad)));
         SBO_HIP(sbo::launch_pack_f64(s, ctx->Linv.as<double>(), ctx->cap, ctx->n, npad, I0, sf2, ctx->x.as<float>(),
                                      ctx->y.as<float>(), ctx->alpha64.as<double>(), ctx->a64.as<double>(),
                                      ctx->kc64.as<double>()));
@@ -756,6 +804,24 @@ sbo_status pack_precise(sbo_ctx *ctx, hipStream_t s, int64_t npad, int64_t I0) {
 // whole-grid / probe ratio measured.
 constexpr int kChkGrid = 4, kChkQueries = sbo::kChkQ - 1, kChkTrain = kChkQueries - kChkGrid * kChkGrid;
 constexpr double kInvCheckTol = 5e-7;
+// The two ingredients the guard's and the probe's query sets share: a g x g
+// lattice over the training box, corners included (x at hx[i g + j], y at
+// hy[i g + j]), and every stride-th stored point from stride / 2 on (count of
+// them, a strided 2-D copy on stream s).
+void bbox_lattice(const float bbox[4], int g, float *hx, float *hy) {
+    for (int i = 0; i < g; ++i)
+        for (int j = 0; j < g; ++j) {
+            hx[i * g + j] = bbox[0] + (bbox[1] - bbox[0]) * (float)j / (float)(g - 1);
+            hy[i * g + j] = bbox[2] + (bbox[3] - bbox[2]) * (float)i / (float)(g - 1);
+        }
+}
+sbo_status copy_strided_points(sbo_ctx *ctx, hipStream_t s, int64_t stride, int64_t count, float *qx, float *qy) {
+    SBO_HIP(hipMemcpy2DAsync(qx, sizeof(float), ctx->x.as<float>() + stride / 2, sizeof(float) * stride,
+                             sizeof(float), (size_t)count, hipMemcpyDeviceToDevice, s));
+    SBO_HIP(hipMemcpy2DAsync(qy, sizeof(float), ctx->y.as<float>() + stride / 2, sizeof(float) * stride,
+                             sizeof(float), (size_t)count, hipMemcpyDeviceToDevice, s));
+    return SBO_OK;
+}
 sbo_status inverse_check_launch(sbo_ctx *ctx) {
     const int64_t n = ctx->n;
     if (!ctx->chk_stream) {
@@ -770,12 +836,7 @@ sbo_status inverse_check_launch(sbo_ctx *ctx) {
                                   0.0, ctx->chk.as<void>(), &q, &cs));
     static thread_local std::vector<float> hq;   // (lives until the copy below has run)
     hq.assign(2 * kChkGrid * kChkGrid, 0.0f);
-    for (int i = 0; i < kChkGrid; ++i)
-        for (int j = 0; j < kChkGrid; ++j) {
-            hq[i * kChkGrid + j] = ctx->bbox[0] + (ctx->bbox[1] - ctx->bbox[0]) * (float)j / (float)(kChkGrid - 1);
-            hq[kChkGrid * kChkGrid + i * kChkGrid + j] =
-                ctx->bbox[2] + (ctx->bbox[3] - ctx->bbox[2]) * (float)i / (float)(kChkGrid - 1);
-        }
+    bbox_lattice(ctx->bbox, kChkGrid, hq.data(), hq.data() + kChkGrid * kChkGrid);
     SBO_HIP(hipEventRecord(ctx->ev_panel, ctx->stream));   // the inverse is done
     SBO_HIP(hipStreamWaitEvent(ctx->chk_stream, ctx->ev_panel, 0));
     SBO_HIP(hipEventRecord(ctx->ev_chk0, ctx->chk_stream));
@@ -786,10 +847,7 @@ sbo_status inverse_check_launch(sbo_ctx *ctx) {
     // fewer points repeat the last one)
     const int64_t stride = std::max<int64_t>(1, n / kChkTrain);
     const int64_t mt = std::min<int64_t>(kChkTrain, (n - stride / 2 + stride - 1) / stride);
-    SBO_HIP(hipMemcpy2DAsync(q + G, sizeof(float), ctx->x.as<float>() + stride / 2, sizeof(float) * stride,
-                             sizeof(float), (size_t)mt, hipMemcpyDeviceToDevice, ctx->chk_stream));
-    SBO_HIP(hipMemcpy2DAsync(q + Q + G, sizeof(float), ctx->y.as<float>() + stride / 2, sizeof(float) * stride,
-                             sizeof(float), (size_t)mt, hipMemcpyDeviceToDevice, ctx->chk_stream));
+    if (sbo_status st = copy_strided_points(ctx, ctx->chk_stream, stride, mt, q + G, q + Q + G)) return st;
     for (int64_t c = G + mt; c < kChkQueries; ++c) {
         SBO_HIP(hipMemcpyAsync(q + c, q + G + mt - 1, sizeof(float), hipMemcpyDeviceToDevice, ctx->chk_stream));
         SBO_HIP(hipMemcpyAsync(q + Q + c, q + Q + G + mt - 1, sizeof(float), hipMemcpyDeviceToDevice,
@@ -842,391 +900,510 @@ sbo_status inverse_check_read(sbo_ctx *ctx, sbo_inv_check &r) {
     return SBO_OK;
 }
 
-// Rebuild alpha, L^-1 and the packed predictive operand from the current L.
-// n_old > 0 (an append of rows n_old..n-1 to an unchanged leading factor):
-// with the f64 inverse of the leading block kept from the last refresh, only
-// the new rows of L^-1 are computed,
-//     [L11  0 ]^-1   [ L11^-1                  0     ]
-//     [L21 L22]    = [ -L22^-1 L21 L11^-1   L22^-1 ]
-// (one b x b dtrtri and two dtrmm, O(b n^2) instead of O(n^3)), and only the
-// row blocks that hold new rows are repacked.  alpha, the per-k coordinates
-// and the tile boxes are rebuilt in full (O(n^2) and O(n)).
-sbo_status refresh_operand(sbo_ctx *ctx, int64_t n_old = 0) {
-    if (sbo_status st = drain_poz(ctx)) return st;
-    const int64_t n = ctx->n, ld = ctx->cap;
-    const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
-    float *L = ctx->L.as<float>();
-    float *alpha = ctx->alpha.as<float>();
-    const int64_t nslots = info_slots(n);
+// What blocked_potrf hands to the refresh of the factor it just wrote.
+struct FactorHandover {
+    int64_t widened_n = 0;   // the factor (n columns) is already widened into Linv
+    int64_t half_n = 0;      // n of a factor whose inverse's first half is done (inverse_finish_half ends it)
+    int half_slots = 0;      // the info slots that half used (1 .. half_slots)
+};
+
+// The guard's ladder (refresh_operand): the digits chosen for this fit, then
+// SBO_OPT_INV_OZ digits, then dgemm products.
+enum InvAttempt { kInvChosen, kInvFullDigits, kInvDgemm };
+
+// Everything one refresh decides, once, before its first launch: the stages
+// below read it and none of them looks the conditions up again.
+struct RefreshPlan {
+    int64_t n, ld, npad, nI;
+    double sf2;
+    bool f64;            // SBO_OPT_INVERSE_BITS 64 (else the f32 strtri path, refresh_f32)
+    bool incr;           // an append with the leading block's f64 inverse kept: only rows n_old.. are new
+    int64_t n_old, I0;   // (I0: first row block holding new rows)
+    size_t old_tiles;    // packed tiles of the row blocks below I0, kept
+    bool half_done;      // the inverse's first half ran beside the Cholesky (blocked_potrf) ...
+    int half_slots;      // ... its info slots 1 .. half_slots stay, the rest are cleared
+    bool widened;        // the factor is already widened into Linv
+    int digits;          // of this inverse's sliced products (0: dgemm)
+    bool guard;          // the accuracy guard runs on this inverse
+    bool inc_alpha;      // alpha updated from the kept z instead of solved in full
+    bool aux;            // alpha and the derived operands go to aux_stream
+    bool eager_x3, eager_f64;
+    int x3_layout;
+    bool fused_norms;    // the tile norms ran with the pack (SBO_FUSED_TN)
+};
+RefreshPlan plan_refresh(const sbo_ctx *ctx, int64_t n_old, const FactorHandover &ho, InvAttempt attempt) {
+    RefreshPlan p{};
+    p.n = ctx->n;
+    p.ld = ctx->cap;
+    p.npad = sbo::round_up(p.n, sbo::kBM);
+    p.nI = p.npad / sbo::kBM;
+    p.sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
+    p.f64 = ctx->inverse_bits == 64;
+    p.incr = n_old > 0 && p.f64 && ctx->linv_n == n_old && ctx->npad > 0;
+    p.n_old = p.incr ? n_old : 0;
+    p.I0 = p.n_old / sbo::kBM;
+    p.old_tiles = (size_t)sbo::total_tiles(p.I0);
+    p.half_done = p.f64 && ctx->inverse_rec && !p.incr && ho.half_n == p.n;
+    p.half_slots = ho.half_slots;
+    p.widened = ho.widened_n == p.n;
+    const int want = attempt == kInvDgemm ? 0 : attempt == kInvFullDigits ? ctx->inv_oz : inv_digits(ctx);
+    const bool sliced = p.f64 && !p.incr && ctx->inverse_rec && !p.half_done && inverse_sliced(ctx, want, p.n);
+    p.digits = sliced ? want : 0;
+    p.guard = p.f64 && !p.incr &&
+              (ctx->inv_check == 2 || attempt == kInvDgemm || (ctx->inv_check == 1 && sliced));
+    p.inc_alpha = p.incr && ctx->z_n == n_old && p.n - n_old <= kAppendInvGemm;
+    p.aux = p.f64 && ctx->blas_aux && ctx->aux_stream && ctx->ev_panel && ctx->ev_pack;
+    p.eager_x3 = p.aux && ctx->kernel_variant >= 2;
+    p.eager_f64 =
+        p.aux && ctx->precision_opt != 0 && (probe_due(ctx) || ctx->precise || ctx->precision_opt == 1);
+    p.x3_layout = sbo::x3_layout(ctx->kernel_variant);
+    p.fused_norms = p.f64 && SBO_FUSED_TN;
+    return p;
+}
+
+// The buffers every refresh writes, and the rocSOLVER info slots cleared (a
+// first half that ran beside the Cholesky keeps its own).
+sbo_status refresh_begin(sbo_ctx *ctx, const RefreshPlan &p) {
+    const int64_t nslots = info_slots(p.n);
     SBO_HIP(ctx->info.reserve(sizeof(rocblas_int) * (size_t)nslots));
     rocblas_int *info = ctx->info.as<rocblas_int>();
-
-    // L^-1 (lower, non-unit).  Default: widen L to f64 and invert with dtrtri
-    // (f64 MFMA), then round sf2 * L^-1 to f32 once while packing -- the f32
-    // strtri path adds its own inversion error on top of the f32
-    // representation error (SBO_OPT_INVERSE_BITS = 32 selects it).
-    const int64_t npad = sbo::round_up(n, sbo::kBM);
-    const int64_t nI = npad / sbo::kBM;
-    const bool incr = n_old > 0 && ctx->inverse_bits == 64 && ctx->linv_n == n_old && ctx->npad > 0;
-    const int64_t I0 = incr ? n_old / sbo::kBM : 0;  // first row block holding new rows
-    const size_t old_tiles = incr ? (size_t)sbo::total_tiles(I0) : 0;
-    SBO_HIP(grow_keep(ctx, ctx->aug, sizeof(float) * (size_t)sbo::total_tiles(nI) * sbo::kTileFloats,
-                      sizeof(float) * old_tiles * sbo::kTileFloats));
-    SBO_HIP(ctx->kcoord.reserve(sizeof(float) * (size_t)(npad / sbo::kBK) * 3 * sbo::kBK));
-    rocblas_int hinfo = 0;
-    bool alpha_aux = false, kcoord_pending = false, x3_planes_aux = false, packs_aux = false, chk_pending = false;
-    bool norms_done = false;   // the tile norms ran with the pack (SBO_FUSED_TN)
-    // a launched guard reads L, L^-1, x/y/obs and ctx->chk on chk_stream: an
-    // early return (a failed launch, NOT_SPD) waits for it before the caller
-    // can regrow or free those buffers or the next fit writes L
-    struct ChkDrain {
-        sbo_ctx *c;
-        bool pending = false;
-        ~ChkDrain() {
-            if (pending && c->chk_stream) (void)hipStreamSynchronize(c->chk_stream);
-        }
-    } drain{ctx};
-    // the inverse's first half ran beside the Cholesky (blocked_potrf): its
-    // info slots 1 .. inv_slot stay, the rest are cleared
-    const bool early = ctx->inverse_bits == 64 && ctx->inverse_rec && !incr && ctx->early_inv_n == n;
-    ctx->early_inv_n = 0;
-    if (early) {
+    SBO_HIP(grow_keep(ctx, ctx->aug, sizeof(float) * (size_t)sbo::total_tiles(p.nI) * sbo::kTileFloats,
+                      sizeof(float) * p.old_tiles * sbo::kTileFloats));
+    SBO_HIP(ctx->kcoord.reserve(sizeof(float) * (size_t)(p.npad / sbo::kBK) * 3 * sbo::kBK));
+    if (p.half_done) {
         SBO_HIP(hipMemsetAsync(info, 0, sizeof(rocblas_int), ctx->stream));
-        SBO_HIP(hipMemsetAsync(info + 1 + ctx->inv_slot, 0, sizeof(rocblas_int) * (size_t)(nslots - 1 - ctx->inv_slot),
+        SBO_HIP(hipMemsetAsync(info + 1 + p.half_slots, 0, sizeof(rocblas_int) * (size_t)(nslots - 1 - p.half_slots),
                                ctx->stream));
     } else {
         SBO_HIP(hipMemsetAsync(info, 0, sizeof(rocblas_int) * (size_t)nslots, ctx->stream));
     }
-    if (ctx->inverse_bits == 64) {
-        double *Li = ctx->Linv.as<double>();
-        if (incr) {
-            const int64_t b = n - n_old;
-            const double one = 1.0, minus_one = -1.0;
-            double *T = Li + n_old;                      // rows n_old.., columns 0..n_old-1
-            double *L22i = Li + n_old + n_old * ld;      // rows n_old.., columns n_old..
-            SBO_HIP(sbo::launch_widen(ctx->stream, L + n_old, ld, b, n_old, false, T, ld));
-            SBO_HIP(sbo::launch_widen(ctx->stream, L + n_old + n_old * ld, ld, b, b, true, L22i, ld));
-            SBO_BLAS(rocsolver_dtrtri(ctx->blas, rocblas_fill_lower, rocblas_diagonal_non_unit, (rocblas_int)b, L22i,
-                                      (rocblas_int)ld, info));
-            SBO_BLAS(rocblas_set_pointer_mode(ctx->blas, rocblas_pointer_mode_host));
-            // S = L21 L11^-1, then T = -L22^-1 S, as two dgemms on the
-            // triangles with their zero halves (one f64 MFMA GEMM each:
-            // rocBLAS's in-place dtrmm ran as ~200 small launches per append).
-            // The strictly upper part of L^-1 is zero: widen() writes it for
-            // the initial inverse and for L22^-1, rocSOLVER dtrtri leaves it,
-            // and the columns an append adds are zeroed above the new rows here.
-            SBO_HIP(hipMemset2DAsync(Li + n_old * ld, sizeof(double) * (size_t)ld, 0, sizeof(double) * (size_t)n_old,
-                                     (size_t)b, ctx->stream));
-            // (sized by the capacity, so that the appends of a streaming loop do not regrow it)
-            SBO_HIP(ctx->scratch.reserve(sizeof(double) * (size_t)sbo::round_up(b, 256) * (size_t)ld));
-            double *S = ctx->scratch.as<double>();
-            const double zero = 0.0;
-            if (b <= kAppendInvRows) {
-                // row by row: S[r,:]^T = Li^T T[r,:]^T, one dtrmv over the
-                // lower triangle (the dgemm read the whole n_old^2 square)
-                for (int64_t r = 0; r < b; ++r) {
-                    SBO_BLAS(rocblas_dcopy(ctx->blas, (rocblas_int)n_old, T + r, (rocblas_int)ld, S + r, (rocblas_int)b));
-                    SBO_BLAS(rocblas_dtrmv(ctx->blas, rocblas_fill_lower, rocblas_operation_transpose,
-                                           rocblas_diagonal_non_unit, (rocblas_int)n_old, Li, (rocblas_int)ld, S + r,
-                                           (rocblas_int)b));
-                }
-            } else {
-                SBO_BLAS(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_none, (rocblas_int)b,
-                                       (rocblas_int)n_old, (rocblas_int)n_old, &one, T, (rocblas_int)ld, Li,
-                                       (rocblas_int)ld, &zero, S, (rocblas_int)b));
-            }
-            SBO_BLAS(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_none, (rocblas_int)b,
-                                   (rocblas_int)n_old, (rocblas_int)b, &minus_one, L22i, (rocblas_int)ld, S,
-                                   (rocblas_int)b, &zero, T, (rocblas_int)ld));
-        } else {
-            SBO_HIP(ctx->Linv.reserve(sizeof(double) * (size_t)ld * (size_t)ld));
-            Li = ctx->Linv.as<double>();
-            if (early) {
-                // A^-1 and S = B A^-1 are done: widen the right columns (their
-                // rows 0..h-1 zero), then C^-1 and X21 = -C^-1 S
-                const int64_t h = inverse_split(n, ctx->inv_base);
-                SBO_HIP(sbo::launch_widen(ctx->stream, L + h + h * ld, ld, n - h, n - h, true, Li + h + h * ld, ld));
-                SBO_HIP(hipMemset2DAsync(Li + h * ld, sizeof(double) * (size_t)ld, 0, sizeof(double) * (size_t)h,
-                                         (size_t)(n - h), ctx->stream));
-                int slot = ctx->inv_slot;
-                if (sbo_status st = inverse_second_half(ctx, ctx->blas, Li, n, ld, ctx->scratch.as<double>(),
-                                                        ctx->scratch.as<double>() + h * (n - h), slot);
-                    st != SBO_OK)
-                    return st;
-            } else if (ctx->inverse_rec) {
-                if (ctx->widened_n != n) SBO_HIP(sbo::launch_widen(ctx->stream, L, ld, n, n, true, Li, ld));
-                ctx->widened_n = 0;
-                SBO_HIP(ctx->scratch.reserve(
-                    sizeof(double) *
-                    (size_t)std::max({inverse_scratch_par(n, ctx->inv_base), leaf_scratch(ctx, n), (int64_t)1})));
-                if (ctx->inv_batched) {
-                    if (sbo_status st = inverse_leaves(ctx, ctx->blas, Li, n, ld, ctx->scratch.as<double>());
-                        st != SBO_OK)
-                        return st;
-                }
-                ctx->inv_leaves_done = ctx->inv_batched;
-                const sbo_status st = inverse_lower_f64_par(ctx, Li, n, ld, ctx->scratch.as<double>());
-                ctx->inv_leaves_done = false;
-                if (st != SBO_OK) return st;
-            } else {
-                SBO_HIP(sbo::launch_widen(ctx->stream, L, ld, n, n, true, Li, ld));
-                SBO_BLAS(rocsolver_dtrtri(ctx->blas, rocblas_fill_lower, rocblas_diagonal_non_unit, (rocblas_int)n,
-                                          Li, (rocblas_int)ld, info));
-            }
-        }
-        ctx->linv_n = n;
-        // the inverse's accuracy guard, on its own stream beside what follows
-        if (!incr && (ctx->inv_check == 2 || ctx->inv_oz_off ||
-                      (ctx->inv_check == 1 && ctx->inverse_rec && !early && inverse_sliced(ctx, n)))) {
-            ctx->chk_res = sbo_inv_check{};
-            ctx->chk_res.digits = (ctx->inverse_rec && !early && inverse_sliced(ctx, n)) ? inv_digits(ctx) : 0;
-            drain.pending = true;   // (set before the launch: a half-queued guard is drained too)
-            if (sbo_status st = inverse_check_launch(ctx)) return st;
-            chk_pending = true;
-        } else if (!incr) {
-            ctx->chk_res = sbo_inv_check{};
-        }
-        // alpha = K^-1 (y - m0) = L^-T L^-1 (y - m0), in f64 from the f64
-        // inverse: two triangular matrix-vector products (bandwidth-bound and
-        // parallel, unlike the two sequential triangular solves of spotrs),
-        // into alpha64 (the precise sweep's mean uses alpha in f64).  They
-        // only feed the coordinate pack: on aux_stream (blas_aux) beside the
-        // operand pack, row sums and tile norms, which read only L^-1 (C4:
-        // 0.75 ms off the fit's critical path).
-        // An append of a few points updates alpha instead (z = L^-1 r kept from
-        // the last refresh): z's new entries are the inverse's new rows times
-        // r, and alpha += (new rows)^T z_new over all n -- two dgemv over b
-        // rows instead of two passes over the whole triangle (0.8 ms at C4).
-        const bool inc_alpha = incr && ctx->z_n == n_old && n - n_old <= kAppendInvGemm;
-        SBO_HIP(grow_keep(ctx, ctx->alpha64, sizeof(double) * (size_t)std::max(npad, ld),
-                          inc_alpha ? sizeof(double) * (size_t)n_old : 0));
-        SBO_HIP(grow_keep(ctx, ctx->zvec, sizeof(double) * (size_t)std::max(npad, ld),
-                          inc_alpha ? sizeof(double) * (size_t)n_old : 0));
-        ctx->z_n = 0;
-        double *d = ctx->alpha64.as<double>(), *zv = ctx->zvec.as<double>();
-        alpha_aux = ctx->blas_aux && ctx->aux_stream && ctx->ev_panel && ctx->ev_pack;
-        hipStream_t sa = alpha_aux ? ctx->aux_stream : ctx->stream;
-        rocblas_handle ha = alpha_aux ? ctx->blas_aux : ctx->blas;
-        if (alpha_aux) {
-            SBO_HIP(hipEventRecord(ctx->ev_panel, ctx->stream));
-            SBO_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_panel, 0));
-        }
-        if (inc_alpha) {
-            const int64_t b = n - n_old;
-            const double one = 1.0;
-            SBO_HIP(ctx->rvec.reserve(sizeof(double) * (size_t)n));
-            double *rv = ctx->rvec.as<double>();
-            SBO_HIP(sbo::launch_widen_sub(sa, ctx->obs.as<float>(), ctx->hyper.prior_mean, n, rv));
-            SBO_BLAS(rocblas_set_pointer_mode(ha, rocblas_pointer_mode_host));
-            SBO_HIP(sbo::launch_row_dot(sa, Li + n_old, ld, b, n, rv, zv + n_old));
-            SBO_HIP(hipMemsetAsync(d + n_old, 0, sizeof(double) * (size_t)b, sa));
-            SBO_BLAS(rocblas_dgemv(ha, rocblas_operation_transpose, (rocblas_int)b, (rocblas_int)n, &one, Li + n_old,
-                                   (rocblas_int)ld, zv + n_old, 1, &one, d, 1));
-        } else {
-            // z = L^-1 r and alpha = L^-T z by the own two-pass kernels (one
-            // read of the triangle each; rocBLAS dtrmv took 1.4 ms at C4)
-            SBO_HIP(ctx->awork.reserve(sbo::alpha_work_bytes(n)));
-            SBO_HIP(sbo::launch_alpha_f64(sa, Li, ld, n, ctx->obs.as<float>(), ctx->hyper.prior_mean, zv, d,
-                                          ctx->awork.as<double>()));
-        }
-        ctx->z_n = n;
-        SBO_HIP(sbo::launch_narrow(sa, d, n, alpha));
-        if (alpha_aux) SBO_HIP(hipEventRecord(ctx->ev_trail, ctx->aux_stream));
-        ctx->a64_I0 = std::min(ctx->a64_I0, I0);
-        if (!incr) ctx->a64_I0 = 0;
-        // the sweeps' operands, derived from the packed f32 tiles (the split
-        // bf16 planes) and from L^-1 (the f64 operand, when the precision probe
-        // or the precise sweep will read it), on aux_stream beside the row sums
-        // and tile norms below, instead of lazily at the first tick (HBM-bound
-        // beside MFMA-bound; C4: 0.22 + 0.41 ms off the fit's critical path)
-        const int layout = sbo::x3_layout(ctx->kernel_variant);
-        const bool eager_x3 = alpha_aux && ctx->kernel_variant >= 2;
-        const bool eager_f64 =
-            alpha_aux && ctx->precision_opt != 0 && (probe_due(ctx) || ctx->precise || ctx->precision_opt == 1);
-        if (eager_x3) {
-            if (layout != ctx->x3_layout) ctx->x3_I0 = 0;
-            const int64_t xI0 = std::max<int64_t>(std::min(ctx->x3_I0, I0), 0);
-            SBO_HIP(grow_keep(ctx, ctx->ax3, sbo::x3_operand_bytes(npad), sbo::x3_operand_bytes(xI0 * sbo::kBM)));
-            SBO_HIP(ctx->kc3.reserve(sbo::x3_coord_bytes(npad)));
-            ctx->x3_I0 = xI0;
-        }
+    return SBO_OK;
+}
 
-        if (eager_f64)   // (before the fork: a growing operand copies and waits on `stream`)
-            if (sbo_status st = reserve_precise(ctx, npad, std::max<int64_t>(ctx->a64_I0, 0))) return st;
-#if SBO_FUSED_TN
-        // the pack and the tile norms in one pass over L^-1 (tile_norm_kernel<true>)
-        SBO_HIP(grow_keep(ctx, ctx->tile_lgn, 2 * sizeof(float4) * (size_t)sbo::total_tiles(nI),
-                          2 * sizeof(float4) * old_tiles));
-        SBO_HIP(sbo::launch_pack_tile_norms(ctx->stream, Li, ld, n, npad, I0, sf2, ctx->aug.as<float>(),
-                                            ctx->tile_lgn.as<float4>()));
-        norms_done = true;
-#else
-        SBO_HIP(sbo::launch_pack_tiles(ctx->stream, Li, ld, n, npad, I0, sf2, ctx->aug.as<float>()));
-#endif
-        if (eager_x3 || eager_f64) {
-            SBO_HIP(hipEventRecord(ctx->ev_panel, ctx->stream));
-            SBO_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_panel, 0));
-            if (eager_x3) {
-                SBO_HIP(sbo::launch_pack_x3(ctx->aux_stream, ctx->aug.as<float>(), nullptr, npad, ctx->x3_I0, layout,
-                                            ctx->ax3.as<char>(), nullptr));
-                x3_planes_aux = true;
-            }
-            // the row sums too (the skip budget's, read by the host after the
-            // tile norms): the tile norms start right after the pack
-            SBO_HIP(ctx->scratch.reserve(sizeof(double) * (size_t)npad));
-            SBO_HIP(sbo::launch_row_l1(ctx->aux_stream, ctx->aug.as<float>(), npad, I0, ctx->scratch.as<double>()));
-            SBO_HIP(hipEventRecord(ctx->ev_pack, ctx->aux_stream));   // what the host reads below
-            // the precise operand after it, left running past this fit's host
-            // sync: only the probe's precise sweep reads it, on the device,
-            // after ev_poz (round 6: 1.7 ms at C4 off the fit's critical path)
-            if (eager_f64) {
-                if (sbo_status st = pack_precise(ctx, ctx->aux_stream, npad, std::max<int64_t>(ctx->a64_I0, 0)))
-                    return st;
-                ctx->a64_I0 = INT64_MAX;
-                SBO_HIP(hipEventRecord(ctx->ev_poz, ctx->aux_stream));
-                ctx->poz_pending = true;
-            }
-            packs_aux = true;
+// An append of rows n_old..n-1 to an unchanged leading factor: with the f64
+// inverse of the leading block kept from the last refresh, only the new rows
+// of L^-1 are computed,
+//     [L11  0 ]^-1   [ L11^-1                  0     ]
+//     [L21 L22]    = [ -L22^-1 L21 L11^-1   L22^-1 ]
+// (one b x b dtrtri and two dtrmm, O(b n^2) instead of O(n^3)).
+sbo_status inverse_incremental(sbo_ctx *ctx, const RefreshPlan &p) {
+    const int64_t n = p.n, ld = p.ld, n_old = p.n_old, b = n - n_old;
+    float *L = ctx->L.as<float>();
+    double *Li = ctx->Linv.as<double>();
+    const double one = 1.0, minus_one = -1.0;
+    double *T = Li + n_old;                      // rows n_old.., columns 0..n_old-1
+    double *L22i = Li + n_old + n_old * ld;      // rows n_old.., columns n_old..
+    SBO_HIP(sbo::launch_widen(ctx->stream, L + n_old, ld, b, n_old, false, T, ld));
+    SBO_HIP(sbo::launch_widen(ctx->stream, L + n_old + n_old * ld, ld, b, b, true, L22i, ld));
+    SBO_BLAS(rocsolver_dtrtri(ctx->blas, rocblas_fill_lower, rocblas_diagonal_non_unit, (rocblas_int)b, L22i,
+                              (rocblas_int)ld, ctx->info.as<rocblas_int>()));
+    SBO_BLAS(rocblas_set_pointer_mode(ctx->blas, rocblas_pointer_mode_host));
+    // S = L21 L11^-1, then T = -L22^-1 S, as two dgemms on the
+    // triangles with their zero halves (one f64 MFMA GEMM each:
+    // rocBLAS's in-place dtrmm ran as ~200 small launches per append).
+    // The strictly upper part of L^-1 is zero: widen() writes it for
+    // the initial inverse and for L22^-1, rocSOLVER dtrtri leaves it,
+    // and the columns an append adds are zeroed above the new rows here.
+    SBO_HIP(hipMemset2DAsync(Li + n_old * ld, sizeof(double) * (size_t)ld, 0, sizeof(double) * (size_t)n_old,
+                             (size_t)b, ctx->stream));
+    // (sized by the capacity, so that the appends of a streaming loop do not regrow it)
+    SBO_HIP(ctx->scratch.reserve(sizeof(double) * (size_t)sbo::round_up(b, 256) * (size_t)ld));
+    double *S = ctx->scratch.as<double>();
+    const double zero = 0.0;
+    if (b <= kAppendInvRows) {
+        // row by row: S[r,:]^T = Li^T T[r,:]^T, one dtrmv over the
+        // lower triangle (the dgemm read the whole n_old^2 square)
+        for (int64_t r = 0; r < b; ++r) {
+            SBO_BLAS(rocblas_dcopy(ctx->blas, (rocblas_int)n_old, T + r, (rocblas_int)ld, S + r, (rocblas_int)b));
+            SBO_BLAS(rocblas_dtrmv(ctx->blas, rocblas_fill_lower, rocblas_operation_transpose,
+                                   rocblas_diagonal_non_unit, (rocblas_int)n_old, Li, (rocblas_int)ld, S + r,
+                                   (rocblas_int)b));
         }
-        kcoord_pending = true;
     } else {
-        ctx->linv_n = 0;
-        // alpha = K^-1 (y - m0) by the f32 triangular solves
-        SBO_HIP(sbo::launch_sub_scalar(ctx->stream, ctx->obs.as<float>(), (float)ctx->hyper.prior_mean, n, alpha));
-        SBO_BLAS(rocsolver_spotrs(ctx->blas, rocblas_fill_lower, (rocblas_int)n, 1, L, (rocblas_int)ld, alpha,
-                                  (rocblas_int)n));
-        SBO_HIP(ctx->Linv.reserve(sizeof(float) * (size_t)ld * (size_t)n));
-        float *Li = ctx->Linv.as<float>();
-        SBO_HIP(hipMemcpyAsync(Li, L, sizeof(float) * (size_t)ld * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
-        SBO_BLAS(rocsolver_strtri(ctx->blas, rocblas_fill_lower, rocblas_diagonal_non_unit, (rocblas_int)n, Li,
-                                  (rocblas_int)ld, info));
-        SBO_HIP(sbo::launch_pack_operand(ctx->stream, Li, ld, n, npad, 0, sf2, ctx->x.as<float>(), ctx->y.as<float>(),
-                                         alpha, ctx->aug.as<float>(), ctx->kcoord.as<float>()));
+        SBO_BLAS(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_none, (rocblas_int)b,
+                               (rocblas_int)n_old, (rocblas_int)n_old, &one, T, (rocblas_int)ld, Li,
+                               (rocblas_int)ld, &zero, S, (rocblas_int)b));
     }
-    // Error budget of the automatic K* tile cutoff (SBO_OPT_TILE_SKIP = -1),
-    // B = SBO_OPT_SKIP_BUDGET: sigma^2 = sf2 - |V|^2 moves by at most
-    // 2 |V|_2 |dV|_2 + |dV|_2^2 with |V|_2 <= sf2^(1/2), so |dV(q)|_2 <=
-    // tau2 = 2^-B sf2^(1/2) / 2 (less 1 %) keeps it below 2^-B sf2.
-    //  - tile-norm test (one row block per workgroup): row block I may lose
-    //    |dV_I|_2 <= tau2 / sqrt(nI); a dropped tile t costs at most
-    //    nu_It K*max(t), nu_It = min(16 max row sum, 8 |A_It|_F) (the tile's
-    //    2-norm gain bound), and the kernel drops the smallest first.
-    //  - distance cutoff (row-block chunks, and the reported L): every K*
-    //    entry of a dropped tile is below 2^-L, so each V_i moves by at most
-    //    2^-L max_i |A_i|_1 and |dV|_2 by sqrt(N) times that; L keeps it
-    //    below tau2.
-    // The mean (last row block) drops only tiles below 2^-L_mean, with
-    // 2^-L_mean |sf2 alpha|_1 <= 2^-B sf2^(1/2).  Rows of earlier row blocks
-    // are unchanged by an append: only the repacked row blocks are measured.
-    {
-        if (!packs_aux) {
-            SBO_HIP(ctx->scratch.reserve(sizeof(double) * (size_t)npad));
-            SBO_HIP(sbo::launch_row_l1(ctx->stream, ctx->aug.as<float>(), npad, I0, ctx->scratch.as<double>()));
-        }
-        if (!norms_done) {
-            SBO_HIP(grow_keep(ctx, ctx->tile_lgn, 2 * sizeof(float4) * (size_t)sbo::total_tiles(nI),
-                              2 * sizeof(float4) * old_tiles));
-            SBO_HIP(sbo::launch_tile_norms(ctx->stream, ctx->aug.as<float>(), npad, I0, ctx->tile_lgn.as<float4>()));
-        }
-        if (kcoord_pending) {
-            if (alpha_aux) SBO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_trail, 0));
-            SBO_HIP(sbo::launch_pack_kcoord(ctx->stream, ctx->x.as<float>(), ctx->y.as<float>(), alpha, n, npad, sf2,
-                                            ctx->kcoord.as<float>()));
-            if (x3_planes_aux)  // the split sweep's coordinates (its planes are on aux_stream)
-                SBO_HIP(sbo::launch_pack_x3(ctx->stream, nullptr, ctx->kcoord.as<float>(), npad, 0, 0, nullptr,
-                                            ctx->kc3.as<float>()));
-        }
-        if (packs_aux) SBO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_pack, 0));  // row sums and packs
-        const int64_t r0 = I0 * sbo::kBM;
-        std::vector<double> rl1((size_t)(npad - r0));
-        std::vector<float> ha((size_t)n);
-        SBO_HIP(hipMemcpyAsync(rl1.data(), ctx->scratch.as<double>() + r0, sizeof(double) * (npad - r0),
-                               hipMemcpyDeviceToHost, ctx->stream));
-        SBO_HIP(hipMemcpyAsync(ha.data(), alpha, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
-        SBO_HIP(hipStreamSynchronize(ctx->stream));
-        double mx = *std::max_element(rl1.begin(), rl1.end());
-        if (incr) mx = std::max(mx, ctx->max_row_l1);
-        ctx->max_row_l1 = mx;
-        double al1 = 0.0;
-        for (float v : ha) al1 += std::fabs((double)v);
-        ctx->alpha_l1 = al1 * sf2;
-        const double tol = std::ldexp(1.0, -ctx->skip_budget), sf = std::sqrt(sf2);
-        const double tau2 = tol * sf / 2.0 * 0.99;  // 1 % for the dV^2 term
-        auto cut = [](double need) {
-            const double l2 = std::log2(std::max(need, 1.0));
-            return std::isfinite(l2) ? std::min(160, std::max(16, (int)std::ceil(l2))) : 160;
-        };
-        ctx->auto_skip_log2 = cut(ctx->max_row_l1 * std::sqrt((double)n) / tau2);
-        ctx->auto_skip_mean_log2 = cut(ctx->alpha_l1 / (tol * sf));
-        ctx->lg_tau_v = (float)std::log2(tau2 / std::sqrt((double)nI));
+    SBO_BLAS(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_none, (rocblas_int)b,
+                           (rocblas_int)n_old, (rocblas_int)b, &minus_one, L22i, (rocblas_int)ld, S,
+                           (rocblas_int)b, &zero, T, (rocblas_int)ld));
+    return SBO_OK;
+}
+
+// The inverse whose first half ran beside the Cholesky (blocked_potrf):
+// A^-1 and S = B A^-1 are done: widen the right columns (their rows 0..h-1
+// zero), then C^-1 and X21 = -C^-1 S
+sbo_status inverse_finish_half(sbo_ctx *ctx, const RefreshPlan &p) {
+    const int64_t n = p.n, ld = p.ld, h = inverse_split(n, ctx->inv_base);
+    float *L = ctx->L.as<float>();
+    double *Li = ctx->Linv.as<double>();
+    SBO_HIP(sbo::launch_widen(ctx->stream, L + h + h * ld, ld, n - h, n - h, true, Li + h + h * ld, ld));
+    SBO_HIP(hipMemset2DAsync(Li + h * ld, sizeof(double) * (size_t)ld, 0, sizeof(double) * (size_t)h,
+                             (size_t)(n - h), ctx->stream));
+    int slot = p.half_slots;
+    return inverse_second_half(ctx, ctx->blas, Li, n, ld, ctx->scratch.as<double>(),
+                               ctx->scratch.as<double>() + h * (n - h), slot, InvMode{});
+}
+
+// The library's own recursion (SBO_OPT_INVERSE 1): the factor widened unless
+// blocked_potrf did it, the base cases up front (SBO_OPT_INV_LEAVES), then
+// the two halves side by side.
+sbo_status inverse_recursive(sbo_ctx *ctx, const RefreshPlan &p) {
+    const int64_t n = p.n, ld = p.ld;
+    double *Li = ctx->Linv.as<double>();
+    if (!p.widened) SBO_HIP(sbo::launch_widen(ctx->stream, ctx->L.as<float>(), ld, n, n, true, Li, ld));
+    SBO_HIP(ctx->scratch.reserve(
+        sizeof(double) * (size_t)std::max({inverse_scratch_par(n, ctx->inv_base), leaf_scratch(ctx, n), (int64_t)1})));
+    if (ctx->inv_batched)
+        if (sbo_status st = inverse_leaves(ctx, ctx->blas, Li, n, ld, ctx->scratch.as<double>()); st != SBO_OK)
+            return st;
+    return inverse_lower_f64_par(ctx, Li, n, ld, ctx->scratch.as<double>(), InvMode{p.digits, ctx->inv_batched});
+}
+
+// rocSOLVER's dtrtri on the widened factor (SBO_OPT_INVERSE 0)
+sbo_status inverse_rocsolver(sbo_ctx *ctx, const RefreshPlan &p) {
+    double *Li = ctx->Linv.as<double>();
+    SBO_HIP(sbo::launch_widen(ctx->stream, ctx->L.as<float>(), p.ld, p.n, p.n, true, Li, p.ld));
+    SBO_BLAS(rocsolver_dtrtri(ctx->blas, rocblas_fill_lower, rocblas_diagonal_non_unit, (rocblas_int)p.n, Li,
+                              (rocblas_int)p.ld, ctx->info.as<rocblas_int>()));
+    return SBO_OK;
+}
+
+// L^-1 (lower, non-unit) in f64: widen L and invert (f64 MFMA), then round
+// sf2 * L^-1 to f32 once while packing -- the f32 strtri path adds its own
+// inversion error on top of the f32 representation error
+// (SBO_OPT_INVERSE_BITS = 32 selects it, refresh_f32).
+sbo_status refresh_inverse(sbo_ctx *ctx, const RefreshPlan &p) {
+    sbo_status st;
+    if (p.incr) {
+        st = inverse_incremental(ctx, p);
+    } else {
+        SBO_HIP(ctx->Linv.reserve(sizeof(double) * (size_t)p.ld * (size_t)p.ld));
+        st = p.half_done ? inverse_finish_half(ctx, p)
+             : ctx->inverse_rec ? inverse_recursive(ctx, p)
+                                : inverse_rocsolver(ctx, p);
     }
-    SBO_HIP(ctx->kbox.reserve(sizeof(float4) * (size_t)(npad / sbo::kBK)));
-    SBO_HIP(sbo::launch_tile_boxes(ctx->stream, ctx->x.as<float>(), ctx->y.as<float>(), n, npad, ctx->kbox.as<float4>()));
-    std::vector<rocblas_int> hinfos((size_t)nslots);
-    SBO_HIP(hipMemcpyAsync(hinfos.data(), info, sizeof(rocblas_int) * (size_t)nslots, hipMemcpyDeviceToHost,
-                           ctx->stream));
+    if (st != SBO_OK) return st;
+    ctx->linv_n = p.n;
+    return SBO_OK;
+}
+
+// the inverse's accuracy guard, on its own stream beside what follows
+sbo_status refresh_guard_launch(sbo_ctx *ctx, const RefreshPlan &p) {
+    if (p.incr) return SBO_OK;
+    ctx->chk_res = sbo_inv_check{};
+    if (!p.guard) return SBO_OK;
+    ctx->chk_res.digits = p.digits;
+    return inverse_check_launch(ctx);
+}
+
+// alpha = K^-1 (y - m0) = L^-T L^-1 (y - m0), in f64 from the f64
+// inverse: two triangular matrix-vector products (bandwidth-bound and
+// parallel, unlike the two sequential triangular solves of spotrs),
+// into alpha64 (the precise sweep's mean uses alpha in f64).  They
+// only feed the coordinate pack: on aux_stream (blas_aux) beside the
+// operand pack, row sums and tile norms, which read only L^-1 (C4:
+// 0.75 ms off the fit's critical path).
+// An append of a few points updates alpha instead (z = L^-1 r kept from
+// the last refresh): z's new entries are the inverse's new rows times
+// r, and alpha += (new rows)^T z_new over all n -- two dgemv over b
+// rows instead of two passes over the whole triangle (0.8 ms at C4).
+sbo_status refresh_alpha(sbo_ctx *ctx, const RefreshPlan &p) {
+    const int64_t n = p.n, ld = p.ld, n_old = p.n_old;
+    double *Li = ctx->Linv.as<double>();
+    SBO_HIP(grow_keep(ctx, ctx->alpha64, sizeof(double) * (size_t)std::max(p.npad, ld),
+                      p.inc_alpha ? sizeof(double) * (size_t)n_old : 0));
+    SBO_HIP(grow_keep(ctx, ctx->zvec, sizeof(double) * (size_t)std::max(p.npad, ld),
+                      p.inc_alpha ? sizeof(double) * (size_t)n_old : 0));
+    ctx->z_n = 0;
+    double *d = ctx->alpha64.as<double>(), *zv = ctx->zvec.as<double>();
+    hipStream_t sa = p.aux ? ctx->aux_stream : ctx->stream;
+    rocblas_handle ha = p.aux ? ctx->blas_aux : ctx->blas;
+    if (p.aux) {
+        SBO_HIP(hipEventRecord(ctx->ev_panel, ctx->stream));
+        SBO_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_panel, 0));
+    }
+    if (p.inc_alpha) {
+        const int64_t b = n - n_old;
+        const double one = 1.0;
+        SBO_HIP(ctx->rvec.reserve(sizeof(double) * (size_t)n));
+        double *rv = ctx->rvec.as<double>();
+        SBO_HIP(sbo::launch_widen_sub(sa, ctx->obs.as<float>(), ctx->hyper.prior_mean, n, rv));
+        SBO_BLAS(rocblas_set_pointer_mode(ha, rocblas_pointer_mode_host));
+        SBO_HIP(sbo::launch_row_dot(sa, Li + n_old, ld, b, n, rv, zv + n_old));
+        SBO_HIP(hipMemsetAsync(d + n_old, 0, sizeof(double) * (size_t)b, sa));
+        SBO_BLAS(rocblas_dgemv(ha, rocblas_operation_transpose, (rocblas_int)b, (rocblas_int)n, &one, Li + n_old,
+                               (rocblas_int)ld, zv + n_old, 1, &one, d, 1));
+    } else {
+        // z = L^-1 r and alpha = L^-T z by the own two-pass kernels (one
+        // read of the triangle each; rocBLAS dtrmv took 1.4 ms at C4)
+        SBO_HIP(ctx->awork.reserve(sbo::alpha_work_bytes(n)));
+        SBO_HIP(sbo::launch_alpha_f64(sa, Li, ld, n, ctx->obs.as<float>(), ctx->hyper.prior_mean, zv, d,
+                                      ctx->awork.as<double>()));
+    }
+    ctx->z_n = n;
+    SBO_HIP(sbo::launch_narrow(sa, d, n, ctx->alpha.as<float>()));
+    if (p.aux) SBO_HIP(hipEventRecord(ctx->ev_trail, ctx->aux_stream));
+    return SBO_OK;
+}
+
+// The packed f32 tiles from L^-1 on `stream`, and the fork: the sweeps'
+// operands, derived from the packed f32 tiles (the split bf16 planes) and
+// from L^-1 (the f64 operand, when the precision probe or the precise sweep
+// will read it), on aux_stream beside the row sums and tile norms, instead
+// of lazily at the first tick (HBM-bound beside MFMA-bound; C4: 0.22 + 0.41
+// ms off the fit's critical path).  refresh_join waits for them.
+sbo_status refresh_packs(sbo_ctx *ctx, const RefreshPlan &p) {
+    const int64_t n = p.n, ld = p.ld, npad = p.npad, I0 = p.I0;
+    double *Li = ctx->Linv.as<double>();
+    ctx->a64_I0 = std::min(ctx->a64_I0, I0);
+    if (!p.incr) ctx->a64_I0 = 0;
+    if (p.eager_x3) {
+        if (p.x3_layout != ctx->x3_layout) ctx->x3_I0 = 0;
+        const int64_t xI0 = std::max<int64_t>(std::min(ctx->x3_I0, I0), 0);
+        SBO_HIP(grow_keep(ctx, ctx->ax3, sbo::x3_operand_bytes(npad), sbo::x3_operand_bytes(xI0 * sbo::kBM)));
+        SBO_HIP(ctx->kc3.reserve(sbo::x3_coord_bytes(npad)));
+        ctx->x3_I0 = xI0;
+    }
+    if (p.eager_f64)   // (before the fork: a growing operand copies and waits on `stream`)
+        if (sbo_status st = reserve_precise(ctx, npad, std::max<int64_t>(ctx->a64_I0, 0))) return st;
+#if SBO_FUSED_TN
+    // the pack and the tile norms in one pass over L^-1 (tile_norm_kernel<true>)
+    SBO_HIP(grow_keep(ctx, ctx->tile_lgn, 2 * sizeof(float4) * (size_t)sbo::total_tiles(p.nI),
+                      2 * sizeof(float4) * p.old_tiles));
+    SBO_HIP(sbo::launch_pack_tile_norms(ctx->stream, Li, ld, n, npad, I0, p.sf2, ctx->aug.as<float>(),
+                                        ctx->tile_lgn.as<float4>()));
+#else
+    SBO_HIP(sbo::launch_pack_tiles(ctx->stream, Li, ld, n, npad, I0, p.sf2, ctx->aug.as<float>()));
+#endif
+    if (!p.eager_x3 && !p.eager_f64) return SBO_OK;
+    SBO_HIP(hipEventRecord(ctx->ev_panel, ctx->stream));
+    SBO_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_panel, 0));
+    if (p.eager_x3)
+        SBO_HIP(sbo::launch_pack_x3(ctx->aux_stream, ctx->aug.as<float>(), nullptr, npad, ctx->x3_I0, p.x3_layout,
+                                    ctx->ax3.as<char>(), nullptr));
+    // the row sums too (the skip budget's, read by the host after the
+    // tile norms): the tile norms start right after the pack
+    SBO_HIP(ctx->scratch.reserve(sizeof(double) * (size_t)npad));
+    SBO_HIP(sbo::launch_row_l1(ctx->aux_stream, ctx->aug.as<float>(), npad, I0, ctx->scratch.as<double>()));
+    SBO_HIP(hipEventRecord(ctx->ev_pack, ctx->aux_stream));   // what the host reads in refresh_skip_budget
+    // the precise operand after it, left running past this fit's host
+    // sync: only the probe's precise sweep reads it, on the device,
+    // after ev_poz (round 6: 1.7 ms at C4 off the fit's critical path)
+    if (p.eager_f64) {
+        if (sbo_status st = pack_precise(ctx, ctx->aux_stream, npad, std::max<int64_t>(ctx->a64_I0, 0))) return st;
+        ctx->a64_I0 = INT64_MAX;
+        SBO_HIP(hipEventRecord(ctx->ev_poz, ctx->aux_stream));
+        ctx->poz_pending = true;
+    }
+    return SBO_OK;
+}
+
+// SBO_OPT_INVERSE_BITS 32: alpha = K^-1 (y - m0) by the f32 triangular
+// solves, L^-1 by rocSOLVER strtri, packed with the coordinates in one launch
+sbo_status refresh_f32(sbo_ctx *ctx, const RefreshPlan &p) {
+    const int64_t n = p.n, ld = p.ld;
+    float *L = ctx->L.as<float>(), *alpha = ctx->alpha.as<float>();
+    ctx->linv_n = 0;
+    SBO_HIP(sbo::launch_sub_scalar(ctx->stream, ctx->obs.as<float>(), (float)ctx->hyper.prior_mean, n, alpha));
+    SBO_BLAS(rocsolver_spotrs(ctx->blas, rocblas_fill_lower, (rocblas_int)n, 1, L, (rocblas_int)ld, alpha,
+                              (rocblas_int)n));
+    SBO_HIP(ctx->Linv.reserve(sizeof(float) * (size_t)ld * (size_t)n));
+    float *Li = ctx->Linv.as<float>();
+    SBO_HIP(hipMemcpyAsync(Li, L, sizeof(float) * (size_t)ld * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
+    SBO_BLAS(rocsolver_strtri(ctx->blas, rocblas_fill_lower, rocblas_diagonal_non_unit, (rocblas_int)n, Li,
+                              (rocblas_int)ld, ctx->info.as<rocblas_int>()));
+    SBO_HIP(sbo::launch_pack_operand(ctx->stream, Li, ld, n, p.npad, 0, p.sf2, ctx->x.as<float>(), ctx->y.as<float>(),
+                                     alpha, ctx->aug.as<float>(), ctx->kcoord.as<float>()));
+    return SBO_OK;
+}
+
+// What is left of the packs on `stream` -- the row sums and tile norms that
+// did not run with the fork, the coordinate pack once alpha is there -- and
+// the join with aux_stream.
+sbo_status refresh_join(sbo_ctx *ctx, const RefreshPlan &p) {
+    const int64_t npad = p.npad;
+    const bool packs_aux = p.eager_x3 || p.eager_f64;
+    if (!packs_aux) {
+        SBO_HIP(ctx->scratch.reserve(sizeof(double) * (size_t)npad));
+        SBO_HIP(sbo::launch_row_l1(ctx->stream, ctx->aug.as<float>(), npad, p.I0, ctx->scratch.as<double>()));
+    }
+    if (!p.fused_norms) {
+        SBO_HIP(grow_keep(ctx, ctx->tile_lgn, 2 * sizeof(float4) * (size_t)sbo::total_tiles(p.nI),
+                          2 * sizeof(float4) * p.old_tiles));
+        SBO_HIP(sbo::launch_tile_norms(ctx->stream, ctx->aug.as<float>(), npad, p.I0, ctx->tile_lgn.as<float4>()));
+    }
+    if (p.f64) {   // (refresh_f32's pack wrote the coordinates)
+        if (p.aux) SBO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_trail, 0));
+        SBO_HIP(sbo::launch_pack_kcoord(ctx->stream, ctx->x.as<float>(), ctx->y.as<float>(), ctx->alpha.as<float>(),
+                                        p.n, npad, p.sf2, ctx->kcoord.as<float>()));
+        if (p.eager_x3)  // the split sweep's coordinates (its planes are on aux_stream)
+            SBO_HIP(sbo::launch_pack_x3(ctx->stream, nullptr, ctx->kcoord.as<float>(), npad, 0, 0, nullptr,
+                                        ctx->kc3.as<float>()));
+    }
+    if (packs_aux) SBO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_pack, 0));  // row sums and packs
+    return SBO_OK;
+}
+
+// The cutoff exponent L that keeps 2^-L `need` below one (16 .. 160), and the
+// two cutoffs of a |dV(q)|_2 budget tau2: every K* entry of a dropped tile is
+// below 2^-L, so each V_i moves by at most 2^-L max_i |A_i|_1 and |dV|_2 by
+// sqrt(N) times that; lg_tau: log2 of each row block's share tau2 / sqrt(nI).
+int skip_cut(double need) {
+    const double l2 = std::log2(std::max(need, 1.0));
+    return std::isfinite(l2) ? std::min(160, std::max(16, (int)std::ceil(l2))) : 160;
+}
+void skip_cutoffs(double max_row_l1, int64_t n, int64_t nI, double tau2, int &L, float &lg_tau) {
+    L = skip_cut(max_row_l1 * std::sqrt((double)n) / tau2);
+    lg_tau = (float)std::log2(tau2 / std::sqrt((double)nI));
+}
+
+// Error budget of the automatic K* tile cutoff (SBO_OPT_TILE_SKIP = -1),
+// B = SBO_OPT_SKIP_BUDGET: sigma^2 = sf2 - |V|^2 moves by at most
+// 2 |V|_2 |dV|_2 + |dV|_2^2 with |V|_2 <= sf2^(1/2), so |dV(q)|_2 <=
+// tau2 = 2^-B sf2^(1/2) / 2 (less 1 %) keeps it below 2^-B sf2.
+//  - tile-norm test (one row block per workgroup): row block I may lose
+//    |dV_I|_2 <= tau2 / sqrt(nI); a dropped tile t costs at most
+//    nu_It K*max(t), nu_It = min(16 max row sum, 8 |A_It|_F) (the tile's
+//    2-norm gain bound), and the kernel drops the smallest first.
+//  - distance cutoff (row-block chunks, and the reported L): every K*
+//    entry of a dropped tile is below 2^-L, so each V_i moves by at most
+//    2^-L max_i |A_i|_1 and |dV|_2 by sqrt(N) times that; L keeps it
+//    below tau2.
+// The mean (last row block) drops only tiles below 2^-L_mean, with
+// 2^-L_mean |sf2 alpha|_1 <= 2^-B sf2^(1/2).  Rows of earlier row blocks
+// are unchanged by an append: only the repacked row blocks are measured.
+sbo_status refresh_skip_budget(sbo_ctx *ctx, const RefreshPlan &p) {
+    const int64_t n = p.n, r0 = p.I0 * sbo::kBM;
+    std::vector<double> rl1((size_t)(p.npad - r0));
+    std::vector<float> ha((size_t)n);
+    SBO_HIP(hipMemcpyAsync(rl1.data(), ctx->scratch.as<double>() + r0, sizeof(double) * (p.npad - r0),
+                           hipMemcpyDeviceToHost, ctx->stream));
+    SBO_HIP(hipMemcpyAsync(ha.data(), ctx->alpha.as<float>(), sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
     SBO_HIP(hipStreamSynchronize(ctx->stream));
+    double mx = *std::max_element(rl1.begin(), rl1.end());
+    if (p.incr) mx = std::max(mx, ctx->max_row_l1);
+    ctx->max_row_l1 = mx;
+    double al1 = 0.0;
+    for (float v : ha) al1 += std::fabs((double)v);
+    ctx->alpha_l1 = al1 * p.sf2;
+    const double tol = std::ldexp(1.0, -ctx->skip_budget), sf = std::sqrt(p.sf2);
+    const double tau2 = tol * sf / 2.0 * 0.99;  // 1 % for the dV^2 term
+    skip_cutoffs(ctx->max_row_l1, n, p.nI, tau2, ctx->auto_skip_log2, ctx->lg_tau_v);
+    ctx->auto_skip_mean_log2 = skip_cut(ctx->alpha_l1 / (tol * sf));
+    return SBO_OK;
+}
+
+// The tile boxes, then every rocSOLVER info slot read in one sync: a singular
+// block anywhere (the first non-zero slot) is NOT_SPD.  Past that check the
+// packed operand is the context's: npad, and which derived operands are stale.
+sbo_status refresh_read_info(sbo_ctx *ctx, const RefreshPlan &p) {
+    SBO_HIP(ctx->kbox.reserve(sizeof(float4) * (size_t)(p.npad / sbo::kBK)));
+    SBO_HIP(sbo::launch_tile_boxes(ctx->stream, ctx->x.as<float>(), ctx->y.as<float>(), p.n, p.npad,
+                                   ctx->kbox.as<float4>()));
+    const int64_t nslots = info_slots(p.n);
+    std::vector<rocblas_int> hinfos((size_t)nslots);
+    SBO_HIP(hipMemcpyAsync(hinfos.data(), ctx->info.as<rocblas_int>(), sizeof(rocblas_int) * (size_t)nslots,
+                           hipMemcpyDeviceToHost, ctx->stream));
+    SBO_HIP(hipStreamSynchronize(ctx->stream));
+    rocblas_int hinfo = 0;
     for (rocblas_int v : hinfos)
         if (hinfo == 0) hinfo = v;
     if (hinfo != 0) ctx->linv_n = 0;
     SBO_CHECK(hinfo == 0, SBO_E_NOT_SPD, "trtri: singular factor (info=" + std::to_string(hinfo) + ")");
-    ctx->npad = npad;
-    if (x3_planes_aux) {
+    ctx->npad = p.npad;
+    if (p.eager_x3) {
         ctx->x3_I0 = INT64_MAX;
-        ctx->x3_layout = sbo::x3_layout(ctx->kernel_variant);
+        ctx->x3_layout = p.x3_layout;
     } else {
-        ctx->x3_I0 = std::min(ctx->x3_I0, I0);  // the split operand is derived lazily (run_tick)
-        if (!incr && ctx->a64_I0 != INT64_MAX) ctx->a64_I0 = 0;
+        ctx->x3_I0 = std::min(ctx->x3_I0, p.I0);  // the split operand is derived lazily (run_tick)
+        if (!p.incr && ctx->a64_I0 != INT64_MAX) ctx->a64_I0 = 0;
     }
-    // The precision probe before the guard's reading (round 6): the guard's
-    // three products on chk_stream run beside the probe's sweeps instead of
-    // ahead of them (C4: the guard finished ~0.7 ms after the tail's last
-    // kernel).  If the guard then fires, the fit's inverse is redone, and the
-    // probe with it only because the fallback below resets probe_n first (as
-    // fill_and_factor does for new data): probe_precision has just set it to
-    // n, and probe_due() would keep the rejected inverse's readings.
-    ctx->fitted = true;
-    const sbo_status pst = probe_precision(ctx);
-    if (pst != SBO_OK) return pst;   // (the drain waits for the guard)
-    if (chk_pending) {
-        sbo_inv_check r = ctx->chk_res;
-        const sbo_status rst = inverse_check_read(ctx, r);
-        drain.pending = false;   // (read: chk_stream is idle)
-        if (rst != SBO_OK) return rst;
-        r.err_fallback = r.err_mean_fallback = -1.0;
-        r.kept_digits = r.digits;
-        ctx->chk_res = r;
-        if (!ctx->inv_oz_off) record_inv_digits(ctx, r);
-        if (!inv_check_passed(ctx, r) && r.digits != 0 && !ctx->inv_oz_off) {
-            // the sliced inverse misses the guard's bound on the variance or
-            // the mean: a reduced-digit one is redone at SBO_OPT_INV_OZ
-            // digits, a full one with dgemm products -- the redone inverse is
-            // checked too (and a six-digit redo that misses tol goes on to
-            // dgemm products); reported as fired with the kept inverse's
-            // readings
-            const bool reduced = r.digits < ctx->inv_oz;
-            if (reduced)
-                ctx->inv_oz_cur = ctx->inv_oz;
-            else
-                ctx->inv_oz_off = true;
-            ctx->probe_n = 0;   // the probe above read the rejected inverse: measure the kept one
-            const sbo_status st = refresh_operand(ctx, 0);
-            ctx->inv_oz_off = false;
-            const sbo_inv_check f = ctx->chk_res;
-            ctx->chk_res = r;
-            ctx->chk_res.fired = 1;
-            ctx->chk_res.err_fallback = f.ran ? (f.fired ? f.err_fallback : f.err) : -1.0;
-            ctx->chk_res.err_mean_fallback = f.ran ? (f.fired ? f.err_mean_fallback : f.err_mean) : -1.0;
-            ctx->chk_res.kept_digits = f.ran ? f.kept_digits : 0;
-            ctx->chk_res.ms = r.ms + f.ms;
-            return st;
+    return SBO_OK;
+}
+
+// The guard's reading of this attempt's inverse, kept in chk_res; true when
+// the inverse has to be redone.
+sbo_status refresh_guard_verdict(sbo_ctx *ctx, InvAttempt attempt, bool &redo) {
+    sbo_inv_check r = ctx->chk_res;
+    if (sbo_status st = inverse_check_read(ctx, r)) return st;
+    r.err_fallback = r.err_mean_fallback = -1.0;
+    r.kept_digits = r.digits;
+    ctx->chk_res = r;
+    if (attempt != kInvDgemm) record_inv_digits(ctx, r);
+    redo = !inv_check_passed(ctx, r) && r.digits != 0 && attempt != kInvDgemm;
+    return SBO_OK;
+}
+
+// Rebuild alpha, L^-1 and the packed predictive operand from the current L
+// (n_old > 0: an append of rows n_old..n-1, inverse_incremental -- only the
+// row blocks that hold new rows are repacked; alpha, the per-k coordinates
+// and the tile boxes are rebuilt in full, O(n^2) and O(n)).  ho: what the
+// factorization that just ran handed over (blocked_potrf).
+// The guard's redo: a sliced inverse that misses the guard's bound on the
+// variance or the mean is redone -- a reduced-digit one at SBO_OPT_INV_OZ
+// digits, a full one with dgemm products; the redone inverse is checked too
+// (and a six-digit redo that misses tol goes on to dgemm products) -- and
+// reported as fired with the kept inverse's readings.
+// The caller's FitCommit waits for a guard still in flight when a stage fails.
+sbo_status refresh_operand(sbo_ctx *ctx, int64_t n_old = 0, FactorHandover ho = {}) {
+    sbo_inv_check first{};   // the reading that fired, and the rejected attempts' guard time
+    bool fired = false;
+    float ms_rejected = 0.0f;
+    for (InvAttempt attempt = kInvChosen;;) {
+        if (sbo_status st = drain_poz(ctx)) return st;
+        const RefreshPlan p = plan_refresh(ctx, n_old, ho, attempt);
+        if (sbo_status st = refresh_begin(ctx, p)) return st;
+        if (p.f64) {
+            if (sbo_status st = refresh_inverse(ctx, p)) return st;
+            if (sbo_status st = refresh_guard_launch(ctx, p)) return st;
+            if (sbo_status st = refresh_alpha(ctx, p)) return st;
+            if (sbo_status st = refresh_packs(ctx, p)) return st;
+        } else {
+            if (sbo_status st = refresh_f32(ctx, p)) return st;
         }
+        if (sbo_status st = refresh_join(ctx, p)) return st;
+        if (sbo_status st = refresh_skip_budget(ctx, p)) return st;
+        if (sbo_status st = refresh_read_info(ctx, p)) return st;
+        // The precision probe before the guard's reading (round 6): the guard's
+        // three products on chk_stream run beside the probe's sweeps instead of
+        // ahead of them (C4: the guard finished ~0.7 ms after the tail's last
+        // kernel).  If the guard then fires, the fit's inverse is redone, and the
+        // probe with it only because probe_n is reset first (as fill_and_factor
+        // does for new data): probe_precision has just set it to n, and
+        // probe_due() would keep the rejected inverse's readings.
+        if (sbo_status st = probe_precision(ctx)) return st;
+        if (!p.guard) break;
+        bool redo = false;
+        if (sbo_status st = refresh_guard_verdict(ctx, attempt, redo)) return st;
+        if (!redo) break;
+        if (!fired) first = ctx->chk_res;
+        fired = true;
+        ms_rejected += ctx->chk_res.ms;
+        if (ctx->chk_res.digits < ctx->inv_oz) {
+            attempt = kInvFullDigits;
+            ctx->inv_oz_cur = ctx->inv_oz;   // (the digits this fit's inverse ends up with)
+        } else {
+            attempt = kInvDgemm;
+        }
+        ctx->probe_n = 0;   // the probe above read the rejected inverse: measure the kept one
+        n_old = 0;          // the redo is a full refresh, with nothing handed over
+        ho = FactorHandover{};
+    }
+    if (fired) {
+        const sbo_inv_check f = ctx->chk_res;   // the kept inverse's reading
+        ctx->chk_res = first;
+        ctx->chk_res.fired = 1;
+        ctx->chk_res.err_fallback = f.ran ? f.err : -1.0;
+        ctx->chk_res.err_mean_fallback = f.ran ? f.err_mean : -1.0;
+        ctx->chk_res.kept_digits = f.ran ? f.kept_digits : 0;
+        ctx->chk_res.ms = ms_rejected + f.ms;
     }
     return SBO_OK;
 }
 
 // The precise sweep's budget: the same construction as the automatic cutoff
-// (refresh_operand) with the tolerance 2^-B times the smallest variance the
+// (refresh_skip_budget) with the tolerance 2^-B times the smallest variance the
 // probe saw inside the training box instead of 2^-B sf2 -- the 1e-5 contract
 // is relative to the largest variance of a query set, and in the dense
 // regime that is orders below sf2.
@@ -1234,11 +1411,7 @@ sbo_status refresh_operand(sbo_ctx *ctx, int64_t n_old = 0) {
 // dropped tiles' effect on any variance below tol (absolute)
 void skip_budget_for(const sbo_ctx *ctx, double tol, int &L, float &lg_tau) {
     const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f, sf = std::sqrt(sf2);
-    const double tau2 = tol / (2.0 * sf) * 0.99;
-    const double need = ctx->max_row_l1 * std::sqrt((double)ctx->n) / tau2;
-    const double l2 = std::log2(std::max(need, 1.0));
-    L = std::isfinite(l2) ? std::min(160, std::max(16, (int)std::ceil(l2))) : 160;
-    lg_tau = (float)std::log2(tau2 / std::sqrt((double)(ctx->npad / sbo::kBM)));
+    skip_cutoffs(ctx->max_row_l1, ctx->n, ctx->npad / sbo::kBM, tol / (2.0 * sf) * 0.99, L, lg_tau);
 }
 void precise_budget(sbo_ctx *ctx) {
     const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
@@ -1289,27 +1462,20 @@ sbo_status probe_precision(sbo_ctx *ctx) {
         const int MT = (int)std::min<int64_t>(n, ctx->probe_train), M = MG + MT;
         const int64_t stride = n / MT;     // >= 1
         std::vector<float> h(2 * (size_t)M);
-        for (int i = 0; i < G; ++i)
-            for (int j = 0; j < G; ++j) {
-                h[i * G + j] = ctx->bbox[0] + (ctx->bbox[1] - ctx->bbox[0]) * (float)j / (float)(G - 1);
-                h[M + i * G + j] = ctx->bbox[2] + (ctx->bbox[3] - ctx->bbox[2]) * (float)i / (float)(G - 1);
-            }
+        bbox_lattice(ctx->bbox, G, h.data(), h.data() + M);
         SBO_HIP(ctx->qprobe.reserve(sizeof(float) * 2 * M));
         SBO_HIP(ctx->oprobe.reserve(sizeof(float) * 2 * M + sizeof(sbo_key)));
         float *qx = ctx->qprobe.as<float>(), *qy = qx + M, *sdf = ctx->oprobe.as<float>(), *sdp = sdf + M;
         sbo_key *key = reinterpret_cast<sbo_key *>(sdp + M);
         SBO_HIP(hipMemcpyAsync(qx, h.data(), sizeof(float) * MG, hipMemcpyHostToDevice, ctx->stream));
         SBO_HIP(hipMemcpyAsync(qy, h.data() + M, sizeof(float) * MG, hipMemcpyHostToDevice, ctx->stream));
-        // the training part: every stride-th stored point (a strided 2-D copy)
-        SBO_HIP(hipMemcpy2DAsync(qx + MG, sizeof(float), ctx->x.as<float>() + stride / 2, sizeof(float) * stride,
-                                 sizeof(float), (size_t)MT, hipMemcpyDeviceToDevice, ctx->stream));
-        SBO_HIP(hipMemcpy2DAsync(qy + MG, sizeof(float), ctx->y.as<float>() + stride / 2, sizeof(float) * stride,
-                                 sizeof(float), (size_t)MT, hipMemcpyDeviceToDevice, ctx->stream));
+        // the training part: every stride-th stored point
+        if (sbo_status cst = copy_strided_points(ctx, ctx->stream, stride, MT, qx + MG, qy + MG)) return cst;
         const bool prof = ctx->prof;
         ctx->prof = false;  // (the probe is not a tick: no events, no counters)
-        ctx->order_p = nullptr;
+        QueryOrder order;
         sbo_status st = run_tick(ctx, qx, qy, M, 0.0, 0.0, SBO_SCORE_WIDTH, 0, nullptr, sdf, nullptr, nullptr,
-                                 nullptr, key, nullptr, kSweepFast);
+                                 nullptr, key, nullptr, kSweepFast, &order);
         if (st == SBO_OK) {
             // the reference's budget: 2^-kProbeRefBits of the largest variance
             // the fast sweep sees (its own error is orders below that: any
@@ -1329,10 +1495,8 @@ sbo_status probe_precision(sbo_ctx *ctx) {
         if (st == SBO_OK) {
             // the same queries as the fast sweep's: its Morton order again
             // (qwork untouched in between)
-            ctx->reuse_order = true;
             st = run_tick(ctx, qx, qy, M, 0.0, 0.0, SBO_SCORE_WIDTH, 0, nullptr, sdp, nullptr, nullptr, nullptr, key,
-                          nullptr, kSweepPreciseDense);
-            ctx->reuse_order = false;
+                          nullptr, kSweepPreciseDense, &order);
         }
         ctx->prof = prof;
         if (st != SBO_OK) return st;
@@ -1389,10 +1553,12 @@ sbo_status probe_precision(sbo_ctx *ctx) {
 // which leave most CUs idle (one-workgroup diagonal blocks, small trailing
 // updates).  inv_stream is CU-masked to leave R CUs to the chain, whose
 // kernels would otherwise queue behind the long dgemm workgroups.
-// refresh_operand finishes the inverse (early_inv_n).
-sbo_status blocked_potrf(sbo_ctx *ctx, float *L, int64_t n, int64_t ld, rocblas_int *info, bool early_inv = false) {
+// refresh_operand finishes the inverse.  *out (may be null): what was handed
+// over -- the widened factor, the first half and its info slots.
+sbo_status blocked_potrf(sbo_ctx *ctx, float *L, int64_t n, int64_t ld, rocblas_int *info, bool early_inv = false,
+                         FactorHandover *out = nullptr) {
+    FactorHandover ho;
     SBO_HIP(hipMemsetAsync(info, 0, sizeof(rocblas_int), ctx->stream));
-    ctx->early_inv_n = 0;
     const bool early = early_inv && ctx->inv_overlap > 0 && n > ctx->inv_base;
     const int64_t h_inv = early ? inverse_split(n, ctx->inv_base) : -1;
     bool early_pending = false;
@@ -1468,7 +1634,6 @@ sbo_status blocked_potrf(sbo_ctx *ctx, float *L, int64_t n, int64_t ld, rocblas_
         SBO_HIP(ctx->Linv.reserve(sizeof(double) * (size_t)ld * (size_t)ld));
         Lw = ctx->Linv.as<double>();
     }
-    ctx->widened_n = 0;
     const float one = 1.0f, minus_one = -1.0f;
     // Two levels (SBO_OPT_CHOL_OUTER = NB2 > kCholNB): outer panels of NB2
     // columns, each factored by the kCholNB chain above with its updates kept
@@ -1532,9 +1697,9 @@ sbo_status blocked_potrf(sbo_ctx *ctx, float *L, int64_t n, int64_t ld, rocblas_
                 const int64_t hq = inverse_split(n, ctx->inv_base);
                 if ((st = inverse_first_half(ctx, ctx->blas_inv, ctx->Linv.as<double>(), n, ld,
                                              ctx->scratch.as<double>(),
-                                             ctx->scratch.as<double>() + hq * (n - hq), slot)) != SBO_OK)
+                                             ctx->scratch.as<double>() + hq * (n - hq), slot, InvMode{})) != SBO_OK)
                     break;
-                ctx->inv_slot = slot;
+                ho.half_slots = slot;
                 if (hipEventRecord(ctx->ev_inv, ctx->inv_stream) != hipSuccess) { st = SBO_E_DEVICE; break; }
             }
             // the outer panel's remaining columns (rows below this block)
@@ -1650,26 +1815,26 @@ sbo_status blocked_potrf(sbo_ctx *ctx, float *L, int64_t n, int64_t ld, rocblas_
                                      (size_t)(n - Kw), ctx->stream));
         SBO_HIP(hipEventRecord(ctx->ev_trail, ctx->aux_stream));
         SBO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_trail, 0));
-        ctx->widened_n = n;
+        ho.widened_n = n;
     }
     if (early_pending) {
         SBO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_inv, 0));
-        ctx->early_inv_n = n;
+        ho.half_n = n;
     }
+    if (out) *out = ho;
     return SBO_OK;
 }
 
 sbo_status factor_and_refresh(sbo_ctx *ctx) {
     rocblas_int *info = ctx->info.as<rocblas_int>();
-    ctx->inv_oz_cur = choose_inv_digits(ctx);   // (before blocked_potrf: its early first half slices too)
-    ctx->widened_n = 0;
-    // only the factorization that runs now may hand the inverse's first half
-    // to refresh_operand (blocked_potrf sets it; the rocSOLVER path never
-    // does, and a failed overlapped fit must not leave a stale one behind)
-    ctx->early_inv_n = 0;
+    ctx->inv_oz_cur = choose_inv_digits(ctx);
+    // only the factorization that runs now hands anything to refresh_operand
+    // (the rocSOLVER path never does)
+    FactorHandover ho;
     if (ctx->chol_blocked) {
         const bool early_inv = ctx->inverse_bits == 64 && ctx->inverse_rec;
-        if (sbo_status st = blocked_potrf(ctx, ctx->L.as<float>(), ctx->n, ctx->cap, info, early_inv); st != SBO_OK)
+        if (sbo_status st = blocked_potrf(ctx, ctx->L.as<float>(), ctx->n, ctx->cap, info, early_inv, &ho);
+            st != SBO_OK)
             return st;
         info = ctx->info.as<rocblas_int>();   // (blocked_potrf may have grown it)
     } else {
@@ -1680,19 +1845,17 @@ sbo_status factor_and_refresh(sbo_ctx *ctx) {
     SBO_HIP(hipMemcpyAsync(&hinfo, info, sizeof(hinfo), hipMemcpyDeviceToHost, ctx->stream));
     SBO_HIP(hipStreamSynchronize(ctx->stream));
     if (hinfo != 0) {
-        ctx->fitted = false;
-        ctx->early_inv_n = 0;
         ctx->err = "spotrf: leading minor " + std::to_string(hinfo) + " not positive definite";
         return SBO_E_NOT_SPD;
     }
     ctx->has_factor = true;
-    return refresh_operand(ctx);
+    return refresh_operand(ctx, 0, ho);
 }
 
 // Predictive sweep + acquisition over m queries already on the device.
 sbo_status run_tick(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, double beta, double f_min,
                     int score_kind, int64_t index_offset, float *mu, float *sd, double *lo, double *hi,
-                    uint8_t *safe, sbo_key *key_dev, float *cost, int sweep) {
+                    uint8_t *safe, sbo_key *key_dev, float *cost, int sweep, QueryOrder *order) {
     const int64_t nI = ctx->npad / sbo::kBM;
     if (sweep == kSweepCtx) sweep = ctx->precise ? kSweepPrecise : kSweepFast;
     SBO_CHECK(sweep == kSweepFast || (ctx->has_factor && ctx->linv_n == ctx->n && ctx->inverse_bits == 64),
@@ -1756,17 +1919,15 @@ sbo_status run_tick(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, d
         if (ctx->query_order == 1 && ctx->qgrid.ok) {
             SBO_HIP(sbo::launch_query_grid(ctx->stream, qx, qy, m, ctx->qgrid, ctx->qgwork.as<void>(), &p, &sx, &sy));
             ms = ctx->qgrid.ms;
-        } else if (ctx->reuse_order && ctx->order_p) {
-            p = ctx->order_p;    // (the probe's second sweep: the same queries, already ordered)
-            sx = ctx->order_sx;
-            sy = ctx->order_sy;
+        } else if (order && order->perm) {
+            p = order->perm;    // (the probe's second sweep: the same queries, already ordered)
+            sx = order->sx;
+            sy = order->sy;
         } else {
             const size_t wb = sbo::query_order_bytes(m);
             SBO_HIP(ctx->qwork.reserve(wb));
             SBO_HIP(sbo::launch_query_order(ctx->stream, qx, qy, m, ctx->bbox, ctx->qwork.as<void>(), wb, &p, &sx, &sy));
-            ctx->order_p = p;
-            ctx->order_sx = sx;
-            ctx->order_sy = sy;
+            if (order) *order = QueryOrder{p, sx, sy};
         }
         perm = p;
         qx = sx;
@@ -2066,6 +2227,7 @@ sbo_status fill_and_factor(sbo_ctx *ctx, double base_noise) {
         }
         ctx->hyper.noise_level = base_noise;
         if (st != SBO_E_NOT_SPD || r >= ctx->jitter_retries) return st;
+        drain_guard(ctx);   // (the retry rewrites L)
     }
 }
 
@@ -2105,7 +2267,6 @@ sbo_status resort_append(sbo_ctx *ctx, const float *x, const float *y, const flo
         SBO_HIP(ctx->L.reserve(sizeof(float) * (size_t)ncap * (size_t)ncap));
         ctx->cap = ncap;
     }
-    ctx->fitted = false;
     ctx->n = n1;
     ctx->linv_n = 0;
     if (sbo_status st = stage_training(ctx, tx, ty, to, n1, 0, 0, SBO_DEVICE_PTRS)) return st;
@@ -2123,7 +2284,7 @@ SBO_API sbo_status sbo_fit(sbo_ctx *ctx, const float *x, const float *y, const f
     if (sbo_status st = check_hyper(ctx, hyper)) return st;
     SBO_HIP(hipSetDevice(ctx->device));
     if (sbo_status st = drain_poz(ctx)) return st;   // (a precise pack may still read x, y, L^-1, alpha64)
-    ctx->fitted = false;
+    FitCommit fc(ctx);
     ctx->hyper = hyper;
     ctx->n = n;
     ctx->cap = n;
@@ -2135,7 +2296,7 @@ SBO_API sbo_status sbo_fit(sbo_ctx *ctx, const float *x, const float *y, const f
     SBO_HIP(ctx->L.reserve(sizeof(float) * (size_t)n * (size_t)n));
     if (sbo_status st = stage_training(ctx, x, y, obs, n, 0, 0, flags)) return st;
     if (sbo_status st = fill_and_factor(ctx, hyper.noise_level)) return st;
-    return finish(ctx, flags);
+    return fc.commit(finish(ctx, flags));
 }
 
 SBO_API sbo_status sbo_get_jitter(const sbo_ctx *ctx, double *jitter) {
@@ -2157,12 +2318,13 @@ SBO_API sbo_status sbo_append(sbo_ctx *ctx, const float *x, const float *y, cons
     if (sbo_status st = drain_poz(ctx)) return st;   // (a precise pack may still read x, y, L^-1, alpha64)
     const int64_t n0 = ctx->n, n1 = n0 + b;
     SBO_CHECK(n1 < (int64_t)1 << 30, SBO_E_INVAL, "sbo_append: n too large");
+    FitCommit fc(ctx);
     const float sf2 = (float)(ctx->hyper.sigma_f * ctx->hyper.sigma_f);
     // SBO_OPT_RESORT: once the points appended since the last k-d sort exceed
     // resort_pct % of the sorted ones, re-sort and refactor all of them
     if (ctx->resort_pct > 0 && ctx->spatial_order != 0 && (n1 - ctx->n_sorted) * 100 > ctx->n_sorted * ctx->resort_pct) {
         if (sbo_status st = resort_append(ctx, x, y, obs, b, flags)) return st;
-        return finish(ctx, flags);
+        return fc.commit(finish(ctx, flags));
     }
 
     // grow storage (geometric) preserving the factor
@@ -2258,13 +2420,12 @@ SBO_API sbo_status sbo_append(sbo_ctx *ctx, const float *x, const float *y, cons
     SBO_HIP(hipMemcpyAsync(&hinfo, info, sizeof(hinfo), hipMemcpyDeviceToHost, ctx->stream));
     SBO_HIP(hipStreamSynchronize(ctx->stream));
     if (hinfo != 0) {
-        ctx->fitted = false;
         ctx->err = "sbo_append: updated block not positive definite (info=" + std::to_string(hinfo) + ")";
         return SBO_E_NOT_SPD;
     }
     ctx->n = n1;
     if (sbo_status st = refresh_operand(ctx, n0)) return st;
-    return finish(ctx, flags);
+    return fc.commit(finish(ctx, flags));
 }
 
 SBO_API sbo_status sbo_predict(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, float *mu, float *sd,
@@ -2870,8 +3031,6 @@ SBO_API sbo_status sbo_warmup(sbo_ctx *ctx, int64_t n_cap, int64_t m_cap, sbo_hy
     ctx->probe_n = 0;
     ctx->precise = false;
     ctx->n_sorted = 0;
-    ctx->widened_n = 0;
-    ctx->early_inv_n = 0;
     ctx->order.clear();
     ctx->chk_res = sbo_inv_check{};
     ctx->inv_oz_next = 0;   // (the synthetic fit's guard reading says nothing about the real data)
@@ -3194,7 +3353,7 @@ SBO_API sbo_status sbo_import_state(sbo_ctx *ctx, const void *dev_buf, int64_t b
             return st;
         }
     }
-    ctx->fitted = false;
+    FitCommit fc(ctx);
     ctx->has_factor = false;
     ctx->precise = false;   // no f64 inverse travels: an imported state ticks with the fast sweep
     ctx->probe_n = 0;
@@ -3239,8 +3398,7 @@ SBO_API sbo_status sbo_import_state(sbo_ctx *ctx, const void *dev_buf, int64_t b
     ctx->lg_tau_v = h.lg_tau_v;
     ctx->spatial_order = h.spatial_order;
     ctx->x3_I0 = 0;
-    ctx->fitted = true;
-    return SBO_OK;
+    return fc.commit(SBO_OK);
 }
 
 }  // extern "C"

@@ -109,7 +109,7 @@ struct sbo_ctx {
     hipEvent_t ev_poz = nullptr;
     bool poz_pending = false;
     int chol_gemm_own = 4;       // SBO_OPT_CHOL_GEMM: 4 (default) / 5 the outer panels' updates int8-sliced, 3 split bf16, 2 every update by chol_update_kernel, 1 the small trailing ones, 0 rocBLAS
-    int chol_diag = 1;           // SBO_OPT_CHOL_DIAG: 1 the MFMA chain kernels (diagonal block, panel), 0 the VALU ones (bitwise equal)
+    int chol_diag = 1;           // SBO_OPT_CHOL_DIAG: the chain kernels (diagonal block, panel): 1 left-looking MFMA, 2 right-looking MFMA, 0 VALU (bitwise equal)
     int chol_outer = 1024;       // SBO_OPT_CHOL_OUTER: outer panel width of the two-level Cholesky (128: one level)
     // the recursive inverse's first half beside the Cholesky's last steps
     // (SBO_OPT_INV_OVERLAP = R > 0: on inv_stream, CU-masked to leave R CUs free)
@@ -121,7 +121,6 @@ struct sbo_ctx {
     int64_t inv_panels = 16;     // SBO_OPT_INV_PANELS: dgemm panels per product of the recursion
     int inv_oz = 6;              // SBO_OPT_INV_OZ: digits of the int8-sliced top-level products (0: dgemm)
     int64_t inv_oz_min = 0;      // SBO_OPT_INV_OZ_MIN: the smallest sliced split (0: 2048 at N >= 12288, else 4096)
-    bool inv_oz_off = false;     // (set while a fit redoes its inverse with dgemm products: the guard fired)
     // SBO_OPT_INV_OZ_ADAPT: the digits of the current fit's sliced products
     // (inv_digits), those the last guard reading allows for the next fit of
     // the same hyper-parameters, about the same N and box area (0: inv_oz), that
@@ -140,15 +139,13 @@ struct sbo_ctx {
     hipEvent_t ev_chk0 = nullptr, ev_chk1 = nullptr;
     sbo::DevBuf chk;
     sbo_inv_check chk_res{};     // (ran = 0: none since the last fit)
-    int64_t early_inv_n = 0;     // n of a factor whose inverse's first half is done (refresh_operand finishes it)
-    int inv_slot = 0;            // info slots the first half used (1 .. inv_slot)
     std::string err;
 
     // fitted model
     int64_t n = 0;       // training points
     int64_t cap = 0;     // allocated leading dimension of L (>= n, for appends)
     sbo_hyper hyper{0.4, 1.0, 0.1, 0.0};
-    bool fitted = false;
+    bool fitted = false;         // written true only by FitCommit::commit (sbo_api.cpp)
     bool has_factor = false;     // false after sbo_import_state: predict-only (no L to append to)
 
     sbo::DevBuf x, y, obs;       // training data, f32, capacity cap
@@ -184,11 +181,6 @@ struct sbo_ctx {
     sbo::DevBuf plan_work;       // the tick's tile plan (launch_plan)
     sbo::DevBuf fwork, fowner, fimg, fpix, fout;  // device frontier (sbo_frontier / sbo_subgoal)
     sbo::DevBuf qwork;           // query ordering workspace
-    // the probe's second sweep reads the same queries: reuse the first's
-    // Morton order (pointers into qwork; valid only while reuse_order is set)
-    bool reuse_order = false;
-    int32_t *order_p = nullptr;
-    float *order_sx = nullptr, *order_sy = nullptr;
     sbo::DevBuf kbox;            // per k-tile bounding boxes (float4)
     sbo::DevBuf alpha;           // K^-1 (y - m0), length cap
     sbo::DevBuf aug;             // packed sf2 * L^-1 tiles
@@ -231,8 +223,6 @@ struct sbo_ctx {
     int reprobe_pct = 25;        // SBO_OPT_REPROBE: appends re-probe once N grew by this share (0: every append)
     bool inv_batched = true;      // SBO_OPT_INV_LEAVES: the recursion's base cases inverted up front, batched
     bool inv_leaves_own = true;   // (SBO_OPT_INV_LEAVES 2, default: by doubling from 128-column blocks, inverse_leaves)
-    bool inv_leaves_done = false; // (set while a recursion runs whose base cases are already inverted)
-    int64_t widened_n = 0;       // blocked_potrf widened the factor into Linv (n) for refresh_operand
     double probe_ref_tol = 0.0;  // the probe reference sweep's skip budget (absolute variance)
     int p_skip_log2 = 160;       // the precise plan's cutoffs and budget (2^-B of the probe's smallest variance)
     float p_lg_tau_v = -1000.0f;
@@ -366,8 +356,10 @@ inline bool variant_allowed(int v) {
 }
 inline int x3_layout(int variant) { return (variant == 13 || variant == 14) ? 1 : 0; }
 // The sweep over the plan with the split operand; qx/qy must be readable in
-// whole 128-query blocks (padded to round_up(m, kBN)).  variant: 2 (4-7:
-// timing diagnostics with parts of the work left out).
+// whole 128-query blocks (padded to round_up(m, kBN)).  variant: 3 (the
+// default, honouring the plan's precision levels) or 22 (every kept tile at
+// six products); the diagnostic build's timing variants go through
+// csrc/diag/predict_x3_diag.hip.
 // Diagnostic build (SBO_OPT_KERNEL_VARIANT 39): summed phase cycles of the
 // split sweep since the last read (see g_x3_stamps), then reset.
 hipError_t read_x3_stamps(double *out, int n);
@@ -385,7 +377,8 @@ hipError_t launch_pack_tile_norms(hipStream_t s, const double *Linv, int64_t ld,
 // Blocked Cholesky: factor the kb x kb diagonal block at A (column-major,
 // lda = ld) of step k0 in place (kb <= kCholNB); info as rocSOLVER's.
 constexpr int kCholNB = 128;
-// version 1: chol_diag_mfma_kernel (16-column panels, MFMA trailing updates; default), 0: chol_diag_kernel
+// version (SBO_OPT_CHOL_DIAG) 1: chol_diag_ll_kernel (left-looking, one MFMA chain per block; default),
+// 2: chol_diag_mfma_kernel (right-looking, 16-column panels), 0: chol_diag_kernel (VALU); bitwise equal
 hipError_t launch_chol_diag(hipStream_t s, float *A, int64_t ld, int kb, int64_t k0, int *info, int version = 1);
 // C -= P Q^T over 128 x 128 tiles (lower: the tiles on and below the diagonal of an m x m C), f32, lda ld, K columns
 hipError_t launch_chol_update(hipStream_t s, const float *P, const float *Q, int64_t ld, int64_t m, int64_t nc,
@@ -400,7 +393,8 @@ hipError_t launch_chol_split(hipStream_t s, const float *P, int64_t ld, int64_t 
 hipError_t launch_chol_update_x3(hipStream_t s, const char *planes, int64_t m, int64_t K, int64_t r0, int64_t rows,
                                  int64_t c0, int64_t cols, bool lower, float *C, int64_t ld);
 // The panel below it: A21 (m2 x kb, lda ld) := A21 L11^-T (forward substitution, f32).
-// version 1: chol_trsm_mfma_kernel (MFMA updates of the later columns; default), 0: chol_trsm_kernel (bitwise equal)
+// version 1: chol_trsm_ll_kernel (left-looking MFMA; default), 2: chol_trsm_mfma_kernel (right-looking),
+// 0: chol_trsm_kernel (VALU); bitwise equal
 hipError_t launch_chol_trsm(hipStream_t s, const float *L11, int64_t ld, int kb, float *A21, int64_t m2, int version = 1);
 // d = (double)in - v;  out = (float)d
 hipError_t launch_widen_sub(hipStream_t s, const float *in, double v, int64_t n, double *d);
