@@ -628,6 +628,15 @@ SBO_API sbo_status sbo_profile_mfma(sbo_ctx *ctx, double *mfma_flops, int64_t *t
  * product(s), half-steps at six / three / one product(s); then reset. */
 SBO_API sbo_status sbo_debug_x3_stamps(sbo_ctx *ctx, double *cycles, int n);
 
+/* Test accessor: the split (bf16 x3) operand of the fitted state, brought up
+ * to date and copied to host memory, in the layout the split sweep stages
+ * (csrc/predict_x3_rowhalf.hpp): packed tile T (the order of the f32 packed
+ * operand), row half R, plane p, row block rb of the half, k half h, lane
+ * l = 16 g + r holds A[16 (8R + rb) + r][32 h + 8 g + j], j = 0..7, as bf16 at
+ * byte T*98304 + R*49152 + p*16384 + (2 rb + h)*1024 + l*16 + 2j.  *bytes is
+ * the operand's size; host_buf may be null to ask for it alone. */
+SBO_API sbo_status sbo_debug_x3_operand(sbo_ctx *ctx, void *host_buf, int64_t cap, int64_t *bytes);
+
 /* Test accessors: the int8-sliced GEMM under the fit (csrc/ozgemm.hip), run
  * alone on the context's stream so that tests/test_gpu_ozgemm.py can hold the
  * product's object code bit for bit to an integer model (tests/oz_model.py).

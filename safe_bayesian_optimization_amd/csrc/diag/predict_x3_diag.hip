@@ -1,9 +1,12 @@
 // diag/predict_x3_diag.hip -- the split sweep with every A/B and timing
 // variant of rounds 1-3 (the DIAG template mask): built only into the
 // diagnostic library (make diag, -DSBO_DIAG, lib/libsbo_diag.so, selected by
-// SBO_LIB for tools/).  The product sweep is ../predict_x3.hip: variant 3 of
-// this file with its options fixed, one code path; variant 3 here is bitwise
-// that kernel (tools/compare_libs.py).
+// SBO_LIB for tools/).  The product sweep (../predict_x3.hip) is the kernel of
+// ../predict_x3_rowhalf.hpp on row-half stages (64 k x 128 rows); variants 3
+// and 22 here launch that same kernel.  Everything below is its predecessor
+// on k-half stages (32 k x 256 rows, x3_layout 0) with the A/B and timing
+// variants built on it; variant 62 is the predecessor with variant 3's
+// options, bitwise variant 3 (tests/test_gpu_x3_rowhalf.py).
 //
 // Every f32 operand value v is split into three bf16 pieces, v = v0 + v1 + v2
 // (round to nearest at each step: |v1| <= 2^-8 |v|, |v2| <= 2^-16 |v|, the
@@ -39,7 +42,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "../sbo_internal.hpp"
+#include "../predict_x3_rowhalf.hpp"
 
 namespace sbo {
 namespace {
@@ -951,10 +954,15 @@ hipError_t launch_pack_x3(hipStream_t s, const float *aug, const float *kcoord, 
     const int64_t nI = npad / kBM;
     const int64_t T0 = tile_start(I0), T1 = tile_start(nI);
     if (ax3 && T1 > T0) {
-        const int64_t th = (T1 - T0) * 2048;
-        hipLaunchKernelGGL(pack_x3_kernel, dim3((unsigned)((th + 255) / 256)), dim3(256), 0, s, aug, T0, T1 - T0, wide,
-                           ax3);
-        hipError_t e = hipGetLastError();
+        hipError_t e;
+        if (wide == 2) {  // the row-half layout of variants 3 and 22 (the product's)
+            e = x3r::launch_pack(s, aug, T0, T1 - T0, ax3);
+        } else {
+            const int64_t th = (T1 - T0) * 2048;
+            hipLaunchKernelGGL(pack_x3_kernel, dim3((unsigned)((th + 255) / 256)), dim3(256), 0, s, aug, T0, T1 - T0,
+                               wide, ax3);
+            e = hipGetLastError();
+        }
         if (e != hipSuccess) return e;
     }
     if (!kc3) return hipSuccess;
@@ -998,12 +1006,14 @@ hipError_t launch_predict_x3(hipStream_t s, const char *ax3, const float *kc3, c
 #define SBO_X3_LAUNCH(NC, D) \
     hipLaunchKernelGGL((predict_x3_kernel<NC, D>), dim3((unsigned)P), dim3(NC == 1 ? 512 : 256), 0, s, ax3, kc3, desc, rec, \
                        seg, P, n_items, nI, a_max, rot, qx, qy, m, ldp, cexp, m0, part, mean)
+    // 3 and 22: the product's kernel (../predict_x3_rowhalf.hpp, the row-half layout)
+    if (variant == 3 || variant == 22)
+        return x3r::launch_sweep(s, ax3, kc3, desc, rec, seg, P, n_items, nI, a_max, qx, qy, m, ldp, cexp, m0, part, mean);
     switch (variant) {
         case 2: SBO_X3_LAUNCH(2, 16); break;   // four waves of 32 queries
         case 9: SBO_X3_LAUNCH(1, 0); break;    // A pieces in a burst at the top of the step
         case 10: SBO_X3_LAUNCH(1, 48); break;  // A fragments one row block ahead
         case 13: SBO_X3_LAUNCH(3, 16); break;  // wide shape: 32x32x16 MFMA, four waves of 32 queries
-        case 22: SBO_X3_LAUNCH(1, 16); break;    // variant 3 with every tile at full precision
 #ifdef SBO_DIAG
         case 4: SBO_X3_LAUNCH(2, 17); break;   // diagnostics: no next-step K*
         case 5: SBO_X3_LAUNCH(2, 18); break;   //   no A pieces
@@ -1057,7 +1067,8 @@ hipError_t launch_predict_x3(hipStream_t s, const char *ax3, const float *kc3, c
         case 59: SBO_X3_LAUNCH(1, 73776 + 33554432 + 1073741824 + 4294967296LL); break;  // variant 3, mean terms by a select (no branch)
         case 58: SBO_X3_LAUNCH(1, 73776 + 33554432 + 1073741824 + 67108864 + 2147483648LL); break;  // variant 3, one-product bodies split by the mean test at compile time
 #endif
-        default: SBO_X3_LAUNCH(1, 73776 + 33554432 + 1073741824 + 67108864); break;  // 3: eight waves of 16 queries, A pieces spread, tile levels, A 1 / 2 / 4 blocks ahead, next coordinates at ph 1, kh-only split between one-product steps, sf2 alpha read only before the mean's row block
+        case 62: SBO_X3_LAUNCH(1, 73776 + 33554432 + 1073741824 + 67108864); break;  // 62: variant 3's predecessor on k-half stages (32 k x 256 rows, chains over two steps), bitwise variant 3 -- eight waves of 16 queries, A pieces spread, tile levels, A 1 / 2 / 4 blocks ahead, next coordinates at ph 1, kh-only split between one-product steps, sf2 alpha read only before the mean's row block
+        default: return hipErrorInvalidValue;   // (no variant of that number)
     }
 #undef SBO_X3_LAUNCH
     return hipGetLastError();

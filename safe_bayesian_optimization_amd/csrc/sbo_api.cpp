@@ -699,6 +699,25 @@ struct QueryOrder {
     int32_t *perm = nullptr;
     float *sx = nullptr, *sy = nullptr;
 };
+// The split operand of the current kernel variant's layout, brought up to
+// date on ctx->stream: the bf16 planes of any row block repacked since it was
+// last derived (all of them after a change of layout) and the coordinates.
+sbo_status derive_x3(sbo_ctx *ctx) {
+    const int64_t nIc = ctx->npad / sbo::kBM;
+    const int layout = sbo::x3_layout(ctx->kernel_variant);
+    if (layout != ctx->x3_layout) ctx->x3_I0 = 0;  // another layout: derive all of it
+    if (ctx->x3_I0 < nIc) {
+        const int64_t I0 = std::max<int64_t>(ctx->x3_I0, 0);
+        SBO_HIP(grow_keep(ctx, ctx->ax3, sbo::x3_operand_bytes(ctx->npad), sbo::x3_operand_bytes(I0 * sbo::kBM)));
+        SBO_HIP(ctx->kc3.reserve(sbo::x3_coord_bytes(ctx->npad)));
+        SBO_HIP(sbo::launch_pack_x3(ctx->stream, ctx->aug.as<float>(), ctx->kcoord.as<float>(), ctx->npad, I0, layout,
+                                    ctx->ax3.as<char>(), ctx->kc3.as<float>()));
+        ctx->x3_I0 = INT64_MAX;
+        ctx->x3_layout = layout;
+    }
+    return SBO_OK;
+}
+
 sbo_status run_tick(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, double beta, double f_min,
                     int score_kind, int64_t index_offset, float *mu, float *sd, double *lo, double *hi,
                     uint8_t *safe, sbo_key *key_dev, float *cost = nullptr, int sweep = kSweepCtx,
@@ -2034,18 +2053,7 @@ sbo_status run_tick(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, d
         // split-operand sweep: derive the bf16 planes of any repacked row
         // block, and give the kernel whole 128-query blocks to read
         const int64_t nIc = ctx->npad / sbo::kBM;
-        const int layout = sbo::x3_layout(ctx->kernel_variant);
-        if (layout != ctx->x3_layout) ctx->x3_I0 = 0;  // another layout: derive all of it
-        if (ctx->x3_I0 < nIc) {
-            const int64_t I0 = std::max<int64_t>(ctx->x3_I0, 0);
-            SBO_HIP(grow_keep(ctx, ctx->ax3, sbo::x3_operand_bytes(ctx->npad),
-                              sbo::x3_operand_bytes(I0 * sbo::kBM)));
-            SBO_HIP(ctx->kc3.reserve(sbo::x3_coord_bytes(ctx->npad)));
-            SBO_HIP(sbo::launch_pack_x3(ctx->stream, ctx->aug.as<float>(), ctx->kcoord.as<float>(), ctx->npad, I0,
-                                        layout, ctx->ax3.as<char>(), ctx->kc3.as<float>()));
-            ctx->x3_I0 = INT64_MAX;
-            ctx->x3_layout = layout;
-        }
+        if (sbo_status st = derive_x3(ctx)) return st;
         if (!perm) {
             const int64_t mp = sbo::round_up(m, sbo::kBN);
             SBO_HIP(ctx->qpad.reserve(sizeof(float) * 2 * (size_t)mp));
@@ -2654,6 +2662,22 @@ SBO_API sbo_status sbo_debug_x3_stamps(sbo_ctx *ctx, double *cycles, int n) {
     SBO_HIP(hipSetDevice(ctx->device));
     SBO_HIP(hipStreamSynchronize(ctx->stream));
     SBO_HIP(sbo::read_x3_stamps(cycles, n));
+    return SBO_OK;
+}
+
+SBO_API sbo_status sbo_debug_x3_operand(sbo_ctx *ctx, void *host_buf, int64_t cap, int64_t *bytes) {
+    if (!ctx || !bytes || cap < 0) return SBO_E_INVAL;
+    if (!ctx->fitted || ctx->kernel_variant < 2) return SBO_E_INVAL;
+    SBO_HIP(hipSetDevice(ctx->device));
+    // (the eager derivation of a fit or an append runs on aux_stream)
+    SBO_HIP(hipStreamSynchronize(ctx->aux_stream));
+    if (sbo_status st = derive_x3(ctx)) return st;
+    const int64_t need = (int64_t)sbo::x3_operand_bytes(ctx->npad);
+    *bytes = need;
+    if (!host_buf) return SBO_OK;
+    if (cap < need) return SBO_E_INVAL;
+    SBO_HIP(hipMemcpyAsync(host_buf, ctx->ax3.as<char>(), (size_t)need, hipMemcpyDeviceToHost, ctx->stream));
+    SBO_HIP(hipStreamSynchronize(ctx->stream));
     return SBO_OK;
 }
 

@@ -325,36 +325,38 @@ hipError_t launch_plan_cost(hipStream_t s, int64_t npad, int64_t m, int P, const
 void plan_views(int64_t npad, int64_t m, int P, const void *work, const int4 **desc, const unsigned short **tl,
                 const int **seg, const int4 **rec = nullptr);
 // Split-operand (bf16 x3) predictive sweep, predict_x3.hip: the packed
-// operand split into three bf16 planes per half-tile and the per-k-tile
-// coordinates in natural order, for row blocks >= I0 (coordinates: all).
+// operand split into three bf16 planes per row half of a tile (48 KiB stages,
+// predict_x3_rowhalf.hpp) and the per-k-tile coordinates in natural order,
+// for row blocks >= I0 (coordinates: all).
 size_t x3_operand_bytes(int64_t npad);
 size_t x3_coord_bytes(int64_t npad);
 // (ax3 null: the coordinates only; kc3 null: the planes only)
-hipError_t launch_pack_x3(hipStream_t s, const float *aug, const float *kcoord, int64_t npad, int64_t I0, int wide,
+hipError_t launch_pack_x3(hipStream_t s, const float *aug, const float *kcoord, int64_t npad, int64_t I0, int layout,
                           char *ax3, float *kc3);
-// the split operand's layout a kernel variant reads (1: the wide 32x32x16 shape)
 // tile-list entry of the plan: k-tile index | precision level code << kLevelShift
 constexpr int kLevelShift = 14;
 // Step record of the split sweep (plan_rec_kernel), one int4 per kept tile in
 // sweep order: x = the packed tile's offset in the split operand (KiB, two
-// half-tiles of 48), y = its k-tile's coordinate offset in kc3 (floats),
+// stages of 48: the tile's halves), y = its k-tile's coordinate offset in kc3 (floats),
 // z = query block, w = row block | level code << 16 | first / last tile of
 // its item (kRecFirst, kRecLast).
 constexpr int kRecFirst = 1 << 20, kRecLast = 1 << 21;
 // the split sweeps that honour the plan's precision levels
-inline bool x3_levels(int variant) { return variant == 3 || variant == 23 || variant == 24 || variant == 30 || variant == 32 || variant == 33 || variant == 39 || variant == 41 || variant == 42 || variant == 43 || variant == 46 || variant == 47 || variant == 48 || variant == 49 || variant == 51 || variant == 52 || variant == 53 || variant == 54 || variant == 55 || variant == 56 || variant == 57 || (variant >= 58 && variant <= 61); }
+inline bool x3_levels(int variant) { return variant == 3 || variant == 23 || variant == 24 || variant == 30 || variant == 32 || variant == 33 || variant == 39 || variant == 41 || variant == 42 || variant == 43 || variant == 46 || variant == 47 || variant == 48 || variant == 49 || variant == 51 || variant == 52 || variant == 53 || variant == 54 || variant == 55 || variant == 56 || variant == 57 || (variant >= 58 && variant <= 62); }
 // Sweeps the product library accepts (all compute the full result; 3 is the
 // default).  The timing diagnostics (parts of the work left out, forced
 // precision levels, phase stamps) exist only in the diagnostic build
 // (-DSBO_DIAG, lib/libsbo_diag.so, selected by SBO_LIB for tools/).
 inline bool variant_allowed(int v) {
 #ifdef SBO_DIAG
-    return v >= 0 && v <= 61;
+    return v >= 0 && v <= 62;
 #else
     return v == 0 || v == 1 || v == 3 || v == 22;
 #endif
 }
-inline int x3_layout(int variant) { return (variant == 13 || variant == 14) ? 1 : 0; }
+// the split operand's layout a kernel variant reads (2: row-half stages, the product's; 0: k-half stages and
+// 1: the wide 32x32x16 shape, the diagnostic build's other variants)
+inline int x3_layout(int variant) { return (variant == 13 || variant == 14) ? 1 : (variant == 3 || variant == 22) ? 2 : 0; }
 // The sweep over the plan with the split operand; qx/qy must be readable in
 // whole 128-query blocks (padded to round_up(m, kBN)).  variant: 3 (the
 // default, honouring the plan's precision levels) or 22 (every kept tile at
