@@ -637,6 +637,22 @@ SBO_API sbo_status sbo_debug_x3_stamps(sbo_ctx *ctx, double *cycles, int n);
  * the operand's size; host_buf may be null to ask for it alone. */
 SBO_API sbo_status sbo_debug_x3_operand(sbo_ctx *ctx, void *host_buf, int64_t cap, int64_t *bytes);
 
+/* Test accessor: the plan a tick of these m queries (host pointers) would
+ * sweep under the context's options -- the plan sbo_query_cost builds; no
+ * sweep runs -- as int32 in host_buf: [0] nI row blocks, [1] nQ query blocks
+ * of 128 sweep positions (the queries in the tick's sweep order, padded grid
+ * patches included), [2] the kept tiles, [3] the non-empty items; then per
+ * item, at 4 + 2 (I nQ + qb): the budget threshold + 1 (thr) and the kept-tile
+ * count; then per kept tile, in the order the sweep walks them, four ints: row
+ * block I, query block qb, k-tile t, precision level (0 six, 1 three, 2 one
+ * product(s)).  *n_out is the number of ints; host_buf may be null to ask for
+ * it alone.  Diagnostic build only: with SBO_PLAN_REF=1 in the environment the
+ * plan comes from the reference builder (every (row block, k-tile) pair's
+ * bounds evaluated in every pass, no column prefilter), and ticks write and
+ * read the partials of empty items. */
+SBO_API sbo_status sbo_debug_plan(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, int32_t *host_buf,
+                                  int64_t cap, int64_t *n_out);
+
 /* Test accessors: the int8-sliced GEMM under the fit (csrc/ozgemm.hip), run
  * alone on the context's stream so that tests/test_gpu_ozgemm.py can hold the
  * product's object code bit for bit to an integer model (tests/oz_model.py).

@@ -34,7 +34,7 @@ EXPORTS = (
     "sbo_get_bounds", "sbo_get_jitter", "sbo_get_tile_bounds", "sbo_state_bytes", "sbo_export_state", "sbo_import_state", "sbo_query_cost",
     "sbo_polygon_correct", "sbo_polydist", "sbo_point_within", "sbo_project_subgoal", "sbo_get_precision",
     "sbo_kd_order", "sbo_get_probe", "sbo_keys_reduce", "sbo_get_inverse_check", "sbo_trim", "sbo_warmup",
-    "sbo_debug_gz_gemm", "sbo_debug_gz_gemm_packed", "sbo_debug_x3_operand",
+    "sbo_debug_gz_gemm", "sbo_debug_gz_gemm_packed", "sbo_debug_x3_operand", "sbo_debug_plan",
 )
 # the sliced GEMM's flags (include/sbo.h, sbo_debug_gz_gemm)
 SBO_GZ_TRI_A = 1
@@ -225,6 +225,8 @@ def lib():
     L.sbo_debug_x3_stamps.restype = st
     L.sbo_debug_x3_operand.argtypes = [vp, vp, i64, ctypes.POINTER(i64)]
     L.sbo_debug_x3_operand.restype = st
+    L.sbo_debug_plan.argtypes = [vp, vp, vp, i64, vp, i64, ctypes.POINTER(i64)]
+    L.sbo_debug_plan.restype = st
     L.sbo_debug_gz_gemm.argtypes = [vp, i32, i32, vp, i64, i64, vp, i64, i64, i64, i64, i64, dbl, vp, i64, i64, u32]
     L.sbo_debug_gz_gemm.restype = st
     L.sbo_debug_gz_gemm_packed.argtypes = [vp, i32, vp, i64, i64, i64, i64, i64, i64, i64, dbl, vp, i64, i64, u32]

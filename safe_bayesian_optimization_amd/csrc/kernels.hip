@@ -1747,6 +1747,21 @@ constexpr unsigned kLevelWeight0 = 64, kLevelWeight1 = 42, kLevelWeight2 = 33;
 constexpr unsigned kMeanWeight0 = 80, kMeanWeight1 = 45, kMeanWeight2 = 33;
 __device__ unsigned g_mean_w[3] = {kMeanWeight0, kMeanWeight1, kMeanWeight2};
 __device__ unsigned g_rb_slope = 0;
+#ifdef SBO_DIAG
+// SBO_PLAN_STATS: [0], [1] near / all (query block, k-tile) pairs of the column
+// prefilter; [2..8] plan_count's wall clock (100 MHz ticks) summed over
+// workgroups: setup, near list, water-filling totals, its serial part,
+// thresholds, levels, the rest of the item loop
+__device__ unsigned long long g_plan_near[9] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+#define SBO_PLAN_LAP(acc)                                \
+    if (threadIdx.x == 0) {                              \
+        const unsigned long long now_ = wall_clock64(); \
+        (acc) += now_ - tprev_;                          \
+        tprev_ = now_;                                   \
+    }
+#else
+#define SBO_PLAN_LAP(acc)
+#endif
 constexpr int kSteps = kBK / 4;          // 16x16x4 k steps per tile
 constexpr int kRowBlocks = kBM / 16;     // 16-row MFMA blocks per wave
 
@@ -1936,9 +1951,26 @@ struct PlanRule {
     // its increments go to bin 0 with weight <= 2 each (exp2(l + 32) < 2^-8
     // rounds up to at most 1, plus 1), so the plan books 6 for it without
     // evaluating the bounds -- most candidate tiles of a row block.
-    __device__ __forceinline__ bool far_tile(int I, int t, float dd) const {
+    __device__ __forceinline__ bool far_lg(float l, float dd) const {
         const float kf = fmaxf(0.0f, fmaxf(key.x + kLg3, key.y + kLg1));
-        return lgn[2 * (tile_start(I) + t)].x + cexp * dd * 0.999f - lg_tau + 0.01f + kf < -(float)kBudgetFloor;
+        return l + cexp * dd * 0.999f - lg_tau + 0.01f + kf < -(float)kBudgetFloor;
+    }
+    __device__ __forceinline__ bool far_tile(int I, int t, float dd) const {
+        return far_lg(lgn[2 * (tile_start(I) + t)].x, dd);
+    }
+
+    // Column prefilter (near != null).  far_lg is non-decreasing in l (every
+    // rounded step of it is; the build forbids contraction), so a k-tile that
+    // is far by colmax[t] = max over row blocks of lgn[..].x is far for every
+    // row block: the query block tests each k-tile once, and the passes below
+    // walk only the ascending list of the others (nearl; bitmap nearm, its
+    // prefix counts per 64 tiles nearp) and book the rest as far_tile would.
+    const unsigned long long *nearm = nullptr;
+    const int *nearp = nullptr;
+    const unsigned short *nearl = nullptr;
+    __device__ __forceinline__ int near_count(int T) const {  // near k-tiles t < T
+        const int c = T >> 6, r = T & 63;
+        return nearp[c] + (r ? __popcll(nearm[c] & ((1ull << r) - 1ull)) : 0);
     }
 
     __device__ __forceinline__ void incs(int I, int t, int (&bi)[3], unsigned long long (&w)[3]) const {
@@ -1959,11 +1991,13 @@ struct PlanRule {
     // everything).  The same increments and fixed-point weights as threshold.
     __device__ unsigned long long total_weight(int I, int lane, bool &over) const {
         const int T = kTilesPerRowBlockStep * (I + 1);
-        unsigned long long wsum = 0;
+        // (prefilter: the far k-tiles booked at once, the loop over the near list)
+        const int n = nearl ? near_count(T) : T;
+        unsigned long long wsum = lane == 0 ? 6ull * (unsigned long long)(T - n) : 0ull;
         int ov = 0;
-        for (int t0 = 0; t0 < T; t0 += 64) {
-            const int t = t0 + lane;
-            if (t < T) {
+        for (int t0 = 0; t0 < n; t0 += 64) {
+            if (t0 + lane < n) {
+                const int t = nearl ? (int)nearl[t0 + lane] : t0 + lane;
                 if (far_tile(I, t, d2(t))) {
                     wsum += 6ull;
                 } else {
@@ -2001,8 +2035,11 @@ struct PlanRule {
         const int T = kTilesPerRowBlockStep * (I + 1);
         for (int i = lane; i < kBudgetBins; i += 64) bins[i] = 0ull;
         __builtin_amdgcn_wave_barrier();
-        unsigned long long nfar = 0;
-        for (int t = lane; t < T; t += 64) {
+        // (prefilter: a far k-tile's bc entry is not written; level_far does not read it)
+        const int n = nearl ? near_count(T) : T;
+        unsigned long long nfar = lane == 0 ? (unsigned long long)(T - n) : 0ull;
+        for (int i = lane; i < n; i += 64) {
+            const int t = nearl ? (int)nearl[i] : i;
             if (far_tile(I, t, d2(t))) {
                 ++nfar;
                 if (bc && t < kPlanBinCache) bc[t] = 0u;  // all three increments in bin 0
@@ -2065,20 +2102,31 @@ struct PlanRule {
                 incs(I, t, bi, w);
                 spent = (bi[0] <= drop_max) + (bi[1] <= drop_max) + (bi[2] <= drop_max);
             }
-            code = spent == 3 ? -1 : (levels == 1 ? spent : (levels > 1 ? levels - 2 : 0));
+            code = spent_code(spent);
         } else {
             code = (skip_d2 <= 0.0f || dd <= skip_d2) ? 0 : -1;  // skip_d2 <= 0: dense
         }
-        // the mean's own cutoff (last row block): keep at the cheapest level
-        // (its V error is below the drop bound already spent)
+        return mean_keep(I, dd, code);
+    }
+    __device__ __forceinline__ int spent_code(int spent) const {
+        return spent == 3 ? -1 : (levels == 1 ? spent : (levels > 1 ? levels - 2 : 0));
+    }
+    // the mean's own cutoff (last row block): keep at the cheapest level
+    // (its V error is below the drop bound already spent)
+    __device__ __forceinline__ int mean_keep(int I, float dd, int code) const {
         if (code < 0 && I == nI - 1 && dd <= skip_d2_mean) code = lgn && levels ? 2 : 0;
         return code;
+    }
+    // level() of a k-tile the column prefilter found far (lgn != null)
+    __device__ __forceinline__ int level_far(int I, int t, int drop_max) const {
+        return mean_keep(I, d2(t), spent_code(drop_max >= 0 ? 3 : 0));
     }
 };
 
 // The plan's reference budget 2^lg_ref = tau2, the whole query block's
 // |dV|_2 budget, from lg_tau = log2(tau2 / sqrt(nI)) (the even share).
 __device__ __forceinline__ float plan_ref(float lg_tau, int nI) { return lg_tau + 0.5f * __log2f((float)nI) - 1e-4f; }
+constexpr int kDropAll = 64 * ((kBudgetBins + 63) / 64) - 1;  // threshold() under an unlimited budget
 constexpr int kPlanMaxI = 512;   // water-filling of the budget for nI <= this (N <= 131072), else even shares
 
 // Query box of block qb (threads 0..127 hold its queries, 128..255 repeat
@@ -2090,11 +2138,19 @@ constexpr int kPlanMaxI = 512;   // water-filling of the budget for nI <= this (
 // kernel's f32 rounding); if even that underflows, the box bound 8 K*max.
 __device__ __forceinline__ float tile_knorm(const float *__restrict__ kc, const QBox &b, float cexp, float d2box) {
     float sum = 0.0f;
-    for (int i = 0; i < kBK; ++i) {
-        const float px = kc[i], py = kc[kBK + i];
-        const float dx = fmaxf(0.0f, fmaxf(b.x0 - px, px - b.x1));
-        const float dy = fmaxf(0.0f, fmaxf(b.y0 - py, py - b.y1));
-        sum += __builtin_amdgcn_exp2f(fmaf(2.0f * cexp, fmaf(dy, dy, dx * dx) * 0.999f, 120.0f));
+    // (four points per load, their loads in flight together; summed in point order)
+    const float4 *kx = reinterpret_cast<const float4 *>(kc), *ky = reinterpret_cast<const float4 *>(kc + kBK);
+#pragma unroll 4
+    for (int i = 0; i < kBK / 4; ++i) {
+        const float4 vx = kx[i], vy = ky[i];
+        const float pxs[4] = {vx.x, vx.y, vx.z, vx.w}, pys[4] = {vy.x, vy.y, vy.z, vy.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float px = pxs[j], py = pys[j];
+            const float dx = fmaxf(0.0f, fmaxf(b.x0 - px, px - b.x1));
+            const float dy = fmaxf(0.0f, fmaxf(b.y0 - py, py - b.y1));
+            sum += __builtin_amdgcn_exp2f(fmaf(2.0f * cexp, fmaf(dy, dy, dx * dx) * 0.999f, 120.0f));
+        }
     }
     return sum > 0.0f ? 0.5f * (__log2f(sum * 1.002f) - 120.0f) + 0.001f : 3.0f + cexp * d2box * 0.999f;
 }
@@ -2166,6 +2222,12 @@ __host__ __device__ __forceinline__ int plan_chunks(int nI) { return (kTilesPerR
 // the budget threshold and the kept-tile count of every item.  key packs
 // (count, non-empty) for the scan; empty items get their (exactly zero)
 // outputs here, so the sweep never visits them.
+// With colmax (the product's path; null: the reference builder the
+// diagnostic build keeps, SBO_PLAN_REF) the kernel is organised by what it
+// costs -- wave-level steps, not pairs: the near list of the column
+// prefilter, the water-filling totals over the flat list of near pairs, and
+// no wave for the cheap row blocks.  Every shortcut
+// is an integer identity or a monotone bound: the plan is the reference's.
 __global__ __launch_bounds__(kPlanThreads) void plan_count_kernel(
     const float4 *__restrict__ kbox, const float *__restrict__ kcoord, const float4 *__restrict__ lgn, int levels,
     float2 lvl_key, int nI,
@@ -2173,22 +2235,78 @@ __global__ __launch_bounds__(kPlanThreads) void plan_count_kernel(
     const float *__restrict__ qx, const float *__restrict__ qy, int64_t m, float cexp, float skip_d2,
     float skip_d2_mean, float lg_tau, float m0, int64_t ldp, float *__restrict__ part, float *__restrict__ mean,
     unsigned long long *__restrict__ key, unsigned char *__restrict__ thr, unsigned long long *__restrict__ wkey,
-    unsigned long long *__restrict__ bits, int wide, int blk) {
+    unsigned long long *__restrict__ bits, int wide, int blk, const float *__restrict__ colmax, int zero_empty,
+    unsigned long long *__restrict__ nemask) {
     // dynamic LDS: the increment-bin cache [kPlanWaves][kPlanBinCache], then
-    // the distance and |k|_2 caches of min(nkt, kPlanD2) tiles each
+    // the distance and |k|_2 caches of min(nkt, kPlanD2) tiles each, then the
+    // near list (u16) of as many
     extern __shared__ unsigned plan_dyn[];
     __shared__ float red[4 * kPlanWaves];
+    __shared__ unsigned long long nearm[kPlanD2 / 64];
+    __shared__ int nearp[kPlanD2 / 64 + 1];
+    __shared__ unsigned long long nem[(1 << kLevelShift) / kTilesPerRowBlockStep / 64];  // bit I: item (I, qb) keeps a tile
     __shared__ unsigned long long bins[kPlanWaves][kBudgetBins];
     __shared__ unsigned long long wtot[kPlanMaxI];
     __shared__ unsigned long long budget_exp;
+    __shared__ int cumn[kPlanMaxI + 1];
+    __shared__ unsigned short todo[kPlanMaxI];
+    __shared__ int ntodo;
+    __shared__ unsigned ovm[kPlanMaxI / 32];
     const int64_t qb = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nkt = kTilesPerRowBlockStep * nI;
+    const int nem_words = (nI + 63) >> 6;
+    for (int i = threadIdx.x; i < nem_words; i += kPlanThreads) nem[i] = 0ull;   // (plan_setup's barriers order it)
     unsigned *bc = plan_dyn + wave * kPlanBinCache;
     float *d2s = reinterpret_cast<float *>(plan_dyn + kPlanWaves * kPlanBinCache);
     float *kns = d2s + min(nkt, kPlanD2);
     PlanRule R{kbox, lgn, cexp, skip_d2, skip_d2_mean, plan_ref(lg_tau, nI), nI, {}, d2s, kns, levels, lvl_key};
+#ifdef SBO_DIAG
+    unsigned long long tprev_ = wall_clock64(), lap[7] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+#endif
     R.box = plan_setup(qx, qy, m, qb, kbox, lgn ? kcoord : nullptr, cexp, nkt, d2s, kns, red);
+    SBO_PLAN_LAP(lap[0])
+    // The column prefilter's near list (PlanRule::nearl).  Beyond the distance
+    // cache (N > 131072) every pair is tested on its own, as without colmax.
+    const bool pre = lgn && colmax && nkt <= kPlanD2;
+    if (pre) {
+        unsigned short *nearl = reinterpret_cast<unsigned short *>(kns + nkt);
+        const int nch = (nkt + 63) >> 6;
+        for (int c = wave; c < nch; c += kPlanWaves) {
+            const int t = c * 64 + lane;
+            const unsigned long long b = __ballot(t < nkt && !R.far_lg(colmax[t < nkt ? t : 0], d2s[t < nkt ? t : 0]));
+            if (lane == 0) nearm[c] = b;
+        }
+        __syncthreads();
+        if (wave == 0) {  // nch <= 32: exclusive prefix of the chunks' near counts
+            const int cnt = lane < nch ? __popcll(nearm[lane]) : 0;
+            int incl = cnt;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int u = __shfl_up(incl, o);
+                if (lane >= o) incl += u;
+            }
+            if (lane < nch) nearp[lane + 1] = incl;
+            if (lane == 0) nearp[0] = 0;
+        }
+        __syncthreads();
+        for (int c = wave; c < nch; c += kPlanWaves) {
+            const unsigned long long b = nearm[c];
+            if ((b >> lane) & 1ull)
+                nearl[nearp[c] + __popcll(b & ((1ull << lane) - 1ull))] = (unsigned short)(c * 64 + lane);
+        }
+        __syncthreads();
+        R.nearm = nearm;
+        R.nearp = nearp;
+        R.nearl = nearl;
+#ifdef SBO_DIAG
+        if (threadIdx.x == 0) {  // SBO_PLAN_STATS: near (query block, k-tile) pairs over all
+            atomicAdd(&g_plan_near[0], (unsigned long long)nearp[nch]);
+            atomicAdd(&g_plan_near[1], (unsigned long long)nkt);
+        }
+#endif
+    }
+    SBO_PLAN_LAP(lap[1])
     // The error budget of the query block, |dV(q)|_2^2 = sum_I |dV_I(q)|_2^2
     // <= tau2^2 = 2^(2 lg_ref) for every query q of the block, shared over
     // its row blocks by water-filling instead of evenly (tau2 / sqrt(nI)
@@ -2197,13 +2315,77 @@ __global__ __launch_bounds__(kPlanThreads) void plan_count_kernel(
     // split evenly over the others (iterated: a larger share can make more
     // row blocks cheap).  Fixed point, 2^32 = 2^lg_ref.
     const bool fill = lgn && nI <= kPlanMaxI;
-    if (fill) {
+    if (fill && pre) {
+        // The totals over the flat list of (row block, near k-tile) pairs,
+        // 256 at a time whatever row block they belong to (a row block has
+        // fewer near k-tiles than a wave has lanes): pair p is near k-tile
+        // p - cumn[I] of the row block I with cumn[I] <= p < cumn[I + 1].
+        // Integer sums: the same totals as total_weight's.
+        for (int I = threadIdx.x; I < nI; I += kPlanThreads) {
+            const int T = kTilesPerRowBlockStep * (I + 1), n = R.near_count(T);
+            cumn[I + 1] = n;
+            wtot[I] = 6ull * (unsigned long long)(T - n);
+        }
+        if (threadIdx.x < kPlanMaxI / 32) ovm[threadIdx.x] = 0u;
+        if (threadIdx.x == 0) cumn[0] = 0;
+        __syncthreads();
+        if (wave == 0) {  // cumn[1..nI]: inclusive scan, (nI + 63) / 64 entries per lane
+            const int per = (nI + 63) >> 6, base = 1 + lane * per;
+            int sum = 0;
+            for (int j = 0; j < per; ++j) sum += base + j <= nI ? cumn[base + j] : 0;
+            int incl = sum;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int u = __shfl_up(incl, o);
+                if (lane >= o) incl += u;
+            }
+            int run = incl - sum;
+            for (int j = 0; j < per; ++j)
+                if (base + j <= nI) {
+                    run += cumn[base + j];
+                    cumn[base + j] = run;
+                }
+        }
+        __syncthreads();
+        const int ptot = cumn[nI];
+        for (int p = threadIdx.x; p < ptot; p += kPlanThreads) {
+            int lo = 0, hi = nI - 1;  // the last I with cumn[I] <= p
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (cumn[mid] <= p) lo = mid;
+                else hi = mid - 1;
+            }
+            const int I = lo, t = (int)R.nearl[p - cumn[I]];
+            if (R.far_tile(I, t, R.d2(t))) {
+                atomicAdd(&wtot[I], 6ull);
+            } else {
+                int bi[3];
+                unsigned long long w[3], ws = 0ull;
+                R.incs(I, t, bi, w);
+                bool ov = false;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    if (bi[j] < kBudgetBins - 1) ws += w[j];
+                    else ov = true;
+                }
+                atomicAdd(&wtot[I], ws);
+                if (ov) atomicOr(&ovm[I >> 5], 1u << (I & 31));
+            }
+        }
+        __syncthreads();
+        for (int I = threadIdx.x; I < nI; I += kPlanThreads)
+            if ((ovm[I >> 5] >> (I & 31)) & 1u) wtot[I] = ~0ull;
+        __syncthreads();
+    } else if (fill) {
         for (int I = wave; I < nI; I += kPlanWaves) {
             bool over;
             const unsigned long long w = R.total_weight(I, lane, over);
             if (lane == 0) wtot[I] = over ? ~0ull : w;
         }
         __syncthreads();
+    }
+    if (fill) {
+        SBO_PLAN_LAP(lap[2])
         if (threadIdx.x == 0) {
             const double one = 4294967296.0;
             double share = 1.0 / sqrt((double)nI);   // the even split, in units of 2^lg_ref
@@ -2224,13 +2406,49 @@ __global__ __launch_bounds__(kPlanThreads) void plan_count_kernel(
             budget_exp = (unsigned long long)floor(share * one);
         }
         __syncthreads();
+        SBO_PLAN_LAP(lap[3])
     }
-    for (int I = wave; I < nI; I += kPlanWaves) {
+    // Under the prefilter the cheap row blocks but the mean's need no wave:
+    // their items are empty with the threshold of an unlimited budget
+    // (kDropAll, see below), written here by one thread each -- their code
+    // bitmaps are not (plan_write reads a non-empty item's only) -- and the
+    // waves share the list of the others.  (zero_empty: the item loop also
+    // writes the empty items' partials.)
+    const bool flat = pre && fill && !zero_empty;
+    if (flat) {
+        if (wave == 0) {
+            int base = 0;
+            for (int I0 = 0; I0 < nI; I0 += 64) {
+                const int I = I0 + lane;
+                const bool work = I < nI && (I == nI - 1 || wtot[I] > budget_exp);
+                const unsigned long long b = __ballot(work);
+                if (work) todo[base + __popcll(b & ((1ull << lane) - 1ull))] = (unsigned short)I;
+                base += __popcll(b);
+            }
+            if (lane == 0) ntodo = base;
+        }
+        for (int I = threadIdx.x; I < nI - 1; I += kPlanThreads)
+            if (wtot[I] <= budget_exp) {
+                const int64_t item = plan_item(I, nI, nQ, qb, blk);
+                key[item] = 0ull;
+                thr[item] = (unsigned char)(kDropAll + 1);
+                wkey[item] = 0ull;
+            }
+        __syncthreads();
+    }
+    const int nwork = flat ? ntodo : nI;
+    for (int idx = wave; idx < nwork; idx += kPlanWaves) {
+        const int I = flat ? (int)todo[idx] : idx;
         const int T = kTilesPerRowBlockStep * (I + 1);
         // a cheap row block (everything within the share) spends its own total
         const unsigned long long bud = !fill ? (unsigned long long)floor(4294967296.0 / sqrt((double)nI))
                                        : (wtot[I] <= budget_exp ? ~0ull : budget_exp);
-        const int drop_max = R.threshold(I, bins[wave], lane, bud, bc);
+        // A cheap row block under the prefilter: threshold() with the budget
+        // ~0 counts every slot of its scan, whatever the bins hold, and every
+        // tile is dropped (but for the mean's cutoff) -- nothing to evaluate.
+        const bool cheap = pre && bud == ~0ull;
+        const int drop_max = cheap ? kDropAll : R.threshold(I, bins[wave], lane, bud, bc);
+        SBO_PLAN_LAP(lap[4])
         const int64_t item = plan_item(I, nI, nQ, qb, blk);
         // the item's codes, 64 tiles per chunk: kept / level 1 / level 2 masks (read by plan_write)
         unsigned long long *ib = bits + item * (int64_t)plan_chunks(nI) * 3;
@@ -2239,7 +2457,24 @@ __global__ __launch_bounds__(kPlanThreads) void plan_count_kernel(
 #pragma unroll 1
         for (int t0 = 0; t0 < T; t0 += 64) {
             const int t = t0 + lane;
-            const int code = t < T ? R.level(I, t, drop_max, bc) : -1;
+            int code;
+            if (cheap) {
+                if (I != nI - 1) {
+                    if (lane < 3) ib[(t0 >> 6) * 3 + lane] = 0ull;
+                    continue;
+                }
+                code = t < T ? R.mean_keep(I, R.d2(t), -1) : -1;
+            } else if (pre) {
+                const unsigned long long nm = nearm[t0 >> 6];
+                // no near k-tile in the chunk, and a far one is dropped: all dropped
+                if (nm == 0ull && drop_max >= 0 && I != nI - 1) {
+                    if (lane < 3) ib[(t0 >> 6) * 3 + lane] = 0ull;
+                    continue;
+                }
+                code = t < T ? (((nm >> lane) & 1ull) ? R.level(I, t, drop_max, bc) : R.level_far(I, t, drop_max)) : -1;
+            } else {
+                code = t < T ? R.level(I, t, drop_max, bc) : -1;
+            }
             const unsigned long long b0 = __ballot(code == 0), b1 = __ballot(code == 1), b2 = __ballot(code == 2);
             if (lane < 3) ib[(t0 >> 6) * 3 + lane] = lane == 0 ? (b0 | b1 | b2) : (lane == 1 ? b1 : b2);
             const int n0 = __popcll(b0), n1 = __popcll(b1), n2 = __popcll(b2);
@@ -2247,6 +2482,7 @@ __global__ __launch_bounds__(kPlanThreads) void plan_count_kernel(
             wsum += I == nI - 1 ? g_mean_w[0] * n0 + g_mean_w[1] * n1 + g_mean_w[2] * n2
                                 : kLevelWeight0 * n0 + kLevelWeight1 * n1 + kLevelWeight2 * n2;
         }
+        SBO_PLAN_LAP(lap[5])
         if (g_rb_slope)
             wsum = (unsigned)((unsigned long long)wsum * (100u * (unsigned)nI + g_rb_slope * (unsigned)I) /
                               (100u * (unsigned)nI));
@@ -2254,22 +2490,31 @@ __global__ __launch_bounds__(kPlanThreads) void plan_count_kernel(
             key[item] = (unsigned long long)cnt | ((cnt > 0 ? 1ull : 0ull) << kPlanKeyShift);
             thr[item] = (unsigned char)(drop_max + 1);
             wkey[item] = wsum;
+            if (cnt > 0) atomicOr(&nem[I >> 6], 1ull << (I & 63));
         }
         if (cnt == 0)
             for (int j = lane; j < kBN; j += 64) {
                 const int64_t q = qb * kBN + j;
                 if (q < m) {
                     // (wide: the precise sweep's f64 partials and mean)
+                    // (zero_empty == 0: the acquisition skips an empty item's partial by nemask)
                     if (wide) {
-                        reinterpret_cast<double *>(part)[(int64_t)I * ldp + q] = 0.0;
+                        if (zero_empty) reinterpret_cast<double *>(part)[(int64_t)I * ldp + q] = 0.0;
                         if (I == nI - 1) reinterpret_cast<double *>(mean)[q] = (double)m0;
                     } else {
-                        part[(int64_t)I * ldp + q] = 0.0f;
+                        if (zero_empty) part[(int64_t)I * ldp + q] = 0.0f;
                         if (I == nI - 1) mean[q] = m0;
                     }
                 }
             }
+        SBO_PLAN_LAP(lap[6])
     }
+#ifdef SBO_DIAG
+    if (threadIdx.x == 0)
+        for (int i = 0; i < 7; ++i) atomicAdd(&g_plan_near[2 + i], lap[i]);
+#endif
+    __syncthreads();
+    for (int i = threadIdx.x; i < nem_words; i += kPlanThreads) nemask[qb * nem_words + i] = nem[i];
 }
 
 // Pass 2 (after the inclusive scan of key): the kept tile indices of every
@@ -2409,7 +2654,11 @@ __global__ void plan_perm_kernel(const unsigned long long *__restrict__ scan, in
                                  int *__restrict__ pos_of, unsigned long long *__restrict__ cnt2) {
     const int64_t nne = (int64_t)(scan[n_items - 1] >> kPlanKeyShift);
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= nne) return;
+    if (k >= nne) {
+        // (the permutation maps [0, nne) onto itself: the positions past it count 0 for the scan)
+        if (k < n_items) cnt2[k] = 0ull;
+        return;
+    }
     const int64_t p = xcd_position(k, xseg, G);
     pos_of[k] = (int)p;
     cnt2[p] = (unsigned long long)(desc[k].w & 0xffff);
@@ -2756,24 +3005,30 @@ __global__ __launch_bounds__(kAcqThreads) void acquire_kernel(
     double sf2, double beta, double f_min, int score_kind, int64_t index_offset,
     const int32_t *__restrict__ perm, float *__restrict__ mu_out, float *__restrict__ sd_out,
     double *__restrict__ lo_out, double *__restrict__ hi_out, uint8_t *__restrict__ safe_out,
-    sbo_key *__restrict__ keys) {
+    sbo_key *__restrict__ keys, const unsigned long long *__restrict__ nemask) {
     const int64_t i = (int64_t)blockIdx.x * kAcqThreads + threadIdx.x;
     double bs = 0.0;
     int64_t bi = -1;
     // (perm -1: a padded grid-patch position, no output)
     if (i < m && (!perm || perm[i] >= 0)) {
         // the row blocks' partials, summed in f64 in ascending I; read eight
-        // at a time so their loads are in flight together (same sum order)
+        // at a time so their loads are in flight together (same sum order).
+        // nemask (the plan's non-empty items, bit I of the query block's
+        // words; may be null): an empty item's partial is not read -- nobody
+        // wrote it, and it would add +0.0 to a sum that is never -0.0
+        const unsigned long long *ne = nemask ? nemask + (i / kBN) * (int64_t)((nI + 63) >> 6) : nullptr;
         double s = 0.0;
         int I = 0;
         for (; I + 8 <= nI; I += 8) {
+            const unsigned b = ne ? (unsigned)(ne[I >> 6] >> (I & 63)) & 0xffu : 0xffu;   // (I % 8 == 0: one word)
             PT v[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = part[(int64_t)(I + u) * ldp + i];
+            for (int u = 0; u < 8; ++u) v[u] = ((b >> u) & 1u) ? part[(int64_t)(I + u) * ldp + i] : (PT)0;
 #pragma unroll
             for (int u = 0; u < 8; ++u) s += (double)v[u];
         }
-        for (; I < nI; ++I) s += (double)part[(int64_t)I * ldp + i];
+        for (; I < nI; ++I)
+            if (!ne || ((ne[I >> 6] >> (I & 63)) & 1ull)) s += (double)part[(int64_t)I * ldp + i];
         double vd = sf2 - s;
         float var = vd > 0.0 ? (float)vd : 0.0f;
         const float sd = __fsqrt_rn(var);
@@ -3044,7 +3299,7 @@ hipError_t launch_tile_boxes(hipStream_t s, const float *x, const float *y, int6
 
 namespace {
 struct PlanLayout {
-    size_t key, scan, thr, desc, tl, seg, temp, temp_bytes, wkey, wscan, lvcnt, rec, bits;
+    size_t key, scan, thr, desc, tl, seg, temp, temp_bytes, wkey, wscan, lvcnt, rec, bits, nemask;
     // XCD-interleaved order (P % 8 == 0): the sweep reads desc2 / tl2 / seg2
     bool xcd;
     size_t xseg, pos_of, cnt2, off2, desc2, tl2, seg2, temp2, temp2_bytes;
@@ -3068,6 +3323,7 @@ PlanLayout plan_layout(int64_t nI, int64_t nQ, int P) {
     L.thr = take((size_t)items);
     L.wkey = take(8 * (size_t)items);
     L.wscan = take(8 * (size_t)items);
+    L.nemask = take(8 * (size_t)nQ * (size_t)((nI + 63) / 64));
     L.lvcnt = take(8 * 3 * 4 * (size_t)kPlanWriteBlocks);
     L.bits = take(8 * 3 * (size_t)items * (size_t)plan_chunks((int)nI));
     L.desc = take(16 * (size_t)(items + 2 * kDescWindow));
@@ -3152,14 +3408,25 @@ hipError_t launch_plan(hipStream_t s, const float4 *kbox, int64_t npad, const fl
     const int levels = lgn ? skip.levels : 0;
     auto *bits = reinterpret_cast<unsigned long long *>(w + L.bits);
     const int nc = std::min(kTilesPerRowBlockStep * nI, kPlanD2);
-    const size_t plan_lds = 4 * (size_t)kPlanWaves * kPlanBinCache + 8 * (size_t)nc;
+    const size_t plan_lds = 4 * (size_t)kPlanWaves * kPlanBinCache + 8 * (size_t)nc + 2 * (size_t)nc;
     hipLaunchKernelGGL(plan_count_kernel, dim3((unsigned)nQ), dim3(kPlanThreads), plan_lds, s, kbox, skip.kcoord, lgn,
                        levels, make_float2(skip.lvl_key[0], skip.lvl_key[1]), nI,
                        nQ, qx, qy,
                        m, cexp, skip_d2, skip_d2_mean, skip.lg_tau_v, m0, ldp, part, mean, key, thr, wkey, bits,
-                       skip.wide ? 1 : 0, skip.order_blk);
+                       skip.wide ? 1 : 0, skip.order_blk, lgn ? skip.colmax : nullptr, skip.zero_empty ? 1 : 0,
+                       reinterpret_cast<unsigned long long *>(w + L.nemask));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+#ifdef SBO_DIAG
+    if (getenv("SBO_PLAN_STATS")) {  // the column prefilter's near fraction of this plan, to stderr
+        unsigned long long h[9] = {}, z[9] = {};
+        (void)hipStreamSynchronize(s);
+        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_plan_near), sizeof(h));
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_plan_near), z, sizeof(z));
+        fprintf(stderr, "plan stats: near (qb, t) pairs %llu of %llu; clock setup %llu near %llu totals %llu fill %llu "
+                        "thresholds %llu levels %llu rest %llu\n", h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8]);
+    }
+#endif
     size_t tb = L.temp_bytes;
     e = rocprim::inclusive_scan(w + L.temp, tb, key, scan, (size_t)items, rocprim::plus<unsigned long long>(), s);
     if (e != hipSuccess) return e;
@@ -3190,9 +3457,11 @@ hipError_t launch_plan(hipStream_t s, const float4 *kbox, int64_t npad, const fl
     auto *tl2 = reinterpret_cast<unsigned short *>(w + L.tl2);
     auto *seg2 = reinterpret_cast<int *>(w + L.seg2);
     const int G = P / 8;
-    // (positions past the last non-empty item keep count 0 for the scan)
-    e = hipMemsetAsync(cnt2, 0, 8 * (size_t)items, s);
-    if (e != hipSuccess) return e;
+    // (positions past the last non-empty item count 0 for the scan: plan_perm writes them)
+    if (skip.ref_chain) {  // (the diagnostic build's reference chain clears them as before)
+        e = hipMemsetAsync(cnt2, 0, 8 * (size_t)items, s);
+        if (e != hipSuccess) return e;
+    }
     hipLaunchKernelGGL(plan_seg_kernel, dim3(1), dim3(256), 0, s, scan, items, desc, 8, xseg, tiles_done, wkey, wscan,
                        nI, nQ, skip.order_blk);
     hipLaunchKernelGGL(plan_perm_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, scan, items, desc,
@@ -3217,6 +3486,39 @@ void plan_views(int64_t npad, int64_t m, int P, const void *work, const int4 **d
     *tl = reinterpret_cast<const unsigned short *>(w + (L.xcd ? L.tl2 : L.tl));
     *seg = reinterpret_cast<const int *>(w + (L.xcd ? L.seg2 : L.seg));
     if (rec) *rec = reinterpret_cast<const int4 *>(w + L.rec);
+}
+
+void plan_item_views(int64_t npad, int64_t m, int P, const void *work, const unsigned long long **key,
+                     const unsigned long long **scan, const unsigned char **thr, const unsigned long long **nonempty) {
+    const PlanLayout L = plan_layout(npad / kBM, (m + kBN - 1) / kBN, P);
+    const char *w = static_cast<const char *>(work);
+    *key = reinterpret_cast<const unsigned long long *>(w + L.key);
+    *scan = reinterpret_cast<const unsigned long long *>(w + L.scan);
+    *thr = reinterpret_cast<const unsigned char *>(w + L.thr);
+    if (nonempty) *nonempty = reinterpret_cast<const unsigned long long *>(w + L.nemask);
+}
+
+namespace {
+// colmax[t] = max over the row blocks I that hold k-tile t of lgn[2 (tile_start(I) + t)].x
+// (+inf if one is NaN: such a pair is never far)
+__global__ void tile_colmax_kernel(const float4 *__restrict__ lgn, int nI, float *__restrict__ colmax) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= kTilesPerRowBlockStep * nI) return;
+    float mx = -INFINITY;
+    for (int I = t / kTilesPerRowBlockStep; I < nI; ++I) {
+        const float v = lgn[2 * (tile_start(I) + t)].x;
+        mx = v != v ? INFINITY : fmaxf(mx, v);
+    }
+    colmax[t] = mx;
+}
+}  // namespace
+
+hipError_t launch_tile_colmax(hipStream_t s, const float4 *lgn, int64_t npad, float *colmax) {
+    const int nI = (int)(npad / kBM);
+    if (nI <= 0) return hipSuccess;
+    hipLaunchKernelGGL(tile_colmax_kernel, dim3((unsigned)((kTilesPerRowBlockStep * nI + 255) / 256)), dim3(256), 0, s,
+                       lgn, nI, colmax);
+    return hipGetLastError();
 }
 
 float exp2_coef_f(float ell) { return (float)exp2_coef(ell); }
@@ -3257,20 +3559,20 @@ hipError_t launch_predict(hipStream_t s, const float *aug, const float *kcoord, 
 hipError_t launch_acquire(hipStream_t s, const float *part, const float *mean, int nI, int64_t ldp,
                           int64_t m, float sf2, double beta, double f_min, int score_kind,
                           int64_t index_offset, const int32_t *perm, float *mu, float *sd, double *lo,
-                          double *hi, uint8_t *safe, sbo_key *block_keys) {
+                          double *hi, uint8_t *safe, sbo_key *block_keys, const unsigned long long *nonempty) {
     hipLaunchKernelGGL(acquire_kernel<float>, dim3((unsigned)acq_blocks(m)), dim3(kAcqThreads), 0, s, part, mean,
                        nI, ldp, m, (double)sf2, beta, f_min, score_kind, index_offset, perm, mu, sd, lo, hi, safe,
-                       block_keys);
+                       block_keys, nonempty);
     return hipGetLastError();
 }
 
 hipError_t launch_acquire(hipStream_t s, const double *part, const double *mean, int nI, int64_t ldp,
                           int64_t m, double sf2, double beta, double f_min, int score_kind,
                           int64_t index_offset, const int32_t *perm, float *mu, float *sd, double *lo,
-                          double *hi, uint8_t *safe, sbo_key *block_keys) {
+                          double *hi, uint8_t *safe, sbo_key *block_keys, const unsigned long long *nonempty) {
     hipLaunchKernelGGL(acquire_kernel<double>, dim3((unsigned)acq_blocks(m)), dim3(kAcqThreads), 0, s, part, mean,
                        nI, ldp, m, sf2, beta, f_min, score_kind, index_offset, perm, mu, sd, lo, hi, safe,
-                       block_keys);
+                       block_keys, nonempty);
     return hipGetLastError();
 }
 

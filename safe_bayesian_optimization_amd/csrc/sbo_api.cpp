@@ -1237,6 +1237,14 @@ sbo_status refresh_f32(sbo_ctx *ctx, const RefreshPlan &p) {
     return SBO_OK;
 }
 
+// The plan's column prefilter (SkipPlan::colmax) from the tile norms on
+// `stream`, whole: an append changes the columns of every k-tile.
+sbo_status refresh_colmax(sbo_ctx *ctx, int64_t npad) {
+    SBO_HIP(ctx->tile_colmax.reserve(sizeof(float) * (size_t)(npad / sbo::kBK)));
+    SBO_HIP(sbo::launch_tile_colmax(ctx->stream, ctx->tile_lgn.as<float4>(), npad, ctx->tile_colmax.as<float>()));
+    return SBO_OK;
+}
+
 // What is left of the packs on `stream` -- the row sums and tile norms that
 // did not run with the fork, the coordinate pack once alpha is there -- and
 // the join with aux_stream.
@@ -1252,6 +1260,7 @@ sbo_status refresh_join(sbo_ctx *ctx, const RefreshPlan &p) {
                           2 * sizeof(float4) * p.old_tiles));
         SBO_HIP(sbo::launch_tile_norms(ctx->stream, ctx->aug.as<float>(), npad, p.I0, ctx->tile_lgn.as<float4>()));
     }
+    if (sbo_status st = refresh_colmax(ctx, npad)) return st;
     if (p.f64) {   // (refresh_f32's pack wrote the coordinates)
         if (p.aux) SBO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_trail, 0));
         SBO_HIP(sbo::launch_pack_kcoord(ctx->stream, ctx->x.as<float>(), ctx->y.as<float>(), ctx->alpha.as<float>(),
@@ -1892,6 +1901,7 @@ sbo_status run_tick(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, d
         skip_budget_for(ctx, ctx->probe_ref_tol, plan.L, plan.lg_tau_v);
         plan.L_mean = ctx->auto_skip_mean_log2;
         plan.lgn = ctx->tile_lgn.as<float4>();
+        plan.colmax = ctx->tile_colmax.as<float>();
         plan.kcoord = ctx->kcoord.as<float>();
     } else if (ctx->skip_log2 < 0) {
         plan.L = precise ? ctx->p_skip_log2 : ctx->auto_skip_log2;
@@ -1901,6 +1911,7 @@ sbo_status run_tick(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, d
         // its budget
         plan.L_mean = precise ? std::min(160, ctx->auto_skip_mean_log2 + 8) : ctx->auto_skip_mean_log2;
         plan.lgn = ctx->tile_lgn.as<float4>();
+        plan.colmax = ctx->tile_colmax.as<float>();
         plan.levels = !precise && sbo::x3_levels(ctx->kernel_variant) ? 1 : 0;
         plan.kcoord = ctx->kcoord.as<float>();
         plan.lg_tau_v = precise ? ctx->p_lg_tau_v : ctx->lg_tau_v;
@@ -1973,12 +1984,25 @@ sbo_status run_tick(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, d
     // (the K* table's precise sweep plans each chunk of query blocks itself)
     const bool chunked = precise && ctx->precise_kernel >= 3 && ctx->precise_kernel != 9 && !cost;
     const bool pairs = ctx->precise_kernel == 4 || ctx->precise_kernel == 10;
+    // (a chunk's plan is gone by the acquisition: its empty items' partials are written)
+    plan.zero_empty = chunked;
+#ifdef SBO_DIAG
+    // the reference plan builder (diagnostic build only): every pair's bounds
+    // evaluated in every pass, empty items' partials written and read
+    if (const char *e = getenv("SBO_PLAN_REF"); e && atoi(e)) {
+        plan.colmax = nullptr;
+        plan.zero_empty = true;
+        plan.ref_chain = true;
+    }
+#endif
     if (!chunked)
         SBO_HIP(sbo::launch_plan(ctx->stream, ctx->kbox.as<float4>(), ctx->npad, qx, qy, ms, ldp,
                                  (float)ctx->hyper.length_scale, (float)ctx->hyper.prior_mean, plan,
                                  ctx->part.as<float>(), ctx->mean.as<float>(),
                                  ctx->prof && !cost ? ctx->counters.as<unsigned long long>() : nullptr, P,
                                  ctx->plan_work.as<void>(), ctx->plan_work.capacity()));
+    ctx->plan_ms = chunked ? 0 : ms;
+    ctx->plan_P = P;
     if (cost) {  // sbo_query_cost: the plan's work per query, no sweep
         SBO_HIP(ctx->qcost.reserve(sizeof(float) * (size_t)((ms + sbo::kBN - 1) / sbo::kBN)));
         SBO_HIP(sbo::launch_plan_cost(ctx->stream, ctx->npad, ms, P, ctx->plan_work.as<void>(), perm,
@@ -2081,14 +2105,19 @@ sbo_status run_tick(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, d
                                     ctx->part.as<float>(), ctx->mean.as<float>(), ctx->kernel_variant, P,
                                     ctx->plan_work.as<void>()));
     }
+    const unsigned long long *pkey = nullptr, *pscan = nullptr, *nonempty = nullptr;
+    const unsigned char *pthr = nullptr;
+    if (!plan.zero_empty)
+        sbo::plan_item_views(ctx->npad, ms, P, ctx->plan_work.as<void>(), &pkey, &pscan, &pthr, &nonempty);
     if (precise) {
         SBO_HIP(sbo::launch_acquire(ctx->stream, ctx->part.as<double>(), ctx->mean.as<double>(), (int)nI, ldp, ms,
                                     ctx->hyper.sigma_f * ctx->hyper.sigma_f, beta, f_min, score_kind, index_offset,
-                                    perm, mu, sd, lo, hi, safe, bkeys));
+                                    perm, mu, sd, lo, hi, safe, bkeys, nonempty));
     } else {
         const float sf2 = (float)(ctx->hyper.sigma_f * ctx->hyper.sigma_f);
         SBO_HIP(sbo::launch_acquire(ctx->stream, ctx->part.as<float>(), ctx->mean.as<float>(), (int)nI, ldp, ms, sf2,
-                                    beta, f_min, score_kind, index_offset, perm, mu, sd, lo, hi, safe, bkeys));
+                                    beta, f_min, score_kind, index_offset, perm, mu, sd, lo, hi, safe, bkeys,
+                                    nonempty));
     }
     SBO_HIP(sbo::launch_reduce_keys(ctx->stream, bkeys, nb, key_dev ? key_dev : bkeys + nb));
     return SBO_OK;
@@ -2678,6 +2707,79 @@ SBO_API sbo_status sbo_debug_x3_operand(sbo_ctx *ctx, void *host_buf, int64_t ca
     if (cap < need) return SBO_E_INVAL;
     SBO_HIP(hipMemcpyAsync(host_buf, ctx->ax3.as<char>(), (size_t)need, hipMemcpyDeviceToHost, ctx->stream));
     SBO_HIP(hipStreamSynchronize(ctx->stream));
+    return SBO_OK;
+}
+
+SBO_API sbo_status sbo_debug_plan(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, int32_t *host_buf,
+                                  int64_t cap, int64_t *n_out) {
+    if (!ctx || !n_out || cap < 0) return SBO_E_INVAL;
+    SBO_CHECK(ctx->fitted, SBO_E_STATE, "sbo_debug_plan: call sbo_fit first");
+    SBO_CHECK(qx && qy, SBO_E_INVAL, "sbo_debug_plan: null pointer");
+    SBO_CHECK(m > 0, SBO_E_EMPTY, "sbo_debug_plan: m must be > 0");
+    SBO_HIP(hipSetDevice(ctx->device));
+    // the plan sbo_query_cost builds (no sweep), then its items and lists read back
+    SBO_HIP(ctx->hq.reserve(Carve::need(m, 4) * 3));
+    Carve c(ctx->hq.as<void>());
+    float *dqx = c.take<float>(m), *dqy = c.take<float>(m), *dc = c.take<float>(m);
+    SBO_HIP(hipMemcpyAsync(dqx, qx, sizeof(float) * m, hipMemcpyHostToDevice, ctx->stream));
+    SBO_HIP(hipMemcpyAsync(dqy, qy, sizeof(float) * m, hipMemcpyHostToDevice, ctx->stream));
+    if (sbo_status st = run_tick(ctx, dqx, dqy, m, 0.0, 0.0, SBO_SCORE_WIDTH, 0, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr, dc))
+        return st;
+    const int64_t nI = ctx->npad / sbo::kBM, ms = ctx->plan_ms, nQ = (ms + sbo::kBN - 1) / sbo::kBN;
+    const int64_t items = nI * nQ;
+    const unsigned long long *key = nullptr, *scan = nullptr;
+    const unsigned char *thr = nullptr;
+    const int4 *desc = nullptr;
+    const unsigned short *tl = nullptr;
+    const int *seg = nullptr;
+    sbo::plan_item_views(ctx->npad, ms, ctx->plan_P, ctx->plan_work.as<void>(), &key, &scan, &thr);
+    sbo::plan_views(ctx->npad, ms, ctx->plan_P, ctx->plan_work.as<void>(), &desc, &tl, &seg);
+    std::vector<unsigned long long> hkey((size_t)items);
+    std::vector<unsigned char> hthr((size_t)items);
+    unsigned long long last = 0;
+    SBO_HIP(hipMemcpyAsync(hkey.data(), key, 8 * (size_t)items, hipMemcpyDeviceToHost, ctx->stream));
+    SBO_HIP(hipMemcpyAsync(hthr.data(), thr, (size_t)items, hipMemcpyDeviceToHost, ctx->stream));
+    SBO_HIP(hipMemcpyAsync(&last, scan + items - 1, 8, hipMemcpyDeviceToHost, ctx->stream));
+    SBO_HIP(hipStreamSynchronize(ctx->stream));
+    const unsigned long long cmask = (1ull << 40) - 1ull;
+    const int64_t total = (int64_t)(last & cmask), nne = (int64_t)(last >> 40);
+    const int64_t need = 4 + 2 * items + 4 * total;
+    *n_out = need;
+    if (!host_buf) return SBO_OK;
+    if (cap < need) return SBO_E_INVAL;
+    std::vector<int4> hdesc((size_t)nne);
+    std::vector<unsigned short> htl((size_t)total);
+    if (nne) SBO_HIP(hipMemcpyAsync(hdesc.data(), desc, 16 * (size_t)nne, hipMemcpyDeviceToHost, ctx->stream));
+    if (total) SBO_HIP(hipMemcpyAsync(htl.data(), tl, 2 * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    SBO_HIP(hipStreamSynchronize(ctx->stream));
+    host_buf[0] = (int32_t)nI;
+    host_buf[1] = (int32_t)nQ;
+    host_buf[2] = (int32_t)total;
+    host_buf[3] = (int32_t)nne;
+    int32_t *it = host_buf + 4, *rec = it + 2 * items;
+    for (int64_t I = 0; I < nI; ++I)
+        for (int64_t qb = 0; qb < nQ; ++qb) {
+            const int64_t item = (nI - 1 - I) * nQ + qb;   // plan_item, row-block-major
+            it[2 * (I * nQ + qb)] = (int32_t)hthr[(size_t)item];
+            it[2 * (I * nQ + qb) + 1] = (int32_t)(hkey[(size_t)item] & cmask);
+        }
+    int64_t r = 0;
+    for (int64_t k = 0; k < nne; ++k) {
+        const int4 d = hdesc[(size_t)k];
+        const int cnt = d.w & 0xffff;
+        const uint64_t off = (uint64_t)(uint32_t)d.z | ((uint64_t)((uint32_t)d.w >> 16) << 32);
+        SBO_CHECK(off + (uint64_t)cnt <= (uint64_t)total && r + cnt <= total, SBO_E_DEVICE,
+                  "sbo_debug_plan: a descriptor points outside the tile list");
+        for (int i = 0; i < cnt; ++i, ++r) {
+            const unsigned short te = htl[(size_t)off + i];
+            rec[4 * r] = d.x;
+            rec[4 * r + 1] = d.y;
+            rec[4 * r + 2] = te & ((1 << sbo::kLevelShift) - 1);
+            rec[4 * r + 3] = te >> sbo::kLevelShift;
+        }
+    }
+    SBO_CHECK(r == total, SBO_E_DEVICE, "sbo_debug_plan: the descriptors' counts do not sum to the plan's total");
     return SBO_OK;
 }
 
@@ -3397,6 +3499,7 @@ SBO_API sbo_status sbo_import_state(sbo_ctx *ctx, const void *dev_buf, int64_t b
                            ctx->stream));
     SBO_HIP(hipMemcpyAsync(ctx->tile_lgn.as<void>(), b + h.off_lgn, 32 * (size_t)sbo::total_tiles(h.npad / sbo::kBM),
                            hipMemcpyDeviceToDevice, ctx->stream));
+    if (sbo_status st = refresh_colmax(ctx, h.npad)) return st;
     SBO_HIP(hipStreamSynchronize(ctx->stream));
     {   // the order must be a permutation of 0..n-1 (it indexes the caller's arrays)
         std::vector<uint8_t> seen((size_t)h.n, 0);

@@ -164,6 +164,7 @@ struct sbo_ctx {
     int auto_skip_mean_log2 = 160;  // auto cutoff the last row block keeps for the mean
     float lg_tau_v = -1000.0f;   // log2 of each row block's |dV_I|_2 budget (tile-norm test)
     sbo::DevBuf tile_lgn;        // per packed tile: log2 gain bounds of A_It and of its bf16 pieces (2 x float4)
+    sbo::DevBuf tile_colmax;     // per k-tile: the largest tile_lgn[..].x of its column (the plan's prefilter)
     int skip_budget = 20;        // SBO_OPT_SKIP_BUDGET: the auto cutoff keeps the skip error below 2^-B
     double max_row_l1 = 0.0;     // max_i sum_j |A_ij|, A = sf2 L^-1
     double alpha_l1 = 0.0;       // sum_j |sf2 alpha_j|
@@ -179,6 +180,8 @@ struct sbo_ctx {
     int sweep_groups = 0;        // SBO_OPT_SWEEP_GROUPS: persistent sweep workgroups (0: one per CU)
     int num_cu = 0;              // compute units of the device
     sbo::DevBuf plan_work;       // the tick's tile plan (launch_plan)
+    int64_t plan_ms = 0;         // sweep positions and workgroups of the unchunked plan last built there
+    int plan_P = 0;              // (sbo_debug_plan)
     sbo::DevBuf fwork, fowner, fimg, fpix, fout;  // device frontier (sbo_frontier / sbo_subgoal)
     sbo::DevBuf qwork;           // query ordering workspace
     sbo::DevBuf kbox;            // per k-tile bounding boxes (float4)
@@ -297,6 +300,14 @@ struct SkipPlan {
     bool records = false;  // also write the split sweep's step records (plan_views' rec)
     bool wide = false;     // empty items' outputs as f64 (the precise sweep's partials and mean)
     int order_blk = 0;     // item order: 0 row-block-major, else blocks of (bi << 8 | bq) -- plan_item
+    // with lgn: per k-tile max over row blocks of lgn[..].x (launch_tile_colmax), the plan's
+    // column prefilter; null: every (row block, k-tile) pair is tested on its own
+    const float *colmax = nullptr;
+    // write an empty item's partial (0) instead of leaving it to the acquisition to skip
+    // (launch_acquire's nonempty): for plans that do not live until then
+    bool zero_empty = false;
+    // diagnostic build's reference: cnt2 cleared by a memset, as before plan_perm wrote every position
+    bool ref_chain = false;
     // rank of a tile's two level increments against drops: log2(time a drop
     // saves / time the level step saves), per-tile sweep time at C4 of six,
     // three, one product(s) 18.6, 12.9, 9.9 ns (variants 22, 20, 21)
@@ -324,6 +335,16 @@ hipError_t launch_plan_cost(hipStream_t s, int64_t npad, int64_t m, int P, const
 // The plan's descriptors, tile lists and per-workgroup ranges inside `work`.
 void plan_views(int64_t npad, int64_t m, int P, const void *work, const int4 **desc, const unsigned short **tl,
                 const int **seg, const int4 **rec = nullptr);
+// Per item of the plan in `work` (index: plan_item order, row-block-major for
+// order_blk 0: (nI - 1 - I) * nQ + qb): key = kept-tile count (low 40 bits) |
+// non-empty << 40, its inclusive scan, and the budget threshold + 1.
+// nonempty (may be null): per query block (nI + 63) / 64 words, bit I set when
+// item (I, qb) keeps a tile (launch_acquire).
+void plan_item_views(int64_t npad, int64_t m, int P, const void *work, const unsigned long long **key,
+                     const unsigned long long **scan, const unsigned char **thr,
+                     const unsigned long long **nonempty = nullptr);
+// colmax[t], t < npad / kBK: the largest lgn[2 (tile_start(I) + t)].x over the row blocks I that hold k-tile t
+hipError_t launch_tile_colmax(hipStream_t s, const float4 *lgn, int64_t npad, float *colmax);
 // Split-operand (bf16 x3) predictive sweep, predict_x3.hip: the packed
 // operand split into three bf16 planes per row half of a tile (48 KiB stages,
 // predict_x3_rowhalf.hpp) and the per-k-tile coordinates in natural order,
@@ -421,16 +442,20 @@ hipError_t launch_tile_boxes(hipStream_t s, const float *x, const float *y, int6
                              float4 *kbox);
 // Acquisition over predictive partials (fused reduce + sets + block argmax).
 // perm (may be null): sweep position i holds caller query perm[i]; outputs and
-// key indices are written in the caller's order.
+// key indices are written in the caller's order.  nonempty (may be null): the
+// non-empty items of the plan the partials were swept under (plan_item_views):
+// the partial of an empty item is not read (SkipPlan::zero_empty).
 hipError_t launch_acquire(hipStream_t s, const float *part, const float *mean, int nI, int64_t ldp,
                           int64_t m, float sf2, double beta, double f_min, int score_kind,
                           int64_t index_offset, const int32_t *perm, float *mu, float *sd, double *lo,
-                          double *hi, uint8_t *safe, sbo_key *block_keys);
+                          double *hi, uint8_t *safe, sbo_key *block_keys,
+                          const unsigned long long *nonempty = nullptr);
 // the same over the precise sweep's f64 partials and mean (sf2 in f64)
 hipError_t launch_acquire(hipStream_t s, const double *part, const double *mean, int nI, int64_t ldp,
                           int64_t m, double sf2, double beta, double f_min, int score_kind,
                           int64_t index_offset, const int32_t *perm, float *mu, float *sd, double *lo,
-                          double *hi, uint8_t *safe, sbo_key *block_keys);
+                          double *hi, uint8_t *safe, sbo_key *block_keys,
+                          const unsigned long long *nonempty = nullptr);
 // Precise sweep (predict_f64.hip, SBO_OPT_PRECISION): A = sf2 L^-1 packed in
 // f64 from the fit's f64 inverse for row blocks >= I0 (tile (I, t) at
 // tile_start(I) + t, two 64 KiB stages in MFMA fragment order), and per k-tile
