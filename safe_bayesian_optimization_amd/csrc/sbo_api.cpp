@@ -624,7 +624,7 @@ sbo_status stage_training(sbo_ctx *ctx, const float *x, const float *y, const fl
 struct Carve {
     char *base;
     size_t off = 0;
-    explicit Carve(void *b) : base(static_cast<char *>(b)) {}
+    explicit Carve(void *b = nullptr) : base(static_cast<char *>(b)) {}
     template <class T> T *take(size_t count) {
         T *p = reinterpret_cast<T *>(base + off);
         off += (count * sizeof(T) + 255) & ~size_t(255);
@@ -649,14 +649,15 @@ struct Bracket {
     sbo_ctx *ctx;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> *list;
     hipEvent_t a = nullptr, b = nullptr;
-    Bracket(sbo_ctx *c, std::vector<std::pair<hipEvent_t, hipEvent_t>> &l) : ctx(c), list(&l) {
-        if (!ctx->prof) return;
+    // (on: a caller's own switch beside sbo_profile's, TickPlan::prof)
+    Bracket(sbo_ctx *c, std::vector<std::pair<hipEvent_t, hipEvent_t>> &l, bool on = true) : ctx(c), list(&l) {
+        if (!ctx->prof || !on) return;
         a = take_event(ctx);
         b = take_event(ctx);
         if (a) (void)hipEventRecord(a, ctx->stream);
     }
     ~Bracket() {
-        if (!ctx->prof || !a || !b) return;
+        if (!a || !b) return;
         (void)hipEventRecord(b, ctx->stream);
         list->emplace_back(a, b);
     }
@@ -688,16 +689,67 @@ hipError_t grow_keep(sbo_ctx *ctx, DevBuf &buf, size_t bytes, size_t keep) {
     return hipSuccess;
 }
 
-// sweep selection of run_tick: -1 the context's (ctx->precise), 0 the fast
-// split sweep, 1 the precise f64 sweep under its budget, 2 the precise sweep
-// under a 2^-kProbeRefBits budget relative to the probe's largest variance (the probe's reference)
-constexpr int kSweepCtx = -1, kSweepFast = 0, kSweepPrecise = 1, kSweepPreciseDense = 2;
-// The Morton order of one query set (pointers into qwork, valid while qwork
-// is untouched): a tick given an empty one fills it, a tick given a filled
-// one sweeps in that order instead of sorting again (the probe's two sweeps).
+// ------------------------------------------------------------ tick pipeline
+// What a tick is asked for: the plan alone (sbo_debug_plan), the plan and its
+// per-query cost (sbo_query_cost), or plan, sweep and acquisition.
+enum class TickWant { kPlan, kCost, kTick };
+// Which sweep: the context's (ctx->precise), the fast sweep, the precise
+// sweep under its budget, or the precise sweep under a budget of
+// 2^-kProbeRefBits of the probe's largest variance (the probe's reference).
+enum class Sweep { kCtx, kFast, kPrecise, kProbeRef };
+// The sweep order of one query set, as an earlier tick of the same queries
+// returned it (TickPlan::perm, qx, qy: pointers into qwork, valid while qwork
+// is untouched).  Empty: the tick orders the queries itself.
 struct QueryOrder {
-    int32_t *perm = nullptr;
-    float *sx = nullptr, *sy = nullptr;
+    const int32_t *perm = nullptr;
+    const float *sx = nullptr, *sy = nullptr;
+};
+// One tick over m queries on the device.  Outputs not wanted stay null; key
+// null leaves the argmax key behind the block keys in ctx->keys.
+struct TickRequest {
+    const float *qx = nullptr, *qy = nullptr;
+    int64_t m = 0;
+    double beta = 0.0, f_min = 0.0;
+    int score = SBO_SCORE_WIDTH;
+    int64_t index_offset = 0;
+    float *mu = nullptr, *sd = nullptr;
+    double *lo = nullptr, *hi = nullptr;
+    uint8_t *safe = nullptr;
+    sbo_key *key = nullptr;
+    float *cost = nullptr;       // kCost: the per-query cost, in the caller's order
+    TickWant want = TickWant::kTick;
+    Sweep sweep = Sweep::kCtx;
+    QueryOrder order;
+    bool quiet = false;          // no profile events, no counters (the probe is not a tick)
+};
+// What SBO_OPT_PRECISE_KERNEL's value selects: the operand's layout (0 f64
+// tiles, 1 int8 digit tiles, 2 int8 with exponents shared by k-tile pairs),
+// the int8 sweep, its K* table (the chunked tick), the pair exponents.
+struct PreciseKernel {
+    int layout;
+    bool int8, table, pairs;
+};
+PreciseKernel precise_kernel_traits(int k) {
+    const bool pairs = k == 4 || k == 10;
+    return {k == 0 ? 0 : pairs ? 2 : 1, k >= 1, k >= 3 && k != 9, pairs};
+}
+// Everything a tick's stages read, computed once from (ctx, request) by
+// tick_plan; tick_order_queries fills the second half.  A plan-only or cost
+// request keeps its items row-block-major (the cost kernel and sbo_debug_plan
+// index them so), is never chunked and counts nothing.
+struct TickPlan {
+    int64_t nI = 0;              // row blocks
+    int P = 0;                   // sweep workgroups
+    bool precise = false;
+    PreciseKernel pk{};
+    bool chunked = false;        // the K* table's sweep: each chunk of query blocks plans itself
+    bool prof = false;           // record events and counters where sbo_profile is on
+    sbo::SkipPlan skip;
+    // the queries in sweep order: ms positions (>= m: padded patches), nQ
+    // query blocks, partials' leading dimension; perm null: the caller's order
+    int64_t ms = 0, nQ = 0, ldp = 0;
+    const int32_t *perm = nullptr;
+    const float *qx = nullptr, *qy = nullptr;
 };
 // The split operand of the current kernel variant's layout, brought up to
 // date on ctx->stream: the bf16 planes of any row block repacked since it was
@@ -718,10 +770,7 @@ sbo_status derive_x3(sbo_ctx *ctx) {
     return SBO_OK;
 }
 
-sbo_status run_tick(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, double beta, double f_min,
-                    int score_kind, int64_t index_offset, float *mu, float *sd, double *lo, double *hi,
-                    uint8_t *safe, sbo_key *key_dev, float *cost = nullptr, int sweep = kSweepCtx,
-                    QueryOrder *order = nullptr);
+sbo_status run_tick(sbo_ctx *ctx, const TickRequest &rq, TickPlan *plan_out = nullptr);
 sbo_status probe_precision(sbo_ctx *ctx);
 // the precision probe runs on this refresh (probe_precision): on a fresh fit,
 // and on appends once N has grown by SBO_OPT_REPROBE % (default a quarter)
@@ -778,7 +827,7 @@ struct FitCommit {
 // before it forks work onto aux_stream, so that the fork is not serialised).
 sbo_status reserve_precise(sbo_ctx *ctx, int64_t npad, int64_t I0) {
     if (sbo_status st = drain_poz(ctx)) return st;
-    if (ctx->precise_kernel >= 1) {
+    if (precise_kernel_traits(ctx->precise_kernel).int8) {
         SBO_HIP(grow_keep(ctx, ctx->aoz, sbo::oz_operand_bytes(npad), sbo::oz_operand_bytes(I0 * sbo::kBM)));
         SBO_HIP(grow_keep(ctx, ctx->eoz, sbo::oz_exp_bytes(npad), sbo::oz_exp_bytes(I0 * sbo::kBM)));
         SBO_HIP(ctx->koz.reserve(sbo::oz_coord_bytes(npad)));
@@ -795,11 +844,11 @@ sbo_status reserve_precise(sbo_ctx *ctx, int64_t npad, int64_t I0) {
 sbo_status pack_precise(sbo_ctx *ctx, hipStream_t s, int64_t npad, int64_t I0) {
     if (sbo_status st = reserve_precise(ctx, npad, I0)) return st;
     const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
-    if (ctx->precise_kernel >= 1) {
+    const PreciseKernel pk = precise_kernel_traits(ctx->precise_kernel);
+    if (pk.int8) {
         SBO_HIP(sbo::launch_pack_oz(s, ctx->Linv.as<double>(), ctx->cap, ctx->n, npad, I0, sf2, ctx->x.as<float>(),
                                     ctx->y.as<float>(), ctx->alpha64.as<double>(), ctx->aoz.as<char>(),
-                                    ctx->eoz.as<int>(), ctx->koz.as<char>(),
-                                    ctx->precise_kernel == 4 || ctx->precise_kernel == 10));
+                                    ctx->eoz.as<int>(), ctx->koz.as<char>(), pk.pairs));
     } else {
         SBO_HIP(sbo::launch_pack_f64(s, ctx->Linv.as<double>(), ctx->cap, ctx->n, npad, I0, sf2, ctx->x.as<float>(),
                                      ctx->y.as<float>(), ctx->alpha64.as<double>(), ctx->a64.as<double>(),
@@ -1499,11 +1548,17 @@ sbo_status probe_precision(sbo_ctx *ctx) {
         SBO_HIP(hipMemcpyAsync(qy, h.data() + M, sizeof(float) * MG, hipMemcpyHostToDevice, ctx->stream));
         // the training part: every stride-th stored point
         if (sbo_status cst = copy_strided_points(ctx, ctx->stream, stride, MT, qx + MG, qy + MG)) return cst;
-        const bool prof = ctx->prof;
-        ctx->prof = false;  // (the probe is not a tick: no events, no counters)
-        QueryOrder order;
-        sbo_status st = run_tick(ctx, qx, qy, M, 0.0, 0.0, SBO_SCORE_WIDTH, 0, nullptr, sdf, nullptr, nullptr,
-                                 nullptr, key, nullptr, kSweepFast, &order);
+        // the two sweeps: the same queries, each its own sweep and output
+        TickRequest fast;
+        fast.qx = qx;
+        fast.qy = qy;
+        fast.m = M;
+        fast.sd = sdf;
+        fast.key = key;
+        fast.sweep = Sweep::kFast;
+        fast.quiet = true;
+        TickPlan fast_plan;
+        sbo_status st = run_tick(ctx, fast, &fast_plan);
         if (st == SBO_OK) {
             // the reference's budget: 2^-kProbeRefBits of the largest variance
             // the fast sweep sees (its own error is orders below that: any
@@ -1523,10 +1578,12 @@ sbo_status probe_precision(sbo_ctx *ctx) {
         if (st == SBO_OK) {
             // the same queries as the fast sweep's: its Morton order again
             // (qwork untouched in between)
-            st = run_tick(ctx, qx, qy, M, 0.0, 0.0, SBO_SCORE_WIDTH, 0, nullptr, sdp, nullptr, nullptr, nullptr, key,
-                          nullptr, kSweepPreciseDense, &order);
+            TickRequest ref = fast;
+            ref.sd = sdp;
+            ref.sweep = Sweep::kProbeRef;
+            ref.order = QueryOrder{fast_plan.perm, fast_plan.qx, fast_plan.qy};
+            st = run_tick(ctx, ref);
         }
-        ctx->prof = prof;
         if (st != SBO_OK) return st;
         SBO_HIP(hipMemcpyAsync(h.data(), sdf, sizeof(float) * 2 * M, hipMemcpyDeviceToHost, ctx->stream));
         SBO_HIP(hipStreamSynchronize(ctx->stream));
@@ -1880,57 +1937,101 @@ sbo_status factor_and_refresh(sbo_ctx *ctx) {
     return refresh_operand(ctx, 0, ho);
 }
 
-// Predictive sweep + acquisition over m queries already on the device.
-sbo_status run_tick(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, double beta, double f_min,
-                    int score_kind, int64_t index_offset, float *mu, float *sd, double *lo, double *hi,
-                    uint8_t *safe, sbo_key *key_dev, float *cost, int sweep, QueryOrder *order) {
-    const int64_t nI = ctx->npad / sbo::kBM;
-    if (sweep == kSweepCtx) sweep = ctx->precise ? kSweepPrecise : kSweepFast;
-    SBO_CHECK(sweep == kSweepFast || (ctx->has_factor && ctx->linv_n == ctx->n && ctx->inverse_bits == 64),
-              SBO_E_STATE, "precise sweep: needs the fit's f64 inverse (not an imported state, INVERSE_BITS 64)");
-    const bool precise = sweep != kSweepFast;
-    // sweep the queries in grid patches or Morton order (compact 128-query
-    // blocks skip more k-tiles); ms sweep positions (>= m: padded patches)
-    const int32_t *perm = nullptr;
-    int64_t ms = m;
-    sbo::SkipPlan plan;
-    if (sweep == kSweepPreciseDense) {
-        // the probe's reference: the precise sweep under a budget of
-        // 2^-kProbeRefBits of the largest variance the probe's fast sweep saw
-        // (probe_precision)
-        skip_budget_for(ctx, ctx->probe_ref_tol, plan.L, plan.lg_tau_v);
-        plan.L_mean = ctx->auto_skip_mean_log2;
-        plan.lgn = ctx->tile_lgn.as<float4>();
-        plan.colmax = ctx->tile_colmax.as<float>();
-        plan.kcoord = ctx->kcoord.as<float>();
+// The tile cutoff of one sweep (sbo::SkipPlan): the fields every regime shares,
+// then one branch per regime -- the probe's reference, the automatic cutoff of
+// the fast and of the precise sweep (SBO_OPT_TILE_SKIP -1), the fixed cutoff.
+sbo::SkipPlan skip_rule(const sbo_ctx *ctx, Sweep sweep) {
+    const bool precise = sweep != Sweep::kFast;
+    const bool split = !precise && ctx->kernel_variant >= 2;
+    sbo::SkipPlan s;
+    s.prod_full = split ? 6 : 1;
+    s.records = split;
+    s.wide = precise;
+    // the tile-norm test's tables (the automatic cutoffs)
+    auto tile_norms = [&] {
+        s.lgn = ctx->tile_lgn.as<float4>();
+        s.colmax = ctx->tile_colmax.as<float>();
+        s.kcoord = ctx->kcoord.as<float>();
+    };
+    if (sweep == Sweep::kProbeRef) {
+        // the precise sweep under a budget of 2^-kProbeRefBits of the largest
+        // variance the probe's fast sweep saw (probe_precision)
+        skip_budget_for(ctx, ctx->probe_ref_tol, s.L, s.lg_tau_v);
+        s.L_mean = ctx->auto_skip_mean_log2;
+        tile_norms();
+    } else if (ctx->skip_log2 < 0 && !precise) {
+        s.L = ctx->auto_skip_log2;
+        s.L_mean = ctx->auto_skip_mean_log2;
+        s.lg_tau_v = ctx->lg_tau_v;
+        s.levels = sbo::x3_levels(ctx->kernel_variant) ? 1 : 0;
+        tile_norms();
     } else if (ctx->skip_log2 < 0) {
-        plan.L = precise ? ctx->p_skip_log2 : ctx->auto_skip_log2;
+        s.L = ctx->p_skip_log2;
         // the precise sweep's mean 2^8 tighter than the budget's 2^-B sf
         // (absolute): its tiles are the last row block's only, and the mean
         // of an ill-conditioned fit (large |alpha|_1) otherwise sits right at
         // its budget
-        plan.L_mean = precise ? std::min(160, ctx->auto_skip_mean_log2 + 8) : ctx->auto_skip_mean_log2;
-        plan.lgn = ctx->tile_lgn.as<float4>();
-        plan.colmax = ctx->tile_colmax.as<float>();
-        plan.levels = !precise && sbo::x3_levels(ctx->kernel_variant) ? 1 : 0;
-        plan.kcoord = ctx->kcoord.as<float>();
-        plan.lg_tau_v = precise ? ctx->p_lg_tau_v : ctx->lg_tau_v;
+        s.L_mean = std::min(160, ctx->auto_skip_mean_log2 + 8);
+        s.lg_tau_v = ctx->p_lg_tau_v;
+        tile_norms();
     } else {
-        plan.L = ctx->skip_log2;
+        s.L = ctx->skip_log2;
     }
-    plan.prod_full = !precise && ctx->kernel_variant >= 2 ? 6 : 1;
-    plan.records = !precise && ctx->kernel_variant >= 2;
-    plan.wide = precise;
-    plan.order_blk = precise && !cost ? ctx->plan_block : 0;   // (the query-cost plan reads its keys row-block-major)
+    return s;
+}
+
 #ifdef SBO_DIAG
-    // timing diagnostic (diagnostic build only): the drop-only plan
-    // with every kept tile at level SBO_LVL_FORCE -- outside the error budget
-    if (const char *e = getenv("SBO_LVL_FORCE"); e && plan.levels) plan.levels = 2 + std::clamp(atoi(e), 0, 2);
+// The diagnostic build's environment overrides of a tick's plan,
+// applied once to the finished rule.
+void diag_skip_overrides(sbo::SkipPlan &s) {
+    // timing diagnostic: the drop-only plan with every kept tile at level
+    // SBO_LVL_FORCE -- outside the error budget
+    if (const char *e = getenv("SBO_LVL_FORCE"); e && s.levels) s.levels = 2 + std::clamp(atoi(e), 0, 2);
     // the level increments' rank keys (SkipPlan::lvl_key), "k0,k1" -- re-calibration A/B
-    if (const char *e = getenv("SBO_LVL_KEY")) (void)sscanf(e, "%f,%f", &plan.lvl_key[0], &plan.lvl_key[1]);
+    if (const char *e = getenv("SBO_LVL_KEY")) (void)sscanf(e, "%f,%f", &s.lvl_key[0], &s.lvl_key[1]);
+    // the reference plan builder: every pair's bounds evaluated in every
+    // pass, empty items' partials written and read
+    if (const char *e = getenv("SBO_PLAN_REF"); e && atoi(e)) {
+        s.colmax = nullptr;
+        s.zero_empty = true;
+        s.ref_chain = true;
+    }
+}
 #endif
-    if (ctx->query_order && plan.L > 0 && m > sbo::kBN) {
-        int32_t *p = nullptr;
+
+// The plan's first half: what the request and the context's options decide
+// before the queries are looked at.
+sbo_status tick_plan(sbo_ctx *ctx, const TickRequest &rq, TickPlan &p) {
+    const Sweep sweep = rq.sweep != Sweep::kCtx ? rq.sweep : ctx->precise ? Sweep::kPrecise : Sweep::kFast;
+    SBO_CHECK(sweep == Sweep::kFast || (ctx->has_factor && ctx->linv_n == ctx->n && ctx->inverse_bits == 64),
+              SBO_E_STATE, "precise sweep: needs the fit's f64 inverse (not an imported state, INVERSE_BITS 64)");
+    const bool full = rq.want == TickWant::kTick;
+    p.nI = ctx->npad / sbo::kBM;
+    p.P = ctx->sweep_groups > 0 ? ctx->sweep_groups : std::max(1, ctx->num_cu);
+    p.precise = sweep != Sweep::kFast;
+    p.pk = precise_kernel_traits(ctx->precise_kernel);
+    // plan only => row-block-major item order, unchunked, no counters
+    p.chunked = full && p.precise && p.pk.table;
+    p.prof = full && ctx->prof && !rq.quiet;
+    p.skip = skip_rule(ctx, sweep);
+    p.skip.order_blk = full && p.precise ? ctx->plan_block : 0;
+    // (a chunk's plan is gone by the acquisition: its empty items' partials are written)
+    p.skip.zero_empty = p.chunked;
+#ifdef SBO_DIAG
+    diag_skip_overrides(p.skip);
+#endif
+    return SBO_OK;
+}
+
+// The queries in sweep order: grid patches or Morton order (compact 128-query
+// blocks skip more k-tiles), the request's own order where it brings one.
+sbo_status tick_order_queries(sbo_ctx *ctx, const TickRequest &rq, TickPlan &p) {
+    const float *qx = rq.qx, *qy = rq.qy;
+    const int64_t m = rq.m;
+    QueryOrder o{nullptr, qx, qy};
+    int64_t ms = m;
+    if (ctx->query_order && p.skip.L > 0 && m > sbo::kBN) {
+        int32_t *perm = nullptr;
         float *sx = nullptr, *sy = nullptr;
         if (ctx->query_order == 1) {
             // a raster grid's shape, read once per query buffer (one stream
@@ -1947,179 +2048,234 @@ sbo_status run_tick(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, d
             }
         }
         if (ctx->query_order == 1 && ctx->qgrid.ok) {
-            SBO_HIP(sbo::launch_query_grid(ctx->stream, qx, qy, m, ctx->qgrid, ctx->qgwork.as<void>(), &p, &sx, &sy));
+            SBO_HIP(sbo::launch_query_grid(ctx->stream, qx, qy, m, ctx->qgrid, ctx->qgwork.as<void>(), &perm, &sx,
+                                           &sy));
+            o = QueryOrder{perm, sx, sy};
             ms = ctx->qgrid.ms;
-        } else if (order && order->perm) {
-            p = order->perm;    // (the probe's second sweep: the same queries, already ordered)
-            sx = order->sx;
-            sy = order->sy;
+        } else if (rq.order.perm) {
+            o = rq.order;    // (the probe's second sweep: the same queries, already ordered)
         } else {
             const size_t wb = sbo::query_order_bytes(m);
             SBO_HIP(ctx->qwork.reserve(wb));
-            SBO_HIP(sbo::launch_query_order(ctx->stream, qx, qy, m, ctx->bbox, ctx->qwork.as<void>(), wb, &p, &sx, &sy));
-            if (order) *order = QueryOrder{p, sx, sy};
+            SBO_HIP(sbo::launch_query_order(ctx->stream, qx, qy, m, ctx->bbox, ctx->qwork.as<void>(), wb, &perm, &sx,
+                                            &sy));
+            o = QueryOrder{perm, sx, sy};
         }
-        perm = p;
-        qx = sx;
-        qy = sy;
     }
-    const int64_t ldp = sbo::round_up(ms, 64);
-    const size_t pw = precise ? sizeof(double) : sizeof(float);   // the precise sweep's partials are f64
-    SBO_HIP(ctx->part.reserve(pw * (size_t)nI * (size_t)ldp));
-    SBO_HIP(ctx->mean.reserve(pw * (size_t)ldp));
-    const int64_t nb = sbo::acq_blocks(ms);
-    SBO_HIP(ctx->keys.reserve(sizeof(sbo_key) * (size_t)(nb + 1)));
-    sbo_key *bkeys = ctx->keys.as<sbo_key>();
-    const int P = ctx->sweep_groups > 0 ? ctx->sweep_groups : std::max(1, ctx->num_cu);
-    {
-        // the plan's tile lists and step records are sized for the dense sweep
-        // (every tile of every item) and indexed by 32-bit list positions
-        // (predict_x3.hip reads an item's first entry from desc.z alone)
-        const int64_t nQ = (ms + sbo::kBN - 1) / sbo::kBN;
-        SBO_CHECK((double)2 * nI * (nI + 1) * (double)nQ < 4294967296.0, SBO_E_INVAL,
-                  "sbo_tick: N x M too large for one tick plan (2 nI (nI + 1) nQ >= 2^32 tile entries); "
-                  "split the queries into shards");
+    p.ms = ms;
+    p.nQ = (ms + sbo::kBN - 1) / sbo::kBN;
+    p.ldp = sbo::round_up(ms, 64);
+    p.perm = o.perm;
+    p.qx = o.sx;
+    p.qy = o.sy;
+    return SBO_OK;
+}
+
+// The tick's workspaces: partials and mean, block keys, the plan.
+sbo_status tick_reserve(sbo_ctx *ctx, const TickPlan &p) {
+    const size_t pw = p.precise ? sizeof(double) : sizeof(float);   // the precise sweep's partials are f64
+    SBO_HIP(ctx->part.reserve(pw * (size_t)p.nI * (size_t)p.ldp));
+    SBO_HIP(ctx->mean.reserve(pw * (size_t)p.ldp));
+    SBO_HIP(ctx->keys.reserve(sizeof(sbo_key) * (size_t)(sbo::acq_blocks(p.ms) + 1)));
+    // the plan's tile lists and step records are sized for the dense sweep
+    // (every tile of every item) and indexed by 32-bit list positions
+    // (predict_x3.hip reads an item's first entry from desc.z alone)
+    SBO_CHECK((double)2 * p.nI * (p.nI + 1) * (double)p.nQ < 4294967296.0, SBO_E_INVAL,
+              "sbo_tick: N x M too large for one tick plan (2 nI (nI + 1) nQ >= 2^32 tile entries); "
+              "split the queries into shards");
+    SBO_HIP(ctx->plan_work.reserve(sbo::predict_work_bytes(ctx->npad, p.ms, p.P)));
+    return SBO_OK;
+}
+
+// The plan of mc sweep positions from c0 on (all of them, or one chunk), in plan_work.
+sbo_status tick_build_plan(sbo_ctx *ctx, const TickPlan &p, int64_t c0, int64_t mc) {
+    // (an f64 plan writes its empty items' outputs as doubles: SkipPlan::wide)
+    const size_t pw = p.precise ? sizeof(double) : sizeof(float);
+    SBO_HIP(sbo::launch_plan(ctx->stream, ctx->kbox.as<float4>(), ctx->npad, p.qx + c0, p.qy + c0, mc, p.ldp,
+                             (float)ctx->hyper.length_scale, (float)ctx->hyper.prior_mean, p.skip,
+                             reinterpret_cast<float *>(ctx->part.as<char>() + pw * (size_t)c0),
+                             reinterpret_cast<float *>(ctx->mean.as<char>() + pw * (size_t)c0),
+                             p.prof ? ctx->counters.as<unsigned long long>() : nullptr, p.P,
+                             ctx->plan_work.as<void>(), ctx->plan_work.capacity()));
+    return SBO_OK;
+}
+
+// sbo_query_cost: the plan's work per query, no sweep.
+sbo_status tick_cost(sbo_ctx *ctx, const TickPlan &p, float *cost) {
+    SBO_HIP(ctx->qcost.reserve(sizeof(float) * (size_t)p.nQ));
+    SBO_HIP(sbo::launch_plan_cost(ctx->stream, ctx->npad, p.ms, p.P, ctx->plan_work.as<void>(), p.perm,
+                                  ctx->qcost.as<float>(), cost));
+    return SBO_OK;
+}
+
+// The precise operand up to date on ctx->stream: the fit's pack may still be
+// running on aux_stream, and row blocks repacked since (or all of them, after
+// a change of SBO_OPT_PRECISE_KERNEL's layout) are derived from the f64 inverse.
+sbo_status precise_operand(sbo_ctx *ctx, const TickPlan &p) {
+    if (ctx->poz_pending) SBO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_poz, 0));
+    if (ctx->a64_I0 < p.nI) {
+        if (sbo_status st = pack_precise(ctx, ctx->stream, ctx->npad, std::max<int64_t>(ctx->a64_I0, 0))) return st;
+        ctx->a64_I0 = INT64_MAX;
     }
-    SBO_HIP(ctx->plan_work.reserve(sbo::predict_work_bytes(ctx->npad, ms, P)));
-    // (the K* table's precise sweep plans each chunk of query blocks itself)
-    const bool chunked = precise && ctx->precise_kernel >= 3 && ctx->precise_kernel != 9 && !cost;
-    const bool pairs = ctx->precise_kernel == 4 || ctx->precise_kernel == 10;
-    // (a chunk's plan is gone by the acquisition: its empty items' partials are written)
-    plan.zero_empty = chunked;
-#ifdef SBO_DIAG
-    // the reference plan builder (diagnostic build only): every pair's bounds
-    // evaluated in every pass, empty items' partials written and read
-    if (const char *e = getenv("SBO_PLAN_REF"); e && atoi(e)) {
-        plan.colmax = nullptr;
-        plan.zero_empty = true;
-        plan.ref_chain = true;
+    return SBO_OK;
+}
+
+// The int8 sweep over mc positions (nq query blocks) from c0 on under the plan
+// in plan_work; a chunked plan's sweep reads the K* table of those blocks in kzt.
+sbo_status launch_oz(sbo_ctx *ctx, const TickPlan &p, int64_t c0, int64_t mc, int64_t nq) {
+    const int4 *desc = nullptr;
+    const unsigned short *tl = nullptr;
+    const int *seg = nullptr;
+    sbo::plan_views(ctx->npad, mc, p.P, ctx->plan_work.as<void>(), &desc, &tl, &seg);
+    SBO_HIP(sbo::launch_predict_oz(ctx->stream, ctx->aoz.as<char>(), ctx->eoz.as<int>(), ctx->koz.as<char>(), desc,
+                                   tl, seg, p.P, (int)(p.nI * nq), (int)p.nI, p.qx + c0, p.qy + c0, mc, p.ldp,
+                                   ctx->hyper.length_scale, ctx->hyper.prior_mean, ctx->part.as<double>() + c0,
+                                   ctx->mean.as<double>() + c0, ctx->precise_kernel,
+                                   p.chunked ? ctx->kzt.as<char>() : nullptr));
+    return SBO_OK;
+}
+
+// SBO_OPT_PRECISE_KERNEL 3: the queries in chunks of Qc blocks -- each
+// chunk's plan, its K* table (every k-tile of its query blocks, once) and the
+// sweep reading it; the table is sized by SBO_OPT_TABLE_MB (2 GiB: a
+// 10^6-point grid at N = 16384 runs in 33 chunks of 244 query blocks).  An
+// item's result does not depend on the chunking (plans are per query block).
+sbo_status sweep_precise_chunked(sbo_ctx *ctx, const TickPlan &p) {
+    const size_t per_qb = sbo::oz_table_bytes(ctx->npad, p.pk.pairs);
+    size_t budget = (size_t)ctx->table_mb << 20;
+    if (budget == 0) {
+        // auto: 1/32 of the free device memory, within [256 MiB, 8 GiB]
+        // (8 GiB: 9 chunks on the lpsc grid, 1.4 % faster than 2 GiB's 33)
+        size_t fr = 0, tot = 0;
+        if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = size_t(64) << 30;
+        budget = std::clamp(fr / 32 + ctx->kzt.capacity() / 32, size_t(256) << 20, size_t(8) << 30);
     }
-#endif
-    if (!chunked)
-        SBO_HIP(sbo::launch_plan(ctx->stream, ctx->kbox.as<float4>(), ctx->npad, qx, qy, ms, ldp,
-                                 (float)ctx->hyper.length_scale, (float)ctx->hyper.prior_mean, plan,
-                                 ctx->part.as<float>(), ctx->mean.as<float>(),
-                                 ctx->prof && !cost ? ctx->counters.as<unsigned long long>() : nullptr, P,
-                                 ctx->plan_work.as<void>(), ctx->plan_work.capacity()));
-    ctx->plan_ms = chunked ? 0 : ms;
-    ctx->plan_P = P;
-    if (cost) {  // sbo_query_cost: the plan's work per query, no sweep
-        SBO_HIP(ctx->qcost.reserve(sizeof(float) * (size_t)((ms + sbo::kBN - 1) / sbo::kBN)));
-        SBO_HIP(sbo::launch_plan_cost(ctx->stream, ctx->npad, ms, P, ctx->plan_work.as<void>(), perm,
-                                      ctx->qcost.as<float>(), cost));
-        return SBO_OK;
+    const int64_t Qc = std::clamp<int64_t>((int64_t)(budget / per_qb), 1, p.nQ);
+    SBO_HIP(ctx->kzt.reserve(per_qb * (size_t)Qc));
+    Bracket br(ctx, ctx->ev_predict, p.prof);
+    for (int64_t qb0 = 0; qb0 < p.nQ; qb0 += Qc) {
+        const int64_t c0 = qb0 * sbo::kBN, mc = std::min<int64_t>(Qc * sbo::kBN, p.ms - c0);
+        const int64_t nq = std::min(Qc, p.nQ - qb0);
+        if (sbo_status st = tick_build_plan(ctx, p, c0, mc)) return st;
+        SBO_HIP(sbo::launch_kstar_table(ctx->stream, ctx->koz.as<char>(), p.qx + c0, p.qy + c0, mc, ctx->npad,
+                                        ctx->hyper.length_scale, nq, ctx->kzt.as<char>(), p.pk.pairs));
+        if (sbo_status st = launch_oz(ctx, p, c0, mc, nq)) return st;
     }
-    if (precise) {
-        // the fit's precise operand may still be packing on aux_stream
-        if (ctx->poz_pending) SBO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_poz, 0));
-        // f64 operand of any repacked row block, derived from the f64 inverse
-        const int64_t nIc = ctx->npad / sbo::kBM;
-        if (ctx->a64_I0 < nIc) {
-            if (sbo_status st = pack_precise(ctx, ctx->stream, ctx->npad, std::max<int64_t>(ctx->a64_I0, 0))) return st;
-            ctx->a64_I0 = INT64_MAX;
-        }
-        const int4 *desc = nullptr;
-        const unsigned short *tl = nullptr;
-        const int *seg = nullptr;
-        if (chunked) {
-            // SBO_OPT_PRECISE_KERNEL 3: the queries in chunks of Qc blocks --
-            // each chunk's plan, its K* table (every k-tile of its query
-            // blocks, once) and the sweep reading it; the table is sized by
-            // SBO_OPT_TABLE_MB (2 GiB: a 10^6-point grid at N = 16384 runs in
-            // 33 chunks of 244 query blocks).  An item's result does not
-            // depend on the chunking (plans are per query block).
-            const int64_t nQ = (ms + sbo::kBN - 1) / sbo::kBN;
-            const size_t per_qb = sbo::oz_table_bytes(ctx->npad, pairs);
-            size_t budget = (size_t)ctx->table_mb << 20;
-            if (budget == 0) {
-                // auto: 1/32 of the free device memory, within [256 MiB, 8 GiB]
-                // (8 GiB: 9 chunks on the lpsc grid, 1.4 % faster than 2 GiB's 33)
-                size_t fr = 0, tot = 0;
-                if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = size_t(64) << 30;
-                budget = std::clamp(fr / 32 + ctx->kzt.capacity() / 32, size_t(256) << 20, size_t(8) << 30);
-            }
-            const int64_t Qc = std::clamp<int64_t>((int64_t)(budget / per_qb), 1, nQ);
-            SBO_HIP(ctx->kzt.reserve(per_qb * (size_t)Qc));
-            double *pd = ctx->part.as<double>(), *md = ctx->mean.as<double>();
-            Bracket br(ctx, ctx->ev_predict);
-            for (int64_t qb0 = 0; qb0 < nQ; qb0 += Qc) {
-                const int64_t c0 = qb0 * sbo::kBN, mc = std::min<int64_t>(Qc * sbo::kBN, ms - c0);
-                const int64_t nq = (mc + sbo::kBN - 1) / sbo::kBN;
-                SBO_HIP(sbo::launch_plan(ctx->stream, ctx->kbox.as<float4>(), ctx->npad, qx + c0, qy + c0, mc, ldp,
-                                         (float)ctx->hyper.length_scale, (float)ctx->hyper.prior_mean, plan,
-                                         reinterpret_cast<float *>(pd + c0), reinterpret_cast<float *>(md + c0),
-                                         ctx->prof ? ctx->counters.as<unsigned long long>() : nullptr, P,
-                                         ctx->plan_work.as<void>(), ctx->plan_work.capacity()));
-                SBO_HIP(sbo::launch_kstar_table(ctx->stream, ctx->koz.as<char>(), qx + c0, qy + c0, mc, ctx->npad,
-                                                ctx->hyper.length_scale, nq, ctx->kzt.as<char>(), pairs));
-                sbo::plan_views(ctx->npad, mc, P, ctx->plan_work.as<void>(), &desc, &tl, &seg);
-                SBO_HIP(sbo::launch_predict_oz(ctx->stream, ctx->aoz.as<char>(), ctx->eoz.as<int>(),
-                                               ctx->koz.as<char>(), desc, tl, seg, P, (int)(nIc * nq), (int)nIc,
-                                               qx + c0, qy + c0, mc, ldp, ctx->hyper.length_scale,
-                                               ctx->hyper.prior_mean, pd + c0, md + c0, ctx->precise_kernel,
-                                               ctx->kzt.as<char>()));
-            }
-        } else {
-        sbo::plan_views(ctx->npad, ms, P, ctx->plan_work.as<void>(), &desc, &tl, &seg);
-        Bracket br(ctx, ctx->ev_predict);
-        if (ctx->precise_kernel >= 1)
-            SBO_HIP(sbo::launch_predict_oz(ctx->stream, ctx->aoz.as<char>(), ctx->eoz.as<int>(), ctx->koz.as<char>(),
-                                           desc, tl, seg, P, (int)(nIc * ((ms + sbo::kBN - 1) / sbo::kBN)), (int)nIc,
-                                           qx, qy, ms, ldp, ctx->hyper.length_scale, ctx->hyper.prior_mean,
-                                           ctx->part.as<double>(), ctx->mean.as<double>(), ctx->precise_kernel));
-        else
-            SBO_HIP(sbo::launch_predict_f64(ctx->stream, ctx->a64.as<double>(), ctx->kc64.as<double>(), desc, tl, seg,
-                                            P, (int)(nIc * ((ms + sbo::kBN - 1) / sbo::kBN)), (int)nIc, qx, qy, ms,
-                                            ldp, ctx->hyper.length_scale, ctx->hyper.prior_mean,
-                                            ctx->part.as<double>(), ctx->mean.as<double>()));
-        }
-    } else if (ctx->kernel_variant >= 2) {
-        // split-operand sweep: derive the bf16 planes of any repacked row
-        // block, and give the kernel whole 128-query blocks to read
-        const int64_t nIc = ctx->npad / sbo::kBM;
-        if (sbo_status st = derive_x3(ctx)) return st;
-        if (!perm) {
-            const int64_t mp = sbo::round_up(m, sbo::kBN);
-            SBO_HIP(ctx->qpad.reserve(sizeof(float) * 2 * (size_t)mp));
-            float *px = ctx->qpad.as<float>(), *py = px + mp;
-            SBO_HIP(hipMemcpyAsync(px, qx, sizeof(float) * (size_t)m, hipMemcpyDeviceToDevice, ctx->stream));
-            SBO_HIP(hipMemcpyAsync(py, qy, sizeof(float) * (size_t)m, hipMemcpyDeviceToDevice, ctx->stream));
-            qx = px;
-            qy = py;
-        }
-        const int4 *desc = nullptr;
-        const unsigned short *tl = nullptr;
-        const int *seg = nullptr;
-        const int4 *rec = nullptr;
-        sbo::plan_views(ctx->npad, ms, P, ctx->plan_work.as<void>(), &desc, &tl, &seg, &rec);
-        Bracket br(ctx, ctx->ev_predict);
-        SBO_HIP(sbo::launch_predict_x3(ctx->stream, ctx->ax3.as<char>(), ctx->kc3.as<float>(), desc, rec, seg, P,
-                                       (int)(nIc * ((ms + sbo::kBN - 1) / sbo::kBN)), (int)nIc, qx, qy, ms, ldp,
-                                       sbo::exp2_coef_f((float)ctx->hyper.length_scale),
-                                       (float)ctx->hyper.prior_mean, ctx->part.as<float>(), ctx->mean.as<float>(),
-                                       ctx->kernel_variant));
-    } else {
-        Bracket br(ctx, ctx->ev_predict);
-        SBO_HIP(sbo::launch_predict(ctx->stream, ctx->aug.as<float>(), ctx->kcoord.as<float>(), ctx->npad, qx, qy,
-                                    ms, ldp, (float)ctx->hyper.length_scale, (float)ctx->hyper.prior_mean,
-                                    ctx->part.as<float>(), ctx->mean.as<float>(), ctx->kernel_variant, P,
-                                    ctx->plan_work.as<void>()));
+    return SBO_OK;
+}
+
+// The precise sweep over the whole plan: the int8 sliced kernel or the f64 one.
+sbo_status sweep_precise(sbo_ctx *ctx, const TickPlan &p) {
+    Bracket br(ctx, ctx->ev_predict, p.prof);
+    if (p.pk.int8) return launch_oz(ctx, p, 0, p.ms, p.nQ);
+    const int4 *desc = nullptr;
+    const unsigned short *tl = nullptr;
+    const int *seg = nullptr;
+    sbo::plan_views(ctx->npad, p.ms, p.P, ctx->plan_work.as<void>(), &desc, &tl, &seg);
+    SBO_HIP(sbo::launch_predict_f64(ctx->stream, ctx->a64.as<double>(), ctx->kc64.as<double>(), desc, tl, seg, p.P,
+                                    (int)(p.nI * p.nQ), (int)p.nI, p.qx, p.qy, p.ms, p.ldp, ctx->hyper.length_scale,
+                                    ctx->hyper.prior_mean, ctx->part.as<double>(), ctx->mean.as<double>()));
+    return SBO_OK;
+}
+
+// The split-operand sweep: derive the bf16 planes of any repacked row block,
+// and give the kernel whole 128-query blocks to read (m: the caller's queries).
+sbo_status sweep_fast_x3(sbo_ctx *ctx, const TickPlan &p, int64_t m) {
+    if (sbo_status st = derive_x3(ctx)) return st;
+    const float *qx = p.qx, *qy = p.qy;
+    if (!p.perm) {
+        const int64_t mp = sbo::round_up(m, sbo::kBN);
+        SBO_HIP(ctx->qpad.reserve(sizeof(float) * 2 * (size_t)mp));
+        float *px = ctx->qpad.as<float>(), *py = px + mp;
+        SBO_HIP(hipMemcpyAsync(px, qx, sizeof(float) * (size_t)m, hipMemcpyDeviceToDevice, ctx->stream));
+        SBO_HIP(hipMemcpyAsync(py, qy, sizeof(float) * (size_t)m, hipMemcpyDeviceToDevice, ctx->stream));
+        qx = px;
+        qy = py;
     }
+    const int4 *desc = nullptr;
+    const unsigned short *tl = nullptr;
+    const int *seg = nullptr;
+    const int4 *rec = nullptr;
+    sbo::plan_views(ctx->npad, p.ms, p.P, ctx->plan_work.as<void>(), &desc, &tl, &seg, &rec);
+    Bracket br(ctx, ctx->ev_predict, p.prof);
+    SBO_HIP(sbo::launch_predict_x3(ctx->stream, ctx->ax3.as<char>(), ctx->kc3.as<float>(), desc, rec, seg, p.P,
+                                   (int)(p.nI * p.nQ), (int)p.nI, qx, qy, p.ms, p.ldp,
+                                   sbo::exp2_coef_f((float)ctx->hyper.length_scale), (float)ctx->hyper.prior_mean,
+                                   ctx->part.as<float>(), ctx->mean.as<float>(), ctx->kernel_variant));
+    return SBO_OK;
+}
+
+sbo_status sweep_fast_f32(sbo_ctx *ctx, const TickPlan &p) {
+    Bracket br(ctx, ctx->ev_predict, p.prof);
+    SBO_HIP(sbo::launch_predict(ctx->stream, ctx->aug.as<float>(), ctx->kcoord.as<float>(), ctx->npad, p.qx, p.qy,
+                                p.ms, p.ldp, (float)ctx->hyper.length_scale, (float)ctx->hyper.prior_mean,
+                                ctx->part.as<float>(), ctx->mean.as<float>(), ctx->kernel_variant, p.P,
+                                ctx->plan_work.as<void>()));
+    return SBO_OK;
+}
+
+// The acquisition over the partials and the key reduction.  The plan's
+// non-empty view only where the plan outlives the sweep (SkipPlan::zero_empty).
+sbo_status tick_acquire(sbo_ctx *ctx, const TickRequest &rq, const TickPlan &p) {
     const unsigned long long *pkey = nullptr, *pscan = nullptr, *nonempty = nullptr;
     const unsigned char *pthr = nullptr;
-    if (!plan.zero_empty)
-        sbo::plan_item_views(ctx->npad, ms, P, ctx->plan_work.as<void>(), &pkey, &pscan, &pthr, &nonempty);
-    if (precise) {
-        SBO_HIP(sbo::launch_acquire(ctx->stream, ctx->part.as<double>(), ctx->mean.as<double>(), (int)nI, ldp, ms,
-                                    ctx->hyper.sigma_f * ctx->hyper.sigma_f, beta, f_min, score_kind, index_offset,
-                                    perm, mu, sd, lo, hi, safe, bkeys, nonempty));
+    if (!p.skip.zero_empty)
+        sbo::plan_item_views(ctx->npad, p.ms, p.P, ctx->plan_work.as<void>(), &pkey, &pscan, &pthr, &nonempty);
+    const int64_t nb = sbo::acq_blocks(p.ms);
+    sbo_key *bkeys = ctx->keys.as<sbo_key>();
+    const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
+    if (p.precise)
+        SBO_HIP(sbo::launch_acquire(ctx->stream, ctx->part.as<double>(), ctx->mean.as<double>(), (int)p.nI, p.ldp,
+                                    p.ms, sf2, rq.beta, rq.f_min, rq.score, rq.index_offset, p.perm, rq.mu, rq.sd,
+                                    rq.lo, rq.hi, rq.safe, bkeys, nonempty));
+    else
+        SBO_HIP(sbo::launch_acquire(ctx->stream, ctx->part.as<float>(), ctx->mean.as<float>(), (int)p.nI, p.ldp,
+                                    p.ms, (float)sf2, rq.beta, rq.f_min, rq.score, rq.index_offset, p.perm, rq.mu,
+                                    rq.sd, rq.lo, rq.hi, rq.safe, bkeys, nonempty));
+    SBO_HIP(sbo::launch_reduce_keys(ctx->stream, bkeys, nb, rq.key ? rq.key : bkeys + nb));
+    return SBO_OK;
+}
+
+// Plan, sweep and acquisition over queries already on the device (or the
+// plan alone, or the plan and its cost: TickWant); plan_out, where given,
+// receives the plan as built (plan_views / plan_item_views of ms and P on
+// plan_work read an unchunked one).
+sbo_status run_tick(sbo_ctx *ctx, const TickRequest &rq, TickPlan *plan_out) {
+    TickPlan p;
+    if (sbo_status st = tick_plan(ctx, rq, p)) return st;
+    if (sbo_status st = tick_order_queries(ctx, rq, p)) return st;
+    if (sbo_status st = tick_reserve(ctx, p)) return st;
+    // (the K* table's precise sweep plans each chunk of query blocks itself)
+    if (!p.chunked)
+        if (sbo_status st = tick_build_plan(ctx, p, 0, p.ms)) return st;
+    if (plan_out) *plan_out = p;
+    if (rq.want == TickWant::kPlan) return SBO_OK;
+    if (rq.want == TickWant::kCost) return tick_cost(ctx, p, rq.cost);
+    sbo_status st;
+    if (p.precise) {
+        st = precise_operand(ctx, p);
+        if (st == SBO_OK) st = p.chunked ? sweep_precise_chunked(ctx, p) : sweep_precise(ctx, p);
+    } else if (ctx->kernel_variant >= 2) {
+        st = sweep_fast_x3(ctx, p, rq.m);
     } else {
-        const float sf2 = (float)(ctx->hyper.sigma_f * ctx->hyper.sigma_f);
-        SBO_HIP(sbo::launch_acquire(ctx->stream, ctx->part.as<float>(), ctx->mean.as<float>(), (int)nI, ldp, ms, sf2,
-                                    beta, f_min, score_kind, index_offset, perm, mu, sd, lo, hi, safe, bkeys,
-                                    nonempty));
+        st = sweep_fast_f32(ctx, p);
     }
-    SBO_HIP(sbo::launch_reduce_keys(ctx->stream, bkeys, nb, key_dev ? key_dev : bkeys + nb));
+    if (st != SBO_OK) return st;
+    return tick_acquire(ctx, rq, p);
+}
+
+// Host queries staged for a tick: hq sized for them and `rest` more bytes,
+// the two coordinate arrays carved first and copied over on ctx->stream; the
+// caller carves its outputs from c.
+sbo_status stage_queries(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, size_t rest, TickRequest &rq,
+                         Carve &c) {
+    SBO_HIP(ctx->hq.reserve(Carve::need(m, 4) * 2 + rest));
+    c = Carve(ctx->hq.as<void>());
+    float *dqx = c.take<float>(m), *dqy = c.take<float>(m);
+    SBO_HIP(hipMemcpyAsync(dqx, qx, sizeof(float) * m, hipMemcpyHostToDevice, ctx->stream));
+    SBO_HIP(hipMemcpyAsync(dqy, qy, sizeof(float) * m, hipMemcpyHostToDevice, ctx->stream));
+    rq.qx = dqx;
+    rq.qy = dqy;
     return SBO_OK;
 }
 
@@ -2478,22 +2634,21 @@ SBO_API sbo_status sbo_query_cost(sbo_ctx *ctx, const float *qx, const float *qy
     SBO_CHECK(qx && qy && cost, SBO_E_INVAL, "sbo_query_cost: null pointer");
     SBO_CHECK(m > 0, SBO_E_EMPTY, "sbo_query_cost: m must be > 0");
     SBO_HIP(hipSetDevice(ctx->device));
+    TickRequest rq;
+    rq.m = m;
+    rq.want = TickWant::kCost;
     if (dev(flags)) {
-        if (sbo_status st = run_tick(ctx, qx, qy, m, 0.0, 0.0, SBO_SCORE_WIDTH, 0, nullptr, nullptr, nullptr,
-                                     nullptr, nullptr, nullptr, cost))
-            return st;
+        rq.qx = qx;
+        rq.qy = qy;
+        rq.cost = cost;
+        if (sbo_status st = run_tick(ctx, rq)) return st;
         return finish(ctx, flags);
     }
-    const size_t need = Carve::need(m, 4) * 3;
-    SBO_HIP(ctx->hq.reserve(need));
-    Carve c(ctx->hq.as<void>());
-    float *dqx = c.take<float>(m), *dqy = c.take<float>(m), *dc = c.take<float>(m);
-    SBO_HIP(hipMemcpyAsync(dqx, qx, sizeof(float) * m, hipMemcpyHostToDevice, ctx->stream));
-    SBO_HIP(hipMemcpyAsync(dqy, qy, sizeof(float) * m, hipMemcpyHostToDevice, ctx->stream));
-    if (sbo_status st = run_tick(ctx, dqx, dqy, m, 0.0, 0.0, SBO_SCORE_WIDTH, 0, nullptr, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr, dc))
-        return st;
-    SBO_HIP(hipMemcpyAsync(cost, dc, sizeof(float) * m, hipMemcpyDeviceToHost, ctx->stream));
+    Carve c;
+    if (sbo_status st = stage_queries(ctx, qx, qy, m, Carve::need(m, 4), rq, c)) return st;
+    rq.cost = c.take<float>(m);
+    if (sbo_status st = run_tick(ctx, rq)) return st;
+    SBO_HIP(hipMemcpyAsync(cost, rq.cost, sizeof(float) * m, hipMemcpyDeviceToHost, ctx->stream));
     SBO_HIP(hipStreamSynchronize(ctx->stream));
     return SBO_OK;
 }
@@ -2508,26 +2663,42 @@ SBO_API sbo_status sbo_tick(sbo_ctx *ctx, const float *qx, const float *qy, int6
     SBO_CHECK(score == SBO_SCORE_WIDTH || score == SBO_SCORE_UCB, SBO_E_INVAL, "sbo_tick: bad score kind");
     SBO_CHECK(std::isfinite(beta) && !std::isnan(f_min), SBO_E_INVAL, "sbo_tick: beta/f_min must be finite");
     SBO_HIP(hipSetDevice(ctx->device));
+    TickRequest rq;
+    rq.m = m;
+    rq.beta = beta;
+    rq.f_min = f_min;
+    rq.score = (int)score;
+    rq.index_offset = index_offset;
     if (dev(flags)) {
-        if (sbo_status st = run_tick(ctx, qx, qy, m, beta, f_min, (int)score, index_offset, mu, sd, lo, hi, safe,
-                                     out))
-            return st;
+        rq.qx = qx;
+        rq.qy = qy;
+        rq.mu = mu;
+        rq.sd = sd;
+        rq.lo = lo;
+        rq.hi = hi;
+        rq.safe = safe;
+        rq.key = out;
+        if (sbo_status st = run_tick(ctx, rq)) return st;
         return finish(ctx, flags);
     }
     // host pointers: stage through device scratch
-    const size_t need = Carve::need(m, 4) * 4 + Carve::need(m, 8) * 2 + Carve::need(m, 1) + Carve::need(1, sizeof(sbo_key));
-    SBO_HIP(ctx->hq.reserve(need));
-    Carve c(ctx->hq.as<void>());
-    float *dqx = c.take<float>(m), *dqy = c.take<float>(m), *dmu = c.take<float>(m), *dsd = c.take<float>(m);
+    Carve c;
+    if (sbo_status st = stage_queries(ctx, qx, qy, m,
+                                      Carve::need(m, 4) * 2 + Carve::need(m, 8) * 2 + Carve::need(m, 1) +
+                                          Carve::need(1, sizeof(sbo_key)),
+                                      rq, c))
+        return st;
+    float *dmu = c.take<float>(m), *dsd = c.take<float>(m);
     double *dlo = c.take<double>(m), *dhi = c.take<double>(m);
     uint8_t *dsafe = c.take<uint8_t>(m);
     sbo_key *dkey = c.take<sbo_key>(1);
-    SBO_HIP(hipMemcpyAsync(dqx, qx, sizeof(float) * m, hipMemcpyHostToDevice, ctx->stream));
-    SBO_HIP(hipMemcpyAsync(dqy, qy, sizeof(float) * m, hipMemcpyHostToDevice, ctx->stream));
-    if (sbo_status st = run_tick(ctx, dqx, dqy, m, beta, f_min, (int)score, index_offset, mu ? dmu : nullptr,
-                                 sd ? dsd : nullptr, lo ? dlo : nullptr, hi ? dhi : nullptr,
-                                 safe ? dsafe : nullptr, dkey))
-        return st;
+    rq.mu = mu ? dmu : nullptr;
+    rq.sd = sd ? dsd : nullptr;
+    rq.lo = lo ? dlo : nullptr;
+    rq.hi = hi ? dhi : nullptr;
+    rq.safe = safe ? dsafe : nullptr;
+    rq.key = dkey;
+    if (sbo_status st = run_tick(ctx, rq)) return st;
     if (mu) SBO_HIP(hipMemcpyAsync(mu, dmu, sizeof(float) * m, hipMemcpyDeviceToHost, ctx->stream));
     if (sd) SBO_HIP(hipMemcpyAsync(sd, dsd, sizeof(float) * m, hipMemcpyDeviceToHost, ctx->stream));
     if (lo) SBO_HIP(hipMemcpyAsync(lo, dlo, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->stream));
@@ -2718,23 +2889,21 @@ SBO_API sbo_status sbo_debug_plan(sbo_ctx *ctx, const float *qx, const float *qy
     SBO_CHECK(m > 0, SBO_E_EMPTY, "sbo_debug_plan: m must be > 0");
     SBO_HIP(hipSetDevice(ctx->device));
     // the plan sbo_query_cost builds (no sweep), then its items and lists read back
-    SBO_HIP(ctx->hq.reserve(Carve::need(m, 4) * 3));
-    Carve c(ctx->hq.as<void>());
-    float *dqx = c.take<float>(m), *dqy = c.take<float>(m), *dc = c.take<float>(m);
-    SBO_HIP(hipMemcpyAsync(dqx, qx, sizeof(float) * m, hipMemcpyHostToDevice, ctx->stream));
-    SBO_HIP(hipMemcpyAsync(dqy, qy, sizeof(float) * m, hipMemcpyHostToDevice, ctx->stream));
-    if (sbo_status st = run_tick(ctx, dqx, dqy, m, 0.0, 0.0, SBO_SCORE_WIDTH, 0, nullptr, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr, dc))
-        return st;
-    const int64_t nI = ctx->npad / sbo::kBM, ms = ctx->plan_ms, nQ = (ms + sbo::kBN - 1) / sbo::kBN;
-    const int64_t items = nI * nQ;
+    TickRequest rq;
+    rq.m = m;
+    rq.want = TickWant::kPlan;
+    Carve c;
+    if (sbo_status st = stage_queries(ctx, qx, qy, m, 0, rq, c)) return st;
+    TickPlan p;
+    if (sbo_status st = run_tick(ctx, rq, &p)) return st;
+    const int64_t nI = p.nI, nQ = p.nQ, items = nI * nQ;
     const unsigned long long *key = nullptr, *scan = nullptr;
     const unsigned char *thr = nullptr;
     const int4 *desc = nullptr;
     const unsigned short *tl = nullptr;
     const int *seg = nullptr;
-    sbo::plan_item_views(ctx->npad, ms, ctx->plan_P, ctx->plan_work.as<void>(), &key, &scan, &thr);
-    sbo::plan_views(ctx->npad, ms, ctx->plan_P, ctx->plan_work.as<void>(), &desc, &tl, &seg);
+    sbo::plan_item_views(ctx->npad, p.ms, p.P, ctx->plan_work.as<void>(), &key, &scan, &thr);
+    sbo::plan_views(ctx->npad, p.ms, p.P, ctx->plan_work.as<void>(), &desc, &tl, &seg);
     std::vector<unsigned long long> hkey((size_t)items);
     std::vector<unsigned char> hthr((size_t)items);
     unsigned long long last = 0;
@@ -2989,11 +3158,9 @@ SBO_API sbo_status sbo_set_option(sbo_ctx *ctx, int option, int64_t value) {
                       "SBO_OPT_PRECISE_KERNEL must be 0 (f64 MFMA), 1 (int8), 3 (int8, K* table) or 4 (int8, "
                       "k-tile pairs)");
 #endif
-            {
-                // the operand layout each kernel reads: f64 tiles, int8 tiles, int8 pairs
-                auto layout = [](int64_t k) { return k == 0 ? 0 : (k == 4 || k == 10) ? 2 : 1; };
-                if (layout(ctx->precise_kernel) != layout(value)) ctx->a64_I0 = 0;   // derive it all
-            }
+            // another operand layout: derive it all
+            if (precise_kernel_traits(ctx->precise_kernel).layout != precise_kernel_traits((int)value).layout)
+                ctx->a64_I0 = 0;
             ctx->precise_kernel = (int)value;
             return SBO_OK;
         case SBO_OPT_INV_OZ:

@@ -180,8 +180,6 @@ struct sbo_ctx {
     int sweep_groups = 0;        // SBO_OPT_SWEEP_GROUPS: persistent sweep workgroups (0: one per CU)
     int num_cu = 0;              // compute units of the device
     sbo::DevBuf plan_work;       // the tick's tile plan (launch_plan)
-    int64_t plan_ms = 0;         // sweep positions and workgroups of the unchunked plan last built there
-    int plan_P = 0;              // (sbo_debug_plan)
     sbo::DevBuf fwork, fowner, fimg, fpix, fout;  // device frontier (sbo_frontier / sbo_subgoal)
     sbo::DevBuf qwork;           // query ordering workspace
     sbo::DevBuf kbox;            // per k-tile bounding boxes (float4)
