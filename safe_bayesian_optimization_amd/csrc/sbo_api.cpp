@@ -238,13 +238,23 @@ void record_inv_digits(sbo_ctx *ctx, const sbo_inv_check &r) {
     ctx->inv_oz_next = nd;
 }
 
+// Has a blocked factorization run on this context?  Its set-up (chol_streams)
+// leaves aux_stream, its rocBLAS handle and the events ev_panel, ev_trail,
+// ev_pack, ev_poz, which the inverse's two-stream top level and the refresh's
+// side work use without making them.  The four events are created together,
+// so ev_panel stands for all of them.  The answer depends on history, not on
+// the options now: a context whose fits so far all ran rocSOLVER's spotrf
+// (SBO_OPT_CHOLESKY 0) has no aux stream and its refresh stays single-stream;
+// one that has run the blocked factorization once keeps it.
+bool aux_ready(const sbo_ctx *ctx) { return ctx->blas_aux && ctx->aux_stream && ctx->ev_panel; }
+
 // does the recursive inverse of n columns slice any of its products?  The
 // same gate as inverse_lower_f64_par's: the sliced GEMM's workspaces are handed
 // down only when the top split slices (the levels below slice with them
 // where oz_level allows; with the top split over 16384 it is all dgemm), and
 // only on the two-stream path.
 bool inverse_sliced(const sbo_ctx *ctx, int digits, int64_t n) {
-    if (n <= ctx->inv_base || !ctx->blas_aux || !ctx->aux_stream || !ctx->ev_panel) return false;
+    if (n <= ctx->inv_base || !aux_ready(ctx)) return false;
     const int64_t h = inverse_split(n, ctx->inv_base);
     return oz_level(ctx, digits, h, n - h);
 }
@@ -426,7 +436,7 @@ sbo_status inverse_leaves(sbo_ctx *ctx, rocblas_handle hb, double *Li, int64_t n
 // decides it once).
 sbo_status inverse_lower_f64_par(sbo_ctx *ctx, double *Li, int64_t n, int64_t ld, double *S, InvMode mode) {
     int slot = 0;
-    if (n <= ctx->inv_base || !ctx->blas_aux || !ctx->aux_stream || !ctx->ev_panel)
+    if (n <= ctx->inv_base || !aux_ready(ctx))
         return inverse_lower_f64(ctx, ctx->blas, Li, n, ld, S, slot, mode);
     const int64_t h = inverse_split(n, ctx->inv_base), m = n - h;
     double *scrA = S + h * m, *scrC = scrA + inverse_scratch(h, ctx->inv_base);
@@ -973,6 +983,7 @@ struct FactorHandover {
     int64_t widened_n = 0;   // the factor (n columns) is already widened into Linv
     int64_t half_n = 0;      // n of a factor whose inverse's first half is done (inverse_finish_half ends it)
     int half_slots = 0;      // the info slots that half used (1 .. half_slots)
+    rocblas_int *info = nullptr;   // the info slots the factorization wrote (slot 0: the leading minor)
 };
 
 // The guard's ladder (refresh_operand): the digits chosen for this fit, then
@@ -1020,7 +1031,7 @@ RefreshPlan plan_refresh(const sbo_ctx *ctx, int64_t n_old, const FactorHandover
     p.guard = p.f64 && !p.incr &&
               (ctx->inv_check == 2 || attempt == kInvDgemm || (ctx->inv_check == 1 && sliced));
     p.inc_alpha = p.incr && ctx->z_n == n_old && p.n - n_old <= kAppendInvGemm;
-    p.aux = p.f64 && ctx->blas_aux && ctx->aux_stream && ctx->ev_panel && ctx->ev_pack;
+    p.aux = p.f64 && aux_ready(ctx);
     p.eager_x3 = p.aux && ctx->kernel_variant >= 2;
     p.eager_f64 =
         p.aux && ctx->precision_opt != 0 && (probe_due(ctx) || ctx->precise || ctx->precision_opt == 1);
@@ -1616,323 +1627,429 @@ sbo_status probe_precision(sbo_ctx *ctx) {
     return SBO_OK;
 }
 
-// Factor K in L (already filled, lda = cap) and refresh the operand.
-// Right-looking blocked Cholesky of the n x n lower triangle at L (lda = ld)
-// in steps of kCholNB columns: the diagonal block in one workgroup
-// (chol_diag_kernel), the panel below it by rocBLAS strsm (L21 = A21 L11^-T),
-// the trailing update A22 -= L21 L21^T -- the same factorization as spotrf,
-// without its unblocked potf2 panels (which were 23 % of a C4 fit).  With
-// look-ahead: the trailing update is split into the next block column (an
-// sgemm on `stream`, followed at once by the next diagonal block and panel)
-// and the rest (ssyrk on aux_stream), so the one-CU diagonal kernel runs
-// beside the big update instead of between updates.  Event order: the rest
-// of step k waits for step k's panel; the next block column of step k + 1
-// waits for the rest of step k (which also wrote that column).  info:
-// rocSOLVER's.
+// ---- the blocked Cholesky (SBO_OPT_CHOLESKY 1 / 2) ----
 //
-// early_inv (a fit with the recursive f64 inverse and SBO_OPT_INV_OVERLAP =
-// R > 0): once the panel of the block column that ends at h =
-// inverse_split(n, inv_base) is done, the factor's left h columns are final, and the
-// inverse's first half (widen them, A^-1, S = B A^-1: half its flops) runs on
-// inv_stream with its own rocBLAS handle beside the Cholesky's last steps,
-// which leave most CUs idle (one-workgroup diagonal blocks, small trailing
-// updates).  inv_stream is CU-masked to leave R CUs to the chain, whose
-// kernels would otherwise queue behind the long dgemm workgroups.
-// refresh_operand finishes the inverse.  *out (may be null): what was handed
-// over -- the widened factor, the first half and its info slots.
-sbo_status blocked_potrf(sbo_ctx *ctx, float *L, int64_t n, int64_t ld, rocblas_int *info, bool early_inv = false,
-                         FactorHandover *out = nullptr) {
-    FactorHandover ho;
-    SBO_HIP(hipMemsetAsync(info, 0, sizeof(rocblas_int), ctx->stream));
-    const bool early = early_inv && ctx->inv_overlap > 0 && n > ctx->inv_base;
-    const int64_t h_inv = early ? inverse_split(n, ctx->inv_base) : -1;
-    bool early_pending = false;
-    if (early) {
-        if (ctx->inv_stream && ctx->inv_reserved != ctx->inv_overlap) {
-            SBO_HIP(hipStreamSynchronize(ctx->inv_stream));
-            SBO_HIP(hipStreamDestroy(ctx->inv_stream));
-            ctx->inv_stream = nullptr;
-        }
-        if (!ctx->inv_stream) {
+// Everything one factorization decides, once, before its first launch
+// (chol_plan): the stages below read it and none of them looks the conditions
+// up again.  SBO_OPT_CHOL_GEMM and SBO_OPT_CHOLESKY are decoded here only.
+struct CholPlan {
+    int64_t n, ld;       // the n x n lower triangle, leading dimension ld
+    int64_t NB, NB2;     // the chain's block (kCholNB) and the outer panel (SBO_OPT_CHOL_OUTER; NB: one level)
+    // SBO_OPT_CHOL_GEMM 0 rocBLAS; 1 chol_update_kernel for trailing updates of
+    // at most 8192 rows (where it measured faster than rocBLAS); 2 for every
+    // update; 3 the outer panel split into bf16 planes; 4 / 5 the outer
+    // panel's updates as the int8-sliced GEMM with that many digits
+    enum Update { kRocblas, kOwnSmall, kOwn, kX3, kOz } update;
+    int oz_digits;       // kOz: 4 or 5
+    int chain;           // SBO_OPT_CHOL_DIAG: the version of the chain's two kernels
+    bool own_trsm;       // the panel solve by chol_trsm_kernel (SBO_OPT_CHOLESKY 1), else rocBLAS strsm (2)
+    bool early;          // the inverse's first half runs beside the last steps (SBO_OPT_INV_OVERLAP) ...
+    int64_t h_inv;       // ... once the factor's left h_inv columns are final (-1: never)
+    bool widen;          // the f64 copy of the factor is written panel by panel into Linv
+    rocblas_int *info;   // rocSOLVER-style info: slot 0 the leading minor, with `early` the first half's after it
+    int64_t info_slots;
+};
+
+// Which of the three updates of a step chol_update runs.  The inner update (the
+// outer panel's remaining columns, after each 128-column block) never reads
+// the packed panel; only the trailing update (everything right of the next
+// outer panel) writes the lower triangle alone, and only it has the size rules
+// of kOwnSmall and kSmallTrail.
+enum class UpdateSite { kInner, kLookahead, kTrailing };
+
+// Below this size the trailing update is one sgemm over the full square
+// (rocBLAS ssyrk: 82 vs 49 us at m = 4000, 67 vs 20 at 2000, k = 128;
+// tools/r3_gemm_probe.cpp); the upper triangle it also writes is never read.
+constexpr int64_t kSmallTrail = 6144;
+
+// The outer panel's rows below it (m3 x W), packed once per outer step for the
+// look-ahead and the trailing update (chol_pack_panel): int8 digits (kOz, W a
+// multiple of 64 and the next panel's width W2 of 128; the last panels are
+// rocBLAS's) or bf16 planes (kX3, W a multiple of 32).  Two buffers alternate
+// across steps: the trailing update on aux_stream may still read the previous
+// one until the next look-ahead has waited for it.
+struct PanelPack {
+    bool oz = false, x3 = false;
+    int buffer = 0;                // which of ctx->cholx3
+    const char *planes = nullptr;
+};
+
+// Failures of the launched stages carry no text of their own: blocked_potrf
+// gives them one (the set-up stages keep SBO_HIP's, which names the call and
+// tells out-of-memory apart).
+#define CHOL_HIP(expr)                               \
+    do {                                             \
+        if ((expr) != hipSuccess) return SBO_E_DEVICE; \
+    } while (0)
+#define CHOL_BLAS(expr)                                           \
+    do {                                                          \
+        if ((expr) != rocblas_status_success) return SBO_E_DEVICE; \
+    } while (0)
+
+// The plan, and the info slots it points at (sized here, so that the pointer
+// is final before the first launch).
+sbo_status chol_plan(sbo_ctx *ctx, int64_t n, int64_t ld, bool early_inv, CholPlan &p) {
+    p.n = n;
+    p.ld = ld;
+    p.NB = sbo::kCholNB;
+    p.NB2 = std::max<int64_t>(p.NB, (int64_t)ctx->chol_outer / p.NB * p.NB);
+    const int g = ctx->chol_gemm_own;
+    p.update = g == 1   ? CholPlan::kOwnSmall
+               : g == 2 ? CholPlan::kOwn
+               : g == 3 ? CholPlan::kX3
+               : g >= 4 ? CholPlan::kOz
+                        : CholPlan::kRocblas;
+    p.oz_digits = p.update == CholPlan::kOz ? g : 0;
+    p.chain = ctx->chol_diag;
+    p.own_trsm = ctx->chol_trsm_own;
+    // early_inv: a fit with the recursive f64 inverse.  Its first half beside
+    // the Cholesky with SBO_OPT_INV_OVERLAP = R > 0; otherwise the factor is
+    // widened for it on the way.
+    p.early = early_inv && ctx->inv_overlap > 0 && n > ctx->inv_base;
+    p.h_inv = p.early ? inverse_split(n, ctx->inv_base) : -1;
+    p.widen = early_inv && !p.early;
+    p.info_slots = p.early ? info_slots(n) : 1;
+    SBO_HIP(ctx->info.reserve(sizeof(rocblas_int) * (size_t)p.info_slots));
+    p.info = ctx->info.as<rocblas_int>();
+    return SBO_OK;
+}
+
+// *s, with the rocBLAS handle *hb bound to it: a stream that stays off the
+// first `reserve` CUs (0: an ordinary non-blocking stream), made on first use
+// and made again when the mask changed.
+sbo_status forked_stream(sbo_ctx *ctx, hipStream_t *s, rocblas_handle *hb, int *reserved, int reserve) {
+    if (*s && *reserved != reserve) {
+        SBO_HIP(hipStreamSynchronize(*s));
+        SBO_HIP(hipStreamDestroy(*s));
+        *s = nullptr;
+    }
+    if (*s && *hb) return SBO_OK;
+    if (!*s) {
+        if (reserve > 0) {
             std::vector<uint32_t> mask((size_t)(ctx->num_cu + 31) / 32, 0u);
-            for (int c = ctx->inv_overlap; c < ctx->num_cu; ++c) mask[(size_t)c / 32] |= 1u << (c % 32);
-            SBO_HIP(hipExtStreamCreateWithCUMask(&ctx->inv_stream, (uint32_t)mask.size(), mask.data()));
-            ctx->inv_reserved = ctx->inv_overlap;
-            if (ctx->blas_inv) SBO_BLAS(rocblas_set_stream(ctx->blas_inv, ctx->inv_stream));
+            for (int c = reserve; c < ctx->num_cu; ++c) mask[(size_t)c / 32] |= 1u << (c % 32);
+            SBO_HIP(hipExtStreamCreateWithCUMask(s, (uint32_t)mask.size(), mask.data()));
+        } else {
+            SBO_HIP(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
         }
+        *reserved = reserve;
+    }
+    if (!*hb) SBO_BLAS(rocblas_create_handle(hb));
+    SBO_BLAS(rocblas_set_stream(*hb, *s));
+    return SBO_OK;
+}
+
+// The lazy set-up: aux_stream for the trailing updates, off the first
+// SBO_OPT_CHOL_RESERVE CUs so that the latency-bound chain finds them free,
+// and for an early half inv_stream, which leaves SBO_OPT_INV_OVERLAP CUs to
+// the chain (its kernels would otherwise queue behind the long dgemm
+// workgroups); each with its handle and its events.  aux_ready() is true from
+// here on.
+sbo_status chol_streams(sbo_ctx *ctx, const CholPlan &p) {
+    if (p.early) {
+        if (sbo_status st = forked_stream(ctx, &ctx->inv_stream, &ctx->blas_inv, &ctx->inv_reserved, ctx->inv_overlap))
+            return st;
         if (!ctx->ev_half) {
             SBO_HIP(hipEventCreateWithFlags(&ctx->ev_half, hipEventDisableTiming));
             SBO_HIP(hipEventCreateWithFlags(&ctx->ev_inv, hipEventDisableTiming));
         }
-        if (!ctx->blas_inv) {
-            SBO_BLAS(rocblas_create_handle(&ctx->blas_inv));
-            SBO_BLAS(rocblas_set_stream(ctx->blas_inv, ctx->inv_stream));
-        }
-        // every buffer the first half touches, sized before it starts (a
-        // reserve that reallocates later would free memory in use)
-        SBO_HIP(ctx->Linv.reserve(sizeof(double) * (size_t)ld * (size_t)ld));
-        SBO_HIP(ctx->scratch.reserve(sizeof(double) * (size_t)std::max<int64_t>(inverse_scratch(n, ctx->inv_base), 1)));
-        const int64_t nslots = info_slots(n);
-        SBO_HIP(ctx->info.reserve(sizeof(rocblas_int) * (size_t)nslots));
-        info = ctx->info.as<rocblas_int>();
-        SBO_HIP(hipMemsetAsync(info, 0, sizeof(rocblas_int) * (size_t)nslots, ctx->stream));
     }
-    SBO_BLAS(rocblas_set_pointer_mode(ctx->blas, rocblas_pointer_mode_host));
-    if (ctx->aux_stream && ctx->aux_reserved != ctx->chol_reserve) {  // another CU mask: a new aux stream
-        SBO_HIP(hipStreamSynchronize(ctx->aux_stream));
-        SBO_HIP(hipStreamDestroy(ctx->aux_stream));
-        ctx->aux_stream = nullptr;
-    }
-    if (!ctx->aux_stream) {
-        if (ctx->chol_reserve > 0) {
-            // the trailing updates stay off the first chol_reserve CUs, so the
-            // latency-bound chain (diagonal block, panel) finds them free
-            std::vector<uint32_t> mask((size_t)(ctx->num_cu + 31) / 32, 0u);
-            for (int c = ctx->chol_reserve; c < ctx->num_cu; ++c) mask[(size_t)c / 32] |= 1u << (c % 32);
-            SBO_HIP(hipExtStreamCreateWithCUMask(&ctx->aux_stream, (uint32_t)mask.size(), mask.data()));
-        } else {
-            SBO_HIP(hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
-        }
-        ctx->aux_reserved = ctx->chol_reserve;
-        if (ctx->blas_aux) SBO_BLAS(rocblas_set_stream(ctx->blas_aux, ctx->aux_stream));
-    }
-    if (!ctx->ev_panel) {
+    if (sbo_status st = forked_stream(ctx, &ctx->aux_stream, &ctx->blas_aux, &ctx->aux_reserved, ctx->chol_reserve))
+        return st;
+    if (!ctx->ev_panel) {   // (all four together: aux_ready tests the first)
         SBO_HIP(hipEventCreateWithFlags(&ctx->ev_panel, hipEventDisableTiming));
         SBO_HIP(hipEventCreateWithFlags(&ctx->ev_trail, hipEventDisableTiming));
         SBO_HIP(hipEventCreateWithFlags(&ctx->ev_pack, hipEventDisableTiming));
         SBO_HIP(hipEventCreateWithFlags(&ctx->ev_poz, hipEventDisableTiming));
     }
-    if (!ctx->blas_aux) {
-        SBO_BLAS(rocblas_create_handle(&ctx->blas_aux));
-        SBO_BLAS(rocblas_set_stream(ctx->blas_aux, ctx->aux_stream));
-    }
+    SBO_BLAS(rocblas_set_pointer_mode(ctx->blas, rocblas_pointer_mode_host));
     SBO_BLAS(rocblas_set_pointer_mode(ctx->blas_aux, rocblas_pointer_mode_host));
-    // The f64 copy of the factor the inverse starts from (refresh_operand),
-    // widened panel by panel as outer panels become final: on aux_stream
-    // after each trailing update, beside the chain's latency-bound second
-    // half, instead of one 0.7 ms pass between the factorization and the
-    // inverse (C4).  The strictly upper part is zeroed with it.
-    const bool wid = early_inv && !early;
-    double *Lw = nullptr;
-    int64_t Kw = 0;   // columns [0, Kw) widened (enqueued)
-    if (wid) {
-        SBO_HIP(ctx->Linv.reserve(sizeof(double) * (size_t)ld * (size_t)ld));
-        Lw = ctx->Linv.as<double>();
-    }
-    const float one = 1.0f, minus_one = -1.0f;
-    // Two levels (SBO_OPT_CHOL_OUTER = NB2 > kCholNB): outer panels of NB2
-    // columns, each factored by the kCholNB chain above with its updates kept
-    // inside the panel (one sgemm per inner step over the panel's remaining
-    // columns); the rest of the trailing matrix takes one rank-NB2 update per
-    // outer panel (k = 512: rocBLAS ssyrk at ~1.5x its k = 128 rate, and a
-    // quarter of the trailing matrix's HBM passes).  The look-ahead is the
-    // outer panel's: the next outer panel's columns first (sgemm on `stream`),
-    // the rest on aux_stream.  NB2 = kCholNB is the one-level factorization.
-    const int64_t NB = sbo::kCholNB;
-    const int64_t NB2 = std::max<int64_t>(NB, (int64_t)ctx->chol_outer / NB * NB);
-    // below this size the trailing update is one sgemm over the full square
-    // (rocBLAS ssyrk: 82 vs 49 us at m = 4000, 67 vs 20 at 2000, k = 128;
-    // tools/r3_gemm_probe.cpp); the upper triangle it also writes is never read
-    constexpr int64_t kSmallTrail = 6144;
-    bool trail_pending = false;
-    if (ctx->chol_gemm_own == 3 && n > NB2)   // both plane buffers at the first panel's size, up front
-        for (sbo::DevBuf &pb : ctx->cholx3) SBO_HIP(pb.reserve(sbo::chol_x3_bytes(n - NB2, NB2)));
-    // SBO_OPT_CHOL_GEMM 4 / 5: the two big updates as the int8-sliced GEMM
-    // with 4 / 5 digits (csrc/ozgemm.hip, f32 in and out) from ONE pack of the
-    // outer panel per step (the look-ahead's both operands and the trailing
-    // update's are row ranges of it), two packs alternating across steps (the
-    // trailing update on aux_stream may still read the previous one), sized up
-    // front for the first outer panel
-    const int oz_nd = (ctx->chol_gemm_own == 4 || ctx->chol_gemm_own == 5) ? ctx->chol_gemm_own : 0;
-    if (oz_nd && n > NB2)
-        for (sbo::DevBuf &pb : ctx->cholx3) SBO_HIP(pb.reserve(sbo::gz_pack_bytes(n - NB2, NB2, oz_nd)));
-    sbo_status st = SBO_OK;
-    for (int64_t K = 0; K < n && st == SBO_OK; K += NB2) {
-        const int64_t W = std::min(NB2, n - K);
-        for (int64_t k = K; k < K + W; k += NB) {
-            const int64_t kb = std::min<int64_t>(NB, n - k);
-            const int64_t m2 = n - k - kb;
-            float *L11 = L + k + k * ld, *A21 = L11 + kb;
-            if (sbo::launch_chol_diag(ctx->stream, L11, ld, (int)kb, k, info, ctx->chol_diag) != hipSuccess) {
-                st = SBO_E_DEVICE;
-                break;
-            }
-            if (m2 <= 0) break;
-            if (ctx->chol_trsm_own) {
-                if (sbo::launch_chol_trsm(ctx->stream, L11, ld, (int)kb, A21, m2, ctx->chol_diag) != hipSuccess) {
-                    st = SBO_E_DEVICE;
-                    break;
-                }
-            } else if (rocblas_strsm(ctx->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_transpose,
-                                     rocblas_diagonal_non_unit, (rocblas_int)m2, (rocblas_int)kb, &one, L11,
-                                     (rocblas_int)ld, A21, (rocblas_int)ld) != rocblas_status_success) {
-                st = SBO_E_DEVICE;
-                break;
-            }
-            if (k + kb == h_inv) {
-                // the left h columns are final: the inverse's first half on inv_stream
-                if (hipEventRecord(ctx->ev_half, ctx->stream) != hipSuccess ||
-                    hipStreamWaitEvent(ctx->inv_stream, ctx->ev_half, 0) != hipSuccess ||
-                    sbo::launch_widen(ctx->inv_stream, L, ld, n, h_inv, true, ctx->Linv.as<double>(), ld) != hipSuccess) {
-                    st = SBO_E_DEVICE;
-                    break;
-                }
-                early_pending = true;
-                int slot = 0;
-                const int64_t hq = inverse_split(n, ctx->inv_base);
-                if ((st = inverse_first_half(ctx, ctx->blas_inv, ctx->Linv.as<double>(), n, ld,
-                                             ctx->scratch.as<double>(),
-                                             ctx->scratch.as<double>() + hq * (n - hq), slot, InvMode{})) != SBO_OK)
-                    break;
-                ho.half_slots = slot;
-                if (hipEventRecord(ctx->ev_inv, ctx->inv_stream) != hipSuccess) { st = SBO_E_DEVICE; break; }
-            }
-            // the outer panel's remaining columns (rows below this block)
-            const int64_t rem = K + W - (k + kb);
-            if (rem > 0) {
-                const bool ok =
-                    ctx->chol_gemm_own == 2
-                        ? sbo::launch_chol_update(ctx->stream, A21, A21, ld, m2, rem, kb, false, L11 + kb + kb * ld) ==
-                              hipSuccess
-                        : rocblas_sgemm(ctx->blas, rocblas_operation_none, rocblas_operation_transpose, (rocblas_int)m2,
-                                        (rocblas_int)rem, (rocblas_int)kb, &minus_one, A21, (rocblas_int)ld, A21,
-                                        (rocblas_int)ld, &one, L11 + kb + kb * ld,
-                                        (rocblas_int)ld) == rocblas_status_success;
-                if (!ok) { st = SBO_E_DEVICE; break; }
-            }
-        }
-        if (st != SBO_OK) break;
-        const int64_t m3 = n - K - W;
-        if (m3 <= 0) break;
-        const float *P = L + (K + W) + K * ld;   // the panel's rows below it: m3 x W
-        float *C1 = L + (K + W) + (K + W) * ld;
-        const int64_t W2 = std::min(NB2, m3);    // the next outer panel
-        // SBO_OPT_CHOL_GEMM 3: the panel split into bf16 planes once, read by
-        // the look-ahead here and the trailing update on aux_stream (two
-        // buffers: this panel's trailing update may still read the previous
-        // buffer's twin until the next look-ahead has waited for it)
-        const bool x3 = ctx->chol_gemm_own == 3 && W % 32 == 0;
-        char *planes = nullptr;
-        const bool ozp = oz_nd && W % 64 == 0 && W2 % 128 == 0;   // (the last panels: rocBLAS)
-        if (ozp) {
-            planes = ctx->cholx3[(K / NB2) & 1].as<char>();
-            if (sbo::launch_gz_pack_f32(ctx->stream, oz_nd, P, ld, m3, W, planes) != hipSuccess) {
-                st = SBO_E_DEVICE;
-                break;
-            }
-        } else if (x3) {
-            sbo::DevBuf &pb = ctx->cholx3[(K / NB2) & 1];
-            if (pb.reserve(sbo::chol_x3_bytes(m3, W)) != hipSuccess ||
-                sbo::launch_chol_split(ctx->stream, P, ld, m3, W, pb.as<char>()) != hipSuccess) {
-                st = SBO_E_DEVICE;
-                break;
-            }
-            planes = pb.as<char>();
-        }
-        if (hipEventRecord(ctx->ev_panel, ctx->stream) != hipSuccess ||
-            (trail_pending && hipStreamWaitEvent(ctx->stream, ctx->ev_trail, 0) != hipSuccess)) { st = SBO_E_DEVICE; break; }
-        const bool la_ok =
-            ozp ? sbo::launch_gz_gemm_packed_f32(ctx->stream, oz_nd, planes, m3, W, 0, m3, 0, W2, -1.0, C1, ld,
-                                                 sbo::kGzBeta1) == hipSuccess
-            : x3 ? sbo::launch_chol_update_x3(ctx->stream, planes, m3, W, 0, m3, 0, W2, false, C1, ld) == hipSuccess
-            : ctx->chol_gemm_own == 2
-                ? sbo::launch_chol_update(ctx->stream, P, P, ld, m3, W2, W, false, C1) == hipSuccess
-                : rocblas_sgemm(ctx->blas, rocblas_operation_none, rocblas_operation_transpose, (rocblas_int)m3,
-                                (rocblas_int)W2, (rocblas_int)W, &minus_one, P, (rocblas_int)ld, P, (rocblas_int)ld,
-                                &one, C1, (rocblas_int)ld) == rocblas_status_success;
-        if (!la_ok) { st = SBO_E_DEVICE; break; }
-        const int64_t m4 = m3 - W2;
-        trail_pending = false;
-        if (m4 > 0) {
-            if (hipStreamWaitEvent(ctx->aux_stream, ctx->ev_panel, 0) != hipSuccess) { st = SBO_E_DEVICE; break; }
-            // (1: the own kernel only where it measured faster than rocBLAS,
-            // the lower update of m4 <= 8192; 2: every update)
-            bool ok;
-            if (ozp)
-                ok = sbo::launch_gz_gemm_packed_f32(ctx->aux_stream, oz_nd, planes, m3, W, W2, m4, W2, m4, -1.0,
-                                                    C1 + W2 + W2 * ld, ld,
-                                                    sbo::kGzBeta1 | sbo::kGzLowerC) == hipSuccess;
-            else if (x3)
-                ok = sbo::launch_chol_update_x3(ctx->aux_stream, planes, m3, W, W2, m4, W2, m4, true,
-                                                C1 + W2 + W2 * ld, ld) == hipSuccess;
-            else if (ctx->chol_gemm_own == 2 || (ctx->chol_gemm_own == 1 && m4 <= 8192))
-                ok = sbo::launch_chol_update(ctx->aux_stream, P + W2, P + W2, ld, m4, m4, W, true,
-                                             C1 + W2 + W2 * ld) == hipSuccess;
-            else
-                ok = (m4 <= kSmallTrail
-                          ? rocblas_sgemm(ctx->blas_aux, rocblas_operation_none, rocblas_operation_transpose,
-                                          (rocblas_int)m4, (rocblas_int)m4, (rocblas_int)W, &minus_one, P + W2,
-                                          (rocblas_int)ld, P + W2, (rocblas_int)ld, &one, C1 + W2 + W2 * ld,
-                                          (rocblas_int)ld)
-                          : rocblas_ssyrk(ctx->blas_aux, rocblas_fill_lower, rocblas_operation_none, (rocblas_int)m4,
-                                          (rocblas_int)W, &minus_one, P + W2, (rocblas_int)ld, &one,
-                                          C1 + W2 + W2 * ld, (rocblas_int)ld)) == rocblas_status_success;
-            if (!ok) { st = SBO_E_DEVICE; break; }
-            trail_pending = true;
-            if (hipEventRecord(ctx->ev_trail, ctx->aux_stream) != hipSuccess) { st = SBO_E_DEVICE; break; }
-        }
-        if (wid) {
-            // this outer panel's columns are final (ev_panel); ev_trail above
-            // leaves the widen off the look-ahead's dependency chain
-            if ((m4 <= 0 && hipStreamWaitEvent(ctx->aux_stream, ctx->ev_panel, 0) != hipSuccess) ||
-                sbo::launch_widen(ctx->aux_stream, L + K + K * ld, ld, n - K, W, true, Lw + K + K * ld, ld) !=
-                    hipSuccess ||
-                (K > 0 && hipMemset2DAsync(Lw + K * ld, sizeof(double) * (size_t)ld, 0, sizeof(double) * (size_t)K,
-                                           (size_t)W, ctx->aux_stream) != hipSuccess)) {
-                st = SBO_E_DEVICE;
-                break;
-            }
-            Kw = K + W;
-        }
-    }
-    if (st != SBO_OK) {
-        (void)hipStreamSynchronize(ctx->aux_stream);
-        if (early_pending) (void)hipStreamSynchronize(ctx->inv_stream);
-        ctx->err = "blocked Cholesky: a rocBLAS or HIP call failed";
-        return st;
-    }
-    if (trail_pending) SBO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_trail, 0));
-    if (wid) {
-        // the last outer panel here; the aux_stream widens before it
-        SBO_HIP(sbo::launch_widen(ctx->stream, L + Kw + Kw * ld, ld, n - Kw, n - Kw, true, Lw + Kw + Kw * ld, ld));
-        if (Kw > 0)
-            SBO_HIP(hipMemset2DAsync(Lw + Kw * ld, sizeof(double) * (size_t)ld, 0, sizeof(double) * (size_t)Kw,
-                                     (size_t)(n - Kw), ctx->stream));
-        SBO_HIP(hipEventRecord(ctx->ev_trail, ctx->aux_stream));
-        SBO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_trail, 0));
-        ho.widened_n = n;
-    }
-    if (early_pending) {
-        SBO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_inv, 0));
-        ho.half_n = n;
-    }
-    if (out) *out = ho;
     return SBO_OK;
 }
 
-sbo_status factor_and_refresh(sbo_ctx *ctx) {
-    rocblas_int *info = ctx->info.as<rocblas_int>();
-    ctx->inv_oz_cur = choose_inv_digits(ctx);
-    // only the factorization that runs now hands anything to refresh_operand
-    // (the rocSOLVER path never does)
-    FactorHandover ho;
-    if (ctx->chol_blocked) {
-        const bool early_inv = ctx->inverse_bits == 64 && ctx->inverse_rec;
-        if (sbo_status st = blocked_potrf(ctx, ctx->L.as<float>(), ctx->n, ctx->cap, info, early_inv, &ho);
-            st != SBO_OK)
-            return st;
-        info = ctx->info.as<rocblas_int>();   // (blocked_potrf may have grown it)
-    } else {
-        SBO_BLAS(rocsolver_spotrf(ctx->blas, rocblas_fill_lower, (rocblas_int)ctx->n, ctx->L.as<float>(),
-                                  (rocblas_int)ctx->cap, info));
+// Every buffer the early half touches, sized before it starts (a reserve that
+// reallocates later would free memory in use), and its info slots cleared.
+sbo_status chol_reserve_early(sbo_ctx *ctx, const CholPlan &p) {
+    SBO_HIP(ctx->Linv.reserve(sizeof(double) * (size_t)p.ld * (size_t)p.ld));
+    SBO_HIP(ctx->scratch.reserve(sizeof(double) * (size_t)std::max<int64_t>(inverse_scratch(p.n, ctx->inv_base), 1)));
+    SBO_HIP(hipMemsetAsync(p.info, 0, sizeof(rocblas_int) * (size_t)p.info_slots, ctx->stream));
+    return SBO_OK;
+}
+
+// The widened factor's place, and both pack buffers at the first outer
+// panel's size, up front.
+sbo_status chol_reserve_panels(sbo_ctx *ctx, const CholPlan &p) {
+    if (p.widen) SBO_HIP(ctx->Linv.reserve(sizeof(double) * (size_t)p.ld * (size_t)p.ld));
+    if (p.n <= p.NB2) return SBO_OK;
+    for (sbo::DevBuf &pb : ctx->cholx3) {
+        if (p.update == CholPlan::kX3) SBO_HIP(pb.reserve(sbo::chol_x3_bytes(p.n - p.NB2, p.NB2)));
+        if (p.update == CholPlan::kOz) SBO_HIP(pb.reserve(sbo::gz_pack_bytes(p.n - p.NB2, p.NB2, p.oz_digits)));
     }
+    return SBO_OK;
+}
+
+// One step of the chain on `stream`: the kb x kb diagonal block at L11 (step
+// k) in one workgroup, then the m2 rows below it, A21 := A21 L11^-T.
+sbo_status chol_chain_step(sbo_ctx *ctx, const CholPlan &p, float *L11, int64_t kb, int64_t k, int64_t m2) {
+    CHOL_HIP(sbo::launch_chol_diag(ctx->stream, L11, p.ld, (int)kb, k, p.info, p.chain));
+    if (m2 <= 0) return SBO_OK;
+    if (p.own_trsm) {
+        CHOL_HIP(sbo::launch_chol_trsm(ctx->stream, L11, p.ld, (int)kb, L11 + kb, m2, p.chain));
+    } else {
+        const float one = 1.0f;
+        CHOL_BLAS(rocblas_strsm(ctx->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_transpose,
+                                rocblas_diagonal_non_unit, (rocblas_int)m2, (rocblas_int)kb, &one, L11,
+                                (rocblas_int)p.ld, L11 + kb, (rocblas_int)p.ld));
+    }
+    return SBO_OK;
+}
+
+// C (mr x nc, lda ld) -= P[r0 .. r0 + mr) P[c0 .. c0 + nc)^T for row ranges of
+// the m x k panel P, on stream s (hb: the rocBLAS handle bound to it), by the
+// plan's back end for this site.
+sbo_status chol_update(const CholPlan &p, const PanelPack &pk, UpdateSite site, hipStream_t s, rocblas_handle hb,
+                       const float *P, int64_t m, int64_t k, int64_t r0, int64_t mr, int64_t c0, int64_t nc,
+                       float *C) {
+    const bool trailing = site == UpdateSite::kTrailing;
+    const bool packed = site != UpdateSite::kInner;
+    if (packed && pk.oz) {
+        CHOL_HIP(sbo::launch_gz_gemm_packed_f32(s, p.oz_digits, pk.planes, m, k, r0, mr, c0, nc, -1.0, C, p.ld,
+                                                sbo::kGzBeta1 | (trailing ? sbo::kGzLowerC : 0u)));
+    } else if (packed && pk.x3) {
+        CHOL_HIP(sbo::launch_chol_update_x3(s, pk.planes, m, k, r0, mr, c0, nc, trailing, C, p.ld));
+    } else if (p.update == CholPlan::kOwn || (p.update == CholPlan::kOwnSmall && trailing && mr <= 8192)) {
+        CHOL_HIP(sbo::launch_chol_update(s, P + r0, P + c0, p.ld, mr, nc, k, trailing, C));
+    } else if (trailing && mr > kSmallTrail) {
+        const float one = 1.0f, minus_one = -1.0f;
+        CHOL_BLAS(rocblas_ssyrk(hb, rocblas_fill_lower, rocblas_operation_none, (rocblas_int)mr, (rocblas_int)k,
+                                &minus_one, P + r0, (rocblas_int)p.ld, &one, C, (rocblas_int)p.ld));
+    } else {
+        const float one = 1.0f, minus_one = -1.0f;
+        CHOL_BLAS(rocblas_sgemm(hb, rocblas_operation_none, rocblas_operation_transpose, (rocblas_int)mr,
+                                (rocblas_int)nc, (rocblas_int)k, &minus_one, P + r0, (rocblas_int)p.ld, P + c0,
+                                (rocblas_int)p.ld, &one, C, (rocblas_int)p.ld));
+    }
+    return SBO_OK;
+}
+
+// Joins the streams blocked_potrf forked if it returns early: aux_stream, and
+// inv_stream once the early half has started.  Dismissed on success (the
+// joins are then events on `stream`, chol_join).
+struct CholJoin {
+    sbo_ctx *ctx;
+    bool early_started = false, dismissed = false;
+    ~CholJoin() {
+        if (dismissed) return;
+        (void)hipStreamSynchronize(ctx->aux_stream);
+        if (early_started) (void)hipStreamSynchronize(ctx->inv_stream);
+    }
+};
+
+// The left h_inv columns are final: the inverse's first half on inv_stream
+// (widen them, A^-1, S = B A^-1: half its flops) beside the Cholesky's last
+// steps, which leave most CUs idle.  refresh_operand finishes the inverse.
+sbo_status chol_early_half(sbo_ctx *ctx, const CholPlan &p, const float *L, CholJoin &join, FactorHandover &ho) {
+    double *Li = ctx->Linv.as<double>(), *S = ctx->scratch.as<double>();
+    CHOL_HIP(hipEventRecord(ctx->ev_half, ctx->stream));
+    CHOL_HIP(hipStreamWaitEvent(ctx->inv_stream, ctx->ev_half, 0));
+    CHOL_HIP(sbo::launch_widen(ctx->inv_stream, L, p.ld, p.n, p.h_inv, true, Li, p.ld));
+    join.early_started = true;
+    int slot = 0;
+    if (sbo_status st = inverse_first_half(ctx, ctx->blas_inv, Li, p.n, p.ld, S, S + p.h_inv * (p.n - p.h_inv), slot,
+                                           InvMode{}))
+        return st;
+    ho.half_slots = slot;
+    CHOL_HIP(hipEventRecord(ctx->ev_inv, ctx->inv_stream));
+    return SBO_OK;
+}
+
+// The pack of the outer panel's m3 x W rows below it, where this step's
+// shapes allow the plan's packed update (else an empty PanelPack: rocBLAS or
+// chol_update_kernel read P itself).
+sbo_status chol_pack_panel(sbo_ctx *ctx, const CholPlan &p, const float *P, int64_t m3, int64_t W, int64_t W2,
+                           int buffer, PanelPack &pk) {
+    pk = PanelPack{};
+    pk.buffer = buffer;
+    pk.oz = p.update == CholPlan::kOz && W % 64 == 0 && W2 % 128 == 0;
+    pk.x3 = p.update == CholPlan::kX3 && W % 32 == 0;
+    if (!pk.oz && !pk.x3) return SBO_OK;
+    sbo::DevBuf &pb = ctx->cholx3[buffer];
+    if (pk.oz) {
+        CHOL_HIP(sbo::launch_gz_pack_f32(ctx->stream, p.oz_digits, P, p.ld, m3, W, pb.as<char>()));
+    } else {
+        CHOL_HIP(pb.reserve(sbo::chol_x3_bytes(m3, W)));
+        CHOL_HIP(sbo::launch_chol_split(ctx->stream, P, p.ld, m3, W, pb.as<char>()));
+    }
+    pk.planes = pb.as<char>();
+    return SBO_OK;
+}
+
+// The outer panel at columns [K, K + W) is factored: its rank-W update of the
+// trailing matrix, in two parts.  The look-ahead -- the next outer panel's W2
+// columns -- on `stream`, followed at once by that panel's chain, so that the
+// one-CU diagonal kernels run beside the big update instead of between
+// updates; the rest on aux_stream.  ev_panel: the panel (and its pack) is
+// ready; ev_trail: the trailing update is done, which the next look-ahead
+// waits for (it wrote those columns too) and the final join.
+sbo_status chol_outer_update(sbo_ctx *ctx, const CholPlan &p, float *L, int64_t K, int64_t W, bool &trail_pending) {
+    const int64_t m3 = p.n - K - W, W2 = std::min(p.NB2, m3), m4 = m3 - W2;
+    const float *P = L + (K + W) + K * p.ld;   // the panel's rows below it: m3 x W
+    float *C1 = L + (K + W) + (K + W) * p.ld;
+    PanelPack pk;
+    if (sbo_status st = chol_pack_panel(ctx, p, P, m3, W, W2, (int)((K / p.NB2) & 1), pk)) return st;
+    CHOL_HIP(hipEventRecord(ctx->ev_panel, ctx->stream));
+    if (trail_pending) CHOL_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_trail, 0));
+    if (sbo_status st = chol_update(p, pk, UpdateSite::kLookahead, ctx->stream, ctx->blas, P, m3, W, 0, m3, 0, W2, C1))
+        return st;
+    trail_pending = false;
+    if (m4 <= 0) return SBO_OK;
+    CHOL_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_panel, 0));
+    if (sbo_status st = chol_update(p, pk, UpdateSite::kTrailing, ctx->aux_stream, ctx->blas_aux, P, m3, W, W2, m4, W2,
+                                    m4, C1 + W2 + W2 * p.ld))
+        return st;
+    trail_pending = true;
+    CHOL_HIP(hipEventRecord(ctx->ev_trail, ctx->aux_stream));
+    return SBO_OK;
+}
+
+// The f64 copy of the factor the inverse starts from (refresh_operand),
+// widened panel by panel as outer panels become final: on aux_stream after
+// each trailing update, beside the chain's latency-bound second half, instead
+// of one 0.7 ms pass between the factorization and the inverse (C4).  The
+// strictly upper part is zeroed with it.  The panel's columns are final at
+// ev_panel, which aux_stream has waited for if it took a trailing update;
+// coming after ev_trail's record, the widen stays off the look-ahead's
+// dependency chain.
+sbo_status chol_widen_panel(sbo_ctx *ctx, const CholPlan &p, const float *L, int64_t K, int64_t W, bool waited) {
+    double *Lw = ctx->Linv.as<double>();
+    if (!waited) CHOL_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_panel, 0));
+    CHOL_HIP(sbo::launch_widen(ctx->aux_stream, L + K + K * p.ld, p.ld, p.n - K, W, true, Lw + K + K * p.ld, p.ld));
+    if (K > 0)
+        CHOL_HIP(hipMemset2DAsync(Lw + K * p.ld, sizeof(double) * (size_t)p.ld, 0, sizeof(double) * (size_t)K,
+                                  (size_t)W, ctx->aux_stream));
+    return SBO_OK;
+}
+
+// `stream` waits for what was forked: the last trailing update, the widened
+// panels (after widening the last outer panel, columns Kw.., itself) and the
+// early half; and says in `ho` what is there for the refresh.
+sbo_status chol_join(sbo_ctx *ctx, const CholPlan &p, const float *L, int64_t Kw, bool trail_pending,
+                     bool early_started, FactorHandover &ho) {
+    if (trail_pending) CHOL_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_trail, 0));
+    if (p.widen) {
+        double *Lw = ctx->Linv.as<double>();
+        const int64_t r = p.n - Kw;
+        CHOL_HIP(sbo::launch_widen(ctx->stream, L + Kw + Kw * p.ld, p.ld, r, r, true, Lw + Kw + Kw * p.ld, p.ld));
+        if (Kw > 0)
+            CHOL_HIP(hipMemset2DAsync(Lw + Kw * p.ld, sizeof(double) * (size_t)p.ld, 0, sizeof(double) * (size_t)Kw,
+                                      (size_t)r, ctx->stream));
+        CHOL_HIP(hipEventRecord(ctx->ev_trail, ctx->aux_stream));
+        CHOL_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_trail, 0));
+        ho.widened_n = p.n;
+    }
+    if (early_started) {
+        CHOL_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_inv, 0));
+        ho.half_n = p.n;
+    }
+    return SBO_OK;
+}
+
+// Right-looking blocked Cholesky of the n x n lower triangle at L (lda = ld),
+// in two levels.  Outer panels of NB2 columns; each is factored by the chain
+// of NB = 128 columns (chol_chain_step: diagonal block, panel below it) with
+// the updates after each block kept inside the outer panel (chol_update,
+// kInner), and the rest of the trailing matrix takes one rank-NB2 update per
+// outer panel, split into the look-ahead on `stream` and the rest on
+// aux_stream (chol_outer_update).  NB2 = NB is the one-level factorization.
+// The same factorization as spotrf without its unblocked potf2 panels; info
+// as rocSOLVER's.  early_inv: a fit whose recursive f64 inverse follows.
+// Either its first half runs on inv_stream as soon as the columns it reads
+// are final (chol_early_half), or the factor is widened to f64 for it panel
+// by panel (chol_widen_panel).  ho: what is handed to the refresh, and the
+// info slots used.  Nothing here waits on the host; after a failure the
+// forked streams are joined (CholJoin) before the error is returned.
+sbo_status blocked_potrf(sbo_ctx *ctx, float *L, int64_t n, int64_t ld, bool early_inv, FactorHandover &ho) {
+    CholPlan p;
+    if (sbo_status st = chol_plan(ctx, n, ld, early_inv, p)) return st;
+    ho = FactorHandover{};
+    ho.info = p.info;
+    SBO_HIP(hipMemsetAsync(p.info, 0, sizeof(rocblas_int), ctx->stream));
+    if (sbo_status st = chol_streams(ctx, p)) return st;
+    if (p.early)
+        if (sbo_status st = chol_reserve_early(ctx, p)) return st;
+    if (sbo_status st = chol_reserve_panels(ctx, p)) return st;
+    CholJoin join{ctx};
+    const auto fail = [ctx](sbo_status st) {
+        ctx->err = "blocked Cholesky: a rocBLAS or HIP call failed";
+        return st;
+    };
+    bool trail_pending = false;
+    int64_t Kw = 0;   // columns [0, Kw) widened (enqueued)
+    for (int64_t K = 0; K < n; K += p.NB2) {
+        const int64_t W = std::min(p.NB2, n - K);
+        for (int64_t k = K; k < K + W; k += p.NB) {
+            const int64_t kb = std::min(p.NB, n - k), m2 = n - k - kb;
+            float *L11 = L + k + k * ld;
+            if (sbo_status st = chol_chain_step(ctx, p, L11, kb, k, m2)) return fail(st);
+            if (m2 <= 0) break;
+            if (k + kb == p.h_inv)
+                if (sbo_status st = chol_early_half(ctx, p, L, join, ho)) return fail(st);
+            const int64_t rem = K + W - (k + kb);   // the outer panel's remaining columns (rows below this block)
+            if (rem > 0)
+                if (sbo_status st = chol_update(p, PanelPack{}, UpdateSite::kInner, ctx->stream, ctx->blas, L11 + kb,
+                                                m2, kb, 0, m2, 0, rem, L11 + kb + kb * ld))
+                    return fail(st);
+        }
+        if (n - K - W <= 0) break;
+        if (sbo_status st = chol_outer_update(ctx, p, L, K, W, trail_pending)) return fail(st);
+        if (p.widen) {   // (a trailing update pending: aux_stream has waited for this panel)
+            if (sbo_status st = chol_widen_panel(ctx, p, L, K, W, trail_pending)) return fail(st);
+            Kw = K + W;
+        }
+    }
+    if (sbo_status st = chol_join(ctx, p, L, Kw, trail_pending, join.early_started, ho)) return fail(st);
+    join.dismissed = true;
+    return SBO_OK;
+}
+#undef CHOL_HIP
+#undef CHOL_BLAS
+
+// The leading minor rocSOLVER's or blocked_potrf's info slot 0 reports, read
+// back (the factorization's one host sync); non-zero: SBO_E_NOT_SPD.
+enum class FactorOf { kFit, kAppendedBlock };
+sbo_status factor_info(sbo_ctx *ctx, const rocblas_int *info, FactorOf what) {
     rocblas_int hinfo = 0;
     SBO_HIP(hipMemcpyAsync(&hinfo, info, sizeof(hinfo), hipMemcpyDeviceToHost, ctx->stream));
     SBO_HIP(hipStreamSynchronize(ctx->stream));
-    if (hinfo != 0) {
-        ctx->err = "spotrf: leading minor " + std::to_string(hinfo) + " not positive definite";
-        return SBO_E_NOT_SPD;
+    if (hinfo == 0) return SBO_OK;
+    ctx->err = what == FactorOf::kFit
+                   ? "spotrf: leading minor " + std::to_string(hinfo) + " not positive definite"
+                   : "sbo_append: updated block not positive definite (info=" + std::to_string(hinfo) + ")";
+    return SBO_E_NOT_SPD;
+}
+
+// The n x n lower triangle at L (already filled, lda = ld) factored in place
+// by the blocked Cholesky or rocSOLVER's spotrf (SBO_OPT_CHOLESKY 0), and its
+// info read.  Only blocked_potrf hands anything to refresh_operand.
+sbo_status factor_block(sbo_ctx *ctx, float *L, int64_t n, int64_t ld, bool early_inv, FactorOf what,
+                        FactorHandover &ho) {
+    ho = FactorHandover{};
+    ho.info = ctx->info.as<rocblas_int>();
+    if (ctx->chol_blocked) {
+        if (sbo_status st = blocked_potrf(ctx, L, n, ld, early_inv, ho)) return st;
+    } else {
+        SBO_BLAS(rocsolver_spotrf(ctx->blas, rocblas_fill_lower, (rocblas_int)n, L, (rocblas_int)ld, ho.info));
     }
+    return factor_info(ctx, ho.info, what);
+}
+
+// Factor K in L (already filled, lda = cap) and refresh the operand.
+sbo_status factor_and_refresh(sbo_ctx *ctx) {
+    ctx->inv_oz_cur = choose_inv_digits(ctx);
+    FactorHandover ho;
+    if (sbo_status st = factor_block(ctx, ctx->L.as<float>(), ctx->n, ctx->cap, ctx->inverse_bits == 64 && ctx->inverse_rec,
+                                     FactorOf::kFit, ho))
+        return st;
     ctx->has_factor = true;
     return refresh_operand(ctx, 0, ho);
 }
@@ -2466,6 +2583,116 @@ sbo_status resort_append(sbo_ctx *ctx, const float *x, const float *y, const flo
     for (int64_t i = 0; i < n1; ++i) ctx->order[(size_t)i] = prev[(size_t)ctx->order[(size_t)i]];
     return fill_and_factor(ctx, ctx->hyper.noise_level - ctx->jitter);
 }
+
+// sbo_append's block update of the lower factor (column-major, lda = cap), n0
+// points there and b staged behind them:
+//   [L11  0 ]   K21 = k(Xnew, X)  -> L21 = K21 L11^-T        (append_panel)
+//   [L21 L22]   K22 = k(Xnew, Xnew) + sn2 I - L21 L21^T      (append_schur)
+//               L22 = chol(K22)                              (factor_block)
+// L21: rows n0.., columns 0..n0-1; L22: rows n0.., columns n0..
+float *append_L21(const sbo_ctx *ctx, int64_t n0) { return ctx->L.as<float>() + n0; }
+float *append_L22(const sbo_ctx *ctx, int64_t n0) { return ctx->L.as<float>() + n0 + n0 * ctx->cap; }
+
+// Storage for n1 > cap points: geometric growth that keeps the points, the
+// factor and, where the incremental refresh will use it, the f64 inverse.
+sbo_status append_grow(sbo_ctx *ctx, int64_t n1) {
+    const int64_t n0 = ctx->n;
+    const int64_t ncap = std::max<int64_t>(n1, sbo::round_up(ctx->cap + ctx->cap / 2, 256));
+    DevBuf nx, ny, no, nL;
+    SBO_HIP(nx.reserve(sizeof(float) * ncap));
+    SBO_HIP(ny.reserve(sizeof(float) * ncap));
+    SBO_HIP(no.reserve(sizeof(float) * ncap));
+    SBO_HIP(nL.reserve(sizeof(float) * (size_t)ncap * (size_t)ncap));
+    SBO_HIP(hipMemcpyAsync(nx.as<float>(), ctx->x.as<float>(), sizeof(float) * n0, hipMemcpyDeviceToDevice, ctx->stream));
+    SBO_HIP(hipMemcpyAsync(ny.as<float>(), ctx->y.as<float>(), sizeof(float) * n0, hipMemcpyDeviceToDevice, ctx->stream));
+    SBO_HIP(hipMemcpyAsync(no.as<float>(), ctx->obs.as<float>(), sizeof(float) * n0, hipMemcpyDeviceToDevice, ctx->stream));
+    SBO_HIP(hipMemcpy2DAsync(nL.as<float>(), sizeof(float) * ncap, ctx->L.as<float>(), sizeof(float) * ctx->cap,
+                             sizeof(float) * n0, n0, hipMemcpyDeviceToDevice, ctx->stream));
+    SBO_HIP(hipStreamSynchronize(ctx->stream));
+    if (ctx->linv_n == n0 && ctx->inverse_bits == 64) {  // keep the f64 inverse for the incremental refresh
+        DevBuf nLi;
+        SBO_HIP(nLi.reserve(sizeof(double) * (size_t)ncap * (size_t)ncap));
+        SBO_HIP(hipMemcpy2DAsync(nLi.as<double>(), sizeof(double) * ncap, ctx->Linv.as<double>(),
+                                 sizeof(double) * ctx->cap, sizeof(double) * n0, n0, hipMemcpyDeviceToDevice,
+                                 ctx->stream));
+        SBO_HIP(hipStreamSynchronize(ctx->stream));
+        ctx->Linv.swap(nLi);
+    } else {
+        ctx->linv_n = 0;
+    }
+    ctx->x.swap(nx);
+    ctx->y.swap(ny);
+    ctx->obs.swap(no);
+    ctx->L.swap(nL);
+    ctx->cap = ncap;
+    SBO_HIP(ctx->alpha.reserve(sizeof(float) * ncap));
+    return SBO_OK;
+}
+
+// K21 and K22 (with the noise on its diagonal) in their places in L
+sbo_status append_fill(sbo_ctx *ctx, int64_t n0, int64_t b) {
+    const int64_t ld = ctx->cap;
+    const float *xs = ctx->x.as<float>(), *ys = ctx->y.as<float>();
+    const float ell = (float)ctx->hyper.length_scale, sn2 = (float)ctx->hyper.noise_level;
+    const float sf2 = (float)(ctx->hyper.sigma_f * ctx->hyper.sigma_f);
+    SBO_HIP(sbo::launch_rbf_fill(ctx->stream, xs + n0, ys + n0, b, xs, ys, n0, ld, ell, sf2, sn2, false,
+                                 append_L21(ctx, n0)));
+    SBO_HIP(sbo::launch_rbf_fill(ctx->stream, xs + n0, ys + n0, b, xs + n0, ys + n0, b, ld, ell, sf2, sn2, true,
+                                 append_L22(ctx, n0)));
+    return SBO_OK;
+}
+
+// L21 = K21 L11^-T in place, one branch per regime (kAppendInvRows,
+// kAppendInvGemm, the level-3 solve).
+sbo_status append_panel(sbo_ctx *ctx, int64_t n0, int64_t b) {
+    const int64_t ld = ctx->cap;
+    float *L21 = append_L21(ctx, n0);
+    const bool inv_kept = ctx->inverse_bits == 64 && ctx->linv_n == n0;
+    SBO_BLAS(rocblas_set_pointer_mode(ctx->blas, rocblas_pointer_mode_host));
+    if (inv_kept && b <= kAppendInvRows) {
+        // a few points (the node's one per change): L21 row by row from the
+        // kept f64 inverse, L21[r,:]^T = L11^-1 K21[r,:]^T, one dtrmv over its
+        // lower triangle per point, rounded to f32 once -- rocBLAS strsm ran
+        // the 1 x n0 solve as ~250 small launches (6.3 ms at C4)
+        SBO_HIP(ctx->rvec.reserve(sizeof(double) * (size_t)n0));
+        double *w = ctx->rvec.as<double>();
+        for (int64_t r = 0; r < b; ++r) {
+            SBO_HIP(sbo::launch_widen(ctx->stream, L21 + r, ld, 1, n0, false, w, 1));
+            SBO_BLAS(rocblas_dtrmv(ctx->blas, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit,
+                                   (rocblas_int)n0, ctx->Linv.as<double>(), (rocblas_int)ld, w, 1));
+            SBO_HIP(sbo::launch_narrow_strided(ctx->stream, w, n0, L21 + r, ld));
+        }
+    } else if (inv_kept && b <= kAppendInvGemm) {
+        // a batch: L21 = K21 L11^-T as one f64 GEMM with the kept inverse
+        // (its strict upper part is zero), rounded to f32 once
+        SBO_HIP(ctx->rvec.reserve(sizeof(double) * (size_t)n0 * (size_t)b * 2));
+        double *kw = ctx->rvec.as<double>(), *cw = kw + (size_t)n0 * (size_t)b;
+        const double done = 1.0, dzero = 0.0;
+        SBO_HIP(sbo::launch_widen(ctx->stream, L21, ld, b, n0, false, kw, b));
+        SBO_BLAS(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_transpose, (rocblas_int)b,
+                               (rocblas_int)n0, (rocblas_int)n0, &done, kw, (rocblas_int)b, ctx->Linv.as<double>(),
+                               (rocblas_int)ld, &dzero, cw, (rocblas_int)b));
+        SBO_HIP(sbo::launch_narrow_2d(ctx->stream, cw, b, b, n0, L21, ld));
+    } else {
+        const float one = 1.0f;
+        SBO_BLAS(rocblas_strsm(ctx->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_transpose,
+                               rocblas_diagonal_non_unit, (rocblas_int)b, (rocblas_int)n0, &one, ctx->L.as<float>(),
+                               (rocblas_int)ld, L21, (rocblas_int)ld));
+    }
+    return SBO_OK;
+}
+
+// K22 -= L21 L21^T as a full b x b sgemm (rocBLAS's ssyrk ran its small-n
+// kernels at ~250 us here; the strict upper half it also writes is never
+// read).  Host pointer mode: append_panel set it.
+sbo_status append_schur(sbo_ctx *ctx, int64_t n0, int64_t b) {
+    const float one = 1.0f, minus_one = -1.0f;
+    const float *L21 = append_L21(ctx, n0);
+    SBO_BLAS(rocblas_sgemm(ctx->blas, rocblas_operation_none, rocblas_operation_transpose, (rocblas_int)b,
+                           (rocblas_int)b, (rocblas_int)n0, &minus_one, L21, (rocblas_int)ctx->cap, L21,
+                           (rocblas_int)ctx->cap, &one, append_L22(ctx, n0), (rocblas_int)ctx->cap));
+    return SBO_OK;
+}
 }  // namespace
 
 SBO_API sbo_status sbo_fit(sbo_ctx *ctx, const float *x, const float *y, const float *obs, int64_t n,
@@ -2512,110 +2739,23 @@ SBO_API sbo_status sbo_append(sbo_ctx *ctx, const float *x, const float *y, cons
     const int64_t n0 = ctx->n, n1 = n0 + b;
     SBO_CHECK(n1 < (int64_t)1 << 30, SBO_E_INVAL, "sbo_append: n too large");
     FitCommit fc(ctx);
-    const float sf2 = (float)(ctx->hyper.sigma_f * ctx->hyper.sigma_f);
     // SBO_OPT_RESORT: once the points appended since the last k-d sort exceed
     // resort_pct % of the sorted ones, re-sort and refactor all of them
     if (ctx->resort_pct > 0 && ctx->spatial_order != 0 && (n1 - ctx->n_sorted) * 100 > ctx->n_sorted * ctx->resort_pct) {
         if (sbo_status st = resort_append(ctx, x, y, obs, b, flags)) return st;
         return fc.commit(finish(ctx, flags));
     }
-
-    // grow storage (geometric) preserving the factor
-    if (n1 > ctx->cap) {
-        const int64_t ncap = std::max<int64_t>(n1, sbo::round_up(ctx->cap + ctx->cap / 2, 256));
-        DevBuf nx, ny, no, nL;
-        SBO_HIP(nx.reserve(sizeof(float) * ncap));
-        SBO_HIP(ny.reserve(sizeof(float) * ncap));
-        SBO_HIP(no.reserve(sizeof(float) * ncap));
-        SBO_HIP(nL.reserve(sizeof(float) * (size_t)ncap * (size_t)ncap));
-        SBO_HIP(hipMemcpyAsync(nx.as<float>(), ctx->x.as<float>(), sizeof(float) * n0, hipMemcpyDeviceToDevice, ctx->stream));
-        SBO_HIP(hipMemcpyAsync(ny.as<float>(), ctx->y.as<float>(), sizeof(float) * n0, hipMemcpyDeviceToDevice, ctx->stream));
-        SBO_HIP(hipMemcpyAsync(no.as<float>(), ctx->obs.as<float>(), sizeof(float) * n0, hipMemcpyDeviceToDevice, ctx->stream));
-        SBO_HIP(hipMemcpy2DAsync(nL.as<float>(), sizeof(float) * ncap, ctx->L.as<float>(), sizeof(float) * ctx->cap,
-                                 sizeof(float) * n0, n0, hipMemcpyDeviceToDevice, ctx->stream));
-        SBO_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->linv_n == n0 && ctx->inverse_bits == 64) {  // keep the f64 inverse for the incremental refresh
-            DevBuf nLi;
-            SBO_HIP(nLi.reserve(sizeof(double) * (size_t)ncap * (size_t)ncap));
-            SBO_HIP(hipMemcpy2DAsync(nLi.as<double>(), sizeof(double) * ncap, ctx->Linv.as<double>(),
-                                     sizeof(double) * ctx->cap, sizeof(double) * n0, n0, hipMemcpyDeviceToDevice,
-                                     ctx->stream));
-            SBO_HIP(hipStreamSynchronize(ctx->stream));
-            ctx->Linv.swap(nLi);
-        } else {
-            ctx->linv_n = 0;
-        }
-        ctx->x.swap(nx);
-        ctx->y.swap(ny);
-        ctx->obs.swap(no);
-        ctx->L.swap(nL);
-        ctx->cap = ncap;
-        SBO_HIP(ctx->alpha.reserve(sizeof(float) * ncap));
-    }
-    const int64_t ld = ctx->cap;
+    // the block update (append_L21): storage, the new points, K21 and K22,
+    // L21, the Schur complement, its factorization, the operand's new rows
+    if (n1 > ctx->cap)
+        if (sbo_status st = append_grow(ctx, n1)) return st;
     if (sbo_status st = stage_training(ctx, x, y, obs, b, n0, n0, flags)) return st;
-
-    // Block Cholesky update of the lower factor (column-major, lda = ld):
-    //   [L11  0 ]   K21 = k(Xnew, X)  -> L21 = K21 L11^-T        (trsm)
-    //   [L21 L22]   K22 = k(Xnew, Xnew) + sn2 I - L21 L21^T      (syrk)
-    //               L22 = chol(K22)                              (potrf)
-    float *L = ctx->L.as<float>();
-    float *xs = ctx->x.as<float>(), *ys = ctx->y.as<float>();
-    const float ell = (float)ctx->hyper.length_scale, sn2 = (float)ctx->hyper.noise_level;
-    float *L21 = L + n0;                  // rows n0.., columns 0..n0-1
-    float *L22 = L + n0 + n0 * ld;        // rows n0.., columns n0..
-    SBO_HIP(sbo::launch_rbf_fill(ctx->stream, xs + n0, ys + n0, b, xs, ys, n0, ld, ell, sf2, sn2, false, L21));
-    SBO_HIP(sbo::launch_rbf_fill(ctx->stream, xs + n0, ys + n0, b, xs + n0, ys + n0, b, ld, ell, sf2, sn2, true, L22));
-    const float one = 1.0f, minus_one = -1.0f;
-    SBO_BLAS(rocblas_set_pointer_mode(ctx->blas, rocblas_pointer_mode_host));
-    if (ctx->inverse_bits == 64 && ctx->linv_n == n0 && b <= kAppendInvRows) {
-        // a few points (the node's one per change): L21 row by row from the
-        // kept f64 inverse, L21[r,:]^T = L11^-1 K21[r,:]^T, one dtrmv over its
-        // lower triangle per point, rounded to f32 once -- rocBLAS strsm ran
-        // the 1 x n0 solve as ~250 small launches (6.3 ms at C4)
-        SBO_HIP(ctx->rvec.reserve(sizeof(double) * (size_t)n0));
-        double *w = ctx->rvec.as<double>();
-        for (int64_t r = 0; r < b; ++r) {
-            SBO_HIP(sbo::launch_widen(ctx->stream, L21 + r, ld, 1, n0, false, w, 1));
-            SBO_BLAS(rocblas_dtrmv(ctx->blas, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit,
-                                   (rocblas_int)n0, ctx->Linv.as<double>(), (rocblas_int)ld, w, 1));
-            SBO_HIP(sbo::launch_narrow_strided(ctx->stream, w, n0, L21 + r, ld));
-        }
-    } else if (ctx->inverse_bits == 64 && ctx->linv_n == n0 && b <= kAppendInvGemm) {
-        // a batch: L21 = K21 L11^-T as one f64 GEMM with the kept inverse
-        // (its strict upper part is zero), rounded to f32 once
-        SBO_HIP(ctx->rvec.reserve(sizeof(double) * (size_t)n0 * (size_t)b * 2));
-        double *kw = ctx->rvec.as<double>(), *cw = kw + (size_t)n0 * (size_t)b;
-        const double done = 1.0, dzero = 0.0;
-        SBO_HIP(sbo::launch_widen(ctx->stream, L21, ld, b, n0, false, kw, b));
-        SBO_BLAS(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_transpose, (rocblas_int)b,
-                               (rocblas_int)n0, (rocblas_int)n0, &done, kw, (rocblas_int)b, ctx->Linv.as<double>(),
-                               (rocblas_int)ld, &dzero, cw, (rocblas_int)b));
-        SBO_HIP(sbo::launch_narrow_2d(ctx->stream, cw, b, b, n0, L21, ld));
-    } else {
-        SBO_BLAS(rocblas_strsm(ctx->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_transpose,
-                               rocblas_diagonal_non_unit, (rocblas_int)b, (rocblas_int)n0, &one, L, (rocblas_int)ld,
-                               L21, (rocblas_int)ld));
-    }
-    // K22 -= L21 L21^T as a full b x b sgemm (rocBLAS's ssyrk ran its
-    // small-n kernels at ~250 us here; the strict upper half it also writes
-    // is never read), then the block's own factorization
-    SBO_BLAS(rocblas_sgemm(ctx->blas, rocblas_operation_none, rocblas_operation_transpose, (rocblas_int)b,
-                           (rocblas_int)b, (rocblas_int)n0, &minus_one, L21, (rocblas_int)ld, L21, (rocblas_int)ld,
-                           &one, L22, (rocblas_int)ld));
-    rocblas_int *info = ctx->info.as<rocblas_int>();
-    if (ctx->chol_blocked) {
-        if (sbo_status st = blocked_potrf(ctx, L22, b, ld, info); st != SBO_OK) return st;
-    } else {
-        SBO_BLAS(rocsolver_spotrf(ctx->blas, rocblas_fill_lower, (rocblas_int)b, L22, (rocblas_int)ld, info));
-    }
-    rocblas_int hinfo = 0;
-    SBO_HIP(hipMemcpyAsync(&hinfo, info, sizeof(hinfo), hipMemcpyDeviceToHost, ctx->stream));
-    SBO_HIP(hipStreamSynchronize(ctx->stream));
-    if (hinfo != 0) {
-        ctx->err = "sbo_append: updated block not positive definite (info=" + std::to_string(hinfo) + ")";
-        return SBO_E_NOT_SPD;
-    }
+    if (sbo_status st = append_fill(ctx, n0, b)) return st;
+    if (sbo_status st = append_panel(ctx, n0, b)) return st;
+    if (sbo_status st = append_schur(ctx, n0, b)) return st;
+    FactorHandover ho;   // (nothing but the info: a block's factorization starts no inverse)
+    if (sbo_status st = factor_block(ctx, append_L22(ctx, n0), b, ctx->cap, false, FactorOf::kAppendedBlock, ho))
+        return st;
     ctx->n = n1;
     if (sbo_status st = refresh_operand(ctx, n0)) return st;
     return fc.commit(finish(ctx, flags));

@@ -201,6 +201,123 @@ def test_blocked_cholesky_not_spd_past_first_block(mapper):
     assert msgs[0] == msgs[1] and "leading minor" in msgs[0], msgs
 
 
+@pytest.mark.parametrize("gemm", [2, 4])
+def test_chol_reserve_remakes_aux_stream(mapper, gemm):
+    """SBO_OPT_CHOL_RESERVE 0 -> 8 -> 0 on one context: each change destroys the
+    look-ahead stream, makes it again with the other CU mask and re-binds its
+    rocBLAS handle.  n = 300 with 128-column outer panels: the first outer step
+    has m3 = 172 rows below it, W2 = 128 and m4 = 44 > 0, so its trailing update
+    really runs on that stream.  The library's own update kernels (SBO_OPT_CHOL_GEMM
+    2, 4) do not depend on which CUs run them: the three factors are bitwise
+    equal, and within the backward-error bound."""
+    n = 300
+    wl = synthetic(n, 8, seed=n + 7)
+    gm = TerrainMapper(0, wl.hyper, ctx=mapper.ctx)
+    got = []
+    try:
+        gm.set_option(N.SBO_OPT_CHOL_OUTER, 128)
+        gm.set_option(N.SBO_OPT_CHOL_GEMM, gemm)
+        for reserve in (0, 8, 0):
+            gm.set_option(N.SBO_OPT_CHOL_RESERVE, reserve)
+            gm.fit(wl.x, wl.y, wl.obs)
+            got.append((gm.factor()[0], gm.order()))
+    finally:
+        gm.set_option(N.SBO_OPT_CHOL_RESERVE, 0)
+        gm.set_option(N.SBO_OPT_CHOL_OUTER, 1024)
+        gm.set_option(N.SBO_OPT_CHOL_GEMM, 4)
+    L, o = got[0]
+    K = O.rbf_fill_f32in(f32(wl.x)[o], f32(wl.y)[o])
+    L64 = L.astype(np.float64)
+    be = np.linalg.norm(L64 @ L64.T - K) / np.linalg.norm(K)
+    print(f"CHOL_GEMM {gemm}: backward error {be:.3e} (bound {10 * n * EPS32:.3e})")
+    assert be <= 10 * n * EPS32, be
+    for L2, o2 in got[1:]:
+        assert np.array_equal(o, o2) and np.array_equal(L, L2)
+
+
+def test_rocblas_trailing_update_size_threshold(dev, mapper):
+    """rocBLAS trailing updates (SBO_OPT_CHOL_GEMM 0) are ssyrk above 6144 rows
+    and one full sgemm up to there.  n = 6401 with 128-column outer panels: the
+    first trailing update has 6145 rows, the second 6017, so consecutive steps
+    take either side.  Backward error within the bound (L L^T in f64 on the
+    device: 2 n^3 flops), posterior within the contract of the default fit's."""
+    n = 6401
+    wl = synthetic(n, 24, 20, seed=n + 9)
+    gm = TerrainMapper(0, wl.hyper, ctx=mapper.ctx)
+    try:
+        gm.fit(wl.x, wl.y, wl.obs)
+        mu0, sd0 = gm.predict(wl.qx, wl.qy)
+        gm.set_option(N.SBO_OPT_CHOL_OUTER, 128)
+        gm.set_option(N.SBO_OPT_CHOL_GEMM, 0)
+        gm.fit(wl.x, wl.y, wl.obs)
+        L, _ = gm.factor()
+        o = gm.order()
+        mu, sd = gm.predict(wl.qx, wl.qy)
+    finally:
+        gm.set_option(N.SBO_OPT_CHOL_OUTER, 1024)
+        gm.set_option(N.SBO_OPT_CHOL_GEMM, 4)
+    K = torch.as_tensor(O.rbf_fill_f32in(f32(wl.x)[o], f32(wl.y)[o]), device=dev)
+    L64 = torch.as_tensor(L, device=dev).double()
+    be = float(torch.linalg.norm(L64 @ L64.T - K) / torch.linalg.norm(K))
+    e_mu, e_var = nrel(mu, mu0.astype(np.float64)), nrel(sd.astype(np.float64) ** 2, sd0.astype(np.float64) ** 2)
+    print(f"n {n}: backward error {be:.3e} (bound {10 * n * EPS32:.3e}), posterior against the default fit: "
+          f"mu {e_mu:.3e} var {e_var:.3e}")
+    assert be <= 10 * n * EPS32, be
+    assert e_mu < REL_TOL and e_var < REL_TOL, (e_mu, e_var)
+
+
+@pytest.fixture(scope="module")
+def append500(dev):
+    """500 points and the posterior of a fresh fit of all of them (library defaults)."""
+    wl = synthetic(500, 24, 20, seed=61)
+    gm = TerrainMapper(0, wl.hyper)
+    try:
+        gm.fit(wl.x, wl.y, wl.obs)
+        mu, sd = gm.predict(wl.qx, wl.qy)
+    finally:
+        gm.close()
+    return wl, mu.astype(np.float64), sd.astype(np.float64) ** 2
+
+
+@pytest.mark.parametrize("gemm", [0, 2, 4])
+@pytest.mark.parametrize("chol", [0, 1, 2])
+def test_block_append_under_factor_options(mapper, append500, chol, gemm):
+    """The block append's own factorization under non-default options: fit 300
+    points, append 200 without the re-sort.  L22 then spans two 128-column
+    blocks (SBO_OPT_CHOL_OUTER 128: an outer step with a look-ahead) at a
+    non-zero offset, with the leading dimension of the grown capacity.  The
+    factor of all 500 points is within the backward-error bound and the
+    posterior within the contract of a fresh fit's."""
+    wl, mu_ref, var_ref = append500
+    n0, n = 300, 500
+    gm = TerrainMapper(0, wl.hyper, ctx=mapper.ctx)
+    try:
+        gm.set_option(N.SBO_OPT_RESORT, 0)
+        gm.set_option(N.SBO_OPT_CHOL_OUTER, 128)
+        gm.set_option(N.SBO_OPT_CHOL_GEMM, gemm)
+        gm.set_option(N.SBO_OPT_CHOLESKY, chol)
+        gm.fit(wl.x[:n0], wl.y[:n0], wl.obs[:n0])
+        gm.append(wl.x[n0:], wl.y[n0:], wl.obs[n0:])
+        assert gm.n == n
+        L, _ = gm.factor()
+        o = gm.order()
+        mu, sd = gm.predict(wl.qx, wl.qy)
+    finally:
+        gm.set_option(N.SBO_OPT_RESORT, 25)
+        gm.set_option(N.SBO_OPT_CHOLESKY, 1)
+        gm.set_option(N.SBO_OPT_CHOL_OUTER, 1024)
+        gm.set_option(N.SBO_OPT_CHOL_GEMM, 4)
+    assert np.array_equal(np.sort(o), np.arange(n))
+    K = O.rbf_fill_f32in(f32(wl.x)[o], f32(wl.y)[o])
+    L64 = L.astype(np.float64)
+    be = np.linalg.norm(L64 @ L64.T - K) / np.linalg.norm(K)
+    e_mu, e_var = nrel(mu, mu_ref), nrel(sd.astype(np.float64) ** 2, var_ref)
+    print(f"CHOLESKY {chol} CHOL_GEMM {gemm}: backward error {be:.3e} (bound {10 * n * EPS32:.3e}), "
+          f"posterior against a fresh fit: mu {e_mu:.3e} var {e_var:.3e}")
+    assert be <= 10 * n * EPS32, be
+    assert e_mu < REL_TOL and e_var < REL_TOL, (e_mu, e_var)
+
+
 def test_jitter_retry_recovers_not_spd(mapper):
     """SBO_OPT_JITTER_RETRIES (failure recovery): a singular K
     (a duplicated point, no noise) is reported as NOT_SPD by default; with

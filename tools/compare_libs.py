@@ -2,7 +2,8 @@
 in its own process (SBO_LIB), writes the fit's tile bounds, mu/sd/lo/hi/S and the key of a few
 workloads, and the outputs are compared element by element.
 
-  python tools/compare_libs.py LIB_A LIB_B [--configs C4 C2 box]"""
+  python tools/compare_libs.py LIB_A LIB_B [--configs C4 C2 box]
+  python tools/compare_libs.py LIB_A LIB_B --factor-matrix   (fits under the Cholesky's options, appends)"""
 import argparse
 import os
 import subprocess
@@ -47,10 +48,70 @@ np.savez({path!r}, **out)
 print("ok", N.LIB_PATH)
 '''
 
+# --factor-matrix: the factorization's options and the append paths.  Per case L, alpha, the f32 view of
+# the inverse (sbo_get_inverse), mu and sd.  Compare a build with itself first: the rocBLAS paths count as
+# evidence only where they repeat.
+FACTOR_CHILD = r'''
+import hashlib, sys, numpy as np
+sys.path.insert(0, {root!r})
+from safe_bayesian_optimization_amd import TerrainMapper, synthetic
+from safe_bayesian_optimization_amd import _native as N
+out = {{}}
+DEFAULTS = ((N.SBO_OPT_CHOLESKY, 1), (N.SBO_OPT_CHOL_OUTER, 1024), (N.SBO_OPT_CHOL_GEMM, 4), (N.SBO_OPT_INV_OVERLAP, 0),
+            (N.SBO_OPT_CHOL_RESERVE, 0), (N.SBO_OPT_RESORT, 25))
+gm = None
+def record(name, wl):
+    L, alpha = gm.factor()
+    A = np.zeros((gm.n, gm.n), np.float32)
+    gm.ctx.check(N.lib().sbo_get_inverse(gm.ctx.handle, A.ctypes.data))
+    mu, sd = gm.predict(wl.qx, wl.qy)
+    for k, v in (("L", L), ("alpha", alpha), ("inv", A), ("mu", mu), ("sd", sd)):
+        v = np.ascontiguousarray(v)     # (arrays past 1 MiB: their SHA-256)
+        out[name + "_" + k] = v if v.nbytes <= 1 << 20 else np.frombuffer(hashlib.sha256(v).digest(), np.uint8)
+def fit(name, wl, n, options):
+    for k, v in DEFAULTS + tuple(options):
+        gm.set_option(k, v)
+    gm.fit(wl.x[:n], wl.y[:n], wl.obs[:n])
+    record(name, wl)
+# the option list of tests/test_gpu_parity.py::test_blocked_cholesky_matches_spotrf: (CHOLESKY, CHOL_OUTER, CHOL_GEMM)
+CHOL = [(0, 1024, 0), (2, 1024, 0), (1, 128, 0), (1, 256, 0), (1, 512, 0), (1, 1024, 0), (1, 512, 1), (1, 512, 2),
+        (1, 512, 4), (1, 512, 5), (1, 128, 4), (1, 256, 4), (1, 1024, 4), (1, 1024, 0)]
+for n in (129, 300, 2048, 4100):
+    wl = synthetic(n, 24, 20, seed=n + 3)
+    gm = TerrainMapper(0, wl.hyper)      # one context per size: every case after the first runs on used streams
+    for i, (ch, outer, gemm) in enumerate(CHOL):
+        fit(f"n{{n}}_{{i:02d}}_chol{{ch}}_outer{{outer}}_gemm{{gemm}}", wl, n,
+            ((N.SBO_OPT_CHOLESKY, ch), (N.SBO_OPT_CHOL_OUTER, outer), (N.SBO_OPT_CHOL_GEMM, gemm)))
+    if n == 4100:
+        for ov in (0, 32, 0):
+            fit(f"n{{n}}_overlap{{ov}}", wl, n, ((N.SBO_OPT_INV_OVERLAP, ov),))
+    for j, rs in enumerate((0, 8, 0)):
+        for gemm in (0, 2, 4):
+            fit(f"n{{n}}_reserve{{j}}_{{rs}}_gemm{{gemm}}", wl, n,
+                ((N.SBO_OPT_CHOL_OUTER, 128), (N.SBO_OPT_CHOL_GEMM, gemm), (N.SBO_OPT_CHOL_RESERVE, rs)))
+    gm.close()
+wl = synthetic(6401, 24, 20, seed=6410)     # rocBLAS trailing updates on both sides of the ssyrk / sgemm switch at 6144 rows
+gm = TerrainMapper(0, wl.hyper)
+for gemm in (0, 1):
+    fit(f"n6401_outer128_gemm{{gemm}}", wl, 6401, ((N.SBO_OPT_CHOL_OUTER, 128), (N.SBO_OPT_CHOL_GEMM, gemm)))
+gm.close()
+wl = synthetic(600, 24, 20, seed=11)
+for b, resort in ((1, 0), (200, 0), (200, 25)):     # (200 of 300 with SBO_OPT_RESORT 25: the re-sort)
+    for ch in (1, 0):
+        gm = TerrainMapper(0, wl.hyper)
+        fit(f"append{{b}}_resort{{resort}}_chol{{ch}}_fit", wl, 300, ((N.SBO_OPT_CHOLESKY, ch), (N.SBO_OPT_RESORT, resort)))
+        gm.append(wl.x[300:300 + b], wl.y[300:300 + b], wl.obs[300:300 + b])
+        record(f"append{{b}}_resort{{resort}}_chol{{ch}}", wl)
+        out[f"append{{b}}_resort{{resort}}_chol{{ch}}_order"] = gm.order()
+        gm.close()
+np.savez({path!r}, **out)
+print("ok", N.LIB_PATH, len(out), "arrays")
+'''
 
-def run(lib, configs, path):
+
+def run(lib, configs, path, child=CHILD):
     env = dict(os.environ, SBO_LIB=os.path.abspath(lib))
-    r = subprocess.run([sys.executable, "-c", CHILD.format(root=ROOT, configs=configs, path=path)], env=env,
+    r = subprocess.run([sys.executable, "-c", child.format(root=ROOT, configs=configs, path=path)], env=env,
                        capture_output=True, text=True, timeout=600)
     if r.returncode != 0:
         raise SystemExit(f"{lib}: {r.stderr[-3000:]}")
@@ -63,17 +124,22 @@ def main():
     p.add_argument("lib_a")
     p.add_argument("lib_b")
     p.add_argument("--configs", nargs="+", default=["C4", "C2", "box"])
+    p.add_argument("--factor-matrix", action="store_true",
+                   help="the factorization's option matrix and the append paths instead of the ticks")
     a = p.parse_args()
-    A = run(a.lib_a, a.configs, os.environ.get("CMP_OUT", "/tmp") + "/cmp_a.npz")
-    B = run(a.lib_b, a.configs, os.environ.get("CMP_OUT", "/tmp") + "/cmp_b.npz")
-    same = True
+    child = FACTOR_CHILD if a.factor_matrix else CHILD
+    A = run(a.lib_a, a.configs, os.environ.get("CMP_OUT", "/tmp") + "/cmp_a.npz", child)
+    B = run(a.lib_b, a.configs, os.environ.get("CMP_OUT", "/tmp") + "/cmp_b.npz", child)
+    same = sorted(A) == sorted(B)
     for k in sorted(A):
-        eq = np.array_equal(A[k], B[k])
-        d = "" if eq else f" max|d| {np.abs(A[k].astype(np.float64) - B[k].astype(np.float64)).max():.3e}, " \
-                          f"{np.count_nonzero(A[k] != B[k])} of {A[k].size} differ"
-        print(f"{k:14s} {'bitwise equal' if eq else 'DIFFERENT'}{d}")
+        eq = k in B and A[k].shape == B[k].shape and np.array_equal(A[k], B[k])
+        d = "" if eq or k not in B or A[k].shape != B[k].shape else \
+            f" max|d| {np.abs(A[k].astype(np.float64) - B[k].astype(np.float64)).max():.3e}, " \
+            f"{np.count_nonzero(A[k] != B[k])} of {A[k].size} differ"
+        if not (a.factor_matrix and eq):     # (the matrix: hundreds of arrays, only the different ones by name)
+            print(f"{k:14s} {'bitwise equal' if eq else 'DIFFERENT'}{d}")
         same &= eq
-    print("ALL BITWISE EQUAL" if same else "OUTPUTS DIFFER")
+    print(f"{len(A)} arrays: " + ("ALL BITWISE EQUAL" if same else "OUTPUTS DIFFER"))
     return 0 if same else 1
 
 

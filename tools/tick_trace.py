@@ -23,8 +23,8 @@ HEADER = """\
 """
 
 
-def listing(d, out):
-    """Per-queue kernel lists; ids do not depend on how concurrent queues interleave in time."""
+def listing(d, out, header=HEADER):
+    """Per-queue kernel lists under `header`; ids do not depend on how concurrent queues interleave in time."""
     f = glob.glob(d + "/**/*kernel_trace.csv", recursive=True)[0]
     rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
     queues = {}
@@ -38,7 +38,7 @@ def listing(d, out):
         for n in ks:
             ids.setdefault(n, len(ids))
     with open(out, "w") as fo:
-        fo.write(HEADER)
+        fo.write(header)
         fo.write(f"# total kernels {len(rows)}, queues {len(queues)}, distinct kernels {len(ids)}\n")
         for i, ks in enumerate(queues.values()):
             fo.write(f"queue {i}: {len(ks)} kernels\n")
