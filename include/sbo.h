@@ -144,6 +144,83 @@ SBO_API sbo_status sbo_tick(sbo_ctx *ctx, const float *qx, const float *qy, int6
                             float *mu, float *sd, double *lo, double *hi, uint8_t *safe,
                             sbo_key *out, uint32_t flags);
 
+/* sbo_tick with a kept posterior: the node's steady state, "one measurement
+ * arrived (sbo_append), give me the map and the subgoal".  Arguments,
+ * outputs, flags, status codes and error strings are sbo_tick's.
+ *
+ * The first call runs sbo_tick's full sweep and keeps, per sweep position, the
+ * f64 mean and variance (about 28 B per query, owned by the context: state,
+ * not workspace -- sbo_trim leaves it, sbo_stream_reset frees it).  A later
+ * call with the same queries after block appends adds only the R appended
+ * rows' share to the kept posterior,
+ *     v = L^-1[n_map:n, 0:n] k*(q),  var -= sum_r v_r^2,  mu += sum_r v_r z_r
+ * (R n multiply-adds per query instead of n^2 / 2), and runs the acquisition
+ * from it.  That path needs: a kept posterior of the same fit epoch (sbo_fit,
+ * a re-sorting append, sbo_import_state, a failed fit or append start a new
+ * one; a block append does not), of the same sweep (fast / precise) and the
+ * same m; bitwise equal queries; the fit's f64 inverse current
+ * (SBO_OPT_INVERSE_BITS 64, not an imported state);
+ * R <= SBO_OPT_STREAM_MAX_ROWS; and the accumulated cutoff bound within the
+ * sweep's skip budget.  Anything else takes the full sweep and keeps its
+ * posterior; on that path every output is bitwise sbo_tick's.  No call is
+ * refused for streaming reasons; sbo_get_stream says what the last one did.
+ *
+ * Synchronisation: before an update the queries are compared on the device
+ * with the kept ones and the appended rows' norms are reduced; their result
+ * (24 bytes) is read back with one synchronisation of the context's stream,
+ * also under SBO_ASYNC.  The full path synchronises as sbo_tick does.
+ *
+ * The update skips a (128-query block, 64-column k-tile) pair when the two
+ * bounding boxes put every K* entry below 2^-L.  With SBO_OPT_TILE_SKIP -1, L
+ * is the smallest exponent whose worst-case effect, from
+ * d_r = sf2 2^-L |L^-1_r|_1 over the appended rows r,
+ *     variance: 2 sqrt(sf2) sqrt(sum d_r^2) + sum d_r^2,   mean: sum d_r |z_r|,
+ * stays within 2^-s (s = SBO_OPT_STREAM_SHARE) of the budget of the sweep in
+ * effect: 2^-B sf2 and 2^-B sf for the fast sweep, 2^-B times the smallest
+ * probe variance (and 2^-B sf) for the precise one.  The bounds spent add up
+ * in err_var / err_mean until the next full sweep, which a call takes
+ * (reason BUDGET) before they would exceed the budget.  SBO_OPT_TILE_SKIP 0:
+ * dense; a fixed L spends its own bound; L >= 150 drops only exact zeros
+ * (bitwise the dense update). */
+SBO_API sbo_status sbo_tick_stream(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, double beta,
+                                   double f_min, sbo_score score, int64_t index_offset, float *mu, float *sd,
+                                   double *lo, double *hi, uint8_t *safe, sbo_key *out, uint32_t flags);
+
+/* What the last sbo_tick_stream did and why.  The caller sets struct_size to
+ * sizeof(sbo_stream_info); the library writes no more than that many bytes. */
+typedef enum sbo_stream_reason {
+    SBO_STREAM_FIRST = 0,            /* no kept posterior yet */
+    SBO_STREAM_UPDATED = 1,          /* the update path ran (rows = 0: acquisition only) */
+    SBO_STREAM_QUERIES_CHANGED = 2,  /* another m, or a query not bitwise the kept one */
+    SBO_STREAM_REFIT = 3,            /* another fit epoch, or another sweep (fast / precise) in effect */
+    SBO_STREAM_NO_INVERSE = 4,       /* no current f64 inverse / z to read the appended rows from */
+    SBO_STREAM_ROWS_OVER_CAP = 5,    /* more appended rows than SBO_OPT_STREAM_MAX_ROWS */
+    SBO_STREAM_BUDGET = 6,           /* the accumulated cutoff bound would exceed the skip budget */
+    SBO_STREAM_RESET = 7             /* first call after sbo_stream_reset */
+} sbo_stream_reason;
+typedef struct sbo_stream_info {
+    uint32_t struct_size;
+    int32_t path;                 /* 0 full sweep, 1 update */
+    int32_t reason;               /* sbo_stream_reason */
+    int32_t cutoff_log2;          /* the update's L (0: dense) */
+    int64_t rows;                 /* R: rows appended since the kept posterior's last tick */
+    int64_t n_map;                /* training rows the kept posterior had seen before this call */
+    int64_t m;
+    int64_t updates_since_full;
+    int64_t tiles_total;          /* (query block, k-tile) pairs of the last update */
+    int64_t tiles_kept;           /* ... and those it multiplied */
+    double err_var, err_mean;     /* worst-case bounds spent since the last full sweep */
+    double budget_var, budget_mean;
+} sbo_stream_info;
+SBO_API sbo_status sbo_get_stream(const sbo_ctx *ctx, sbo_stream_info *out);
+/* Drop the kept posterior and free its memory; the next sbo_tick_stream runs
+ * the full sweep (reason RESET). */
+SBO_API sbo_status sbo_stream_reset(sbo_ctx *ctx);
+/* Test accessor: the kept f64 mean and variance (sf2 - |V|^2, not clamped) in
+ * the caller's order, host buffers of cap >= m doubles each.  SBO_E_STATE
+ * without a kept posterior. */
+SBO_API sbo_status sbo_debug_stream_state(sbo_ctx *ctx, double *mu64, double *var64, int64_t cap);
+
 /* Sweep work of each query under the current fit: builds the tick's tile
  * plan for these queries (no sweep) and writes cost[i] = the k-tiles its
  * 128-query block multiplies, summed over row blocks and weighted by their
@@ -512,6 +589,14 @@ SBO_API sbo_status sbo_kd_order(const float *x, const float *y, int64_t n, int64
  * option change or a hyper-parameter change takes SBO_OPT_INV_OZ digits.
  * sbo_get_inverse_check's digits say which ran. */
 #define SBO_OPT_INV_OZ_ADAPT 29
+/* SBO_OPT_STREAM_SHARE (s in [0, 20], default 10): each update of
+ * sbo_tick_stream may spend 2^-s of the sweep's skip budget on its K* cutoff
+ * (2^-10: a thousand updates before the bounds alone force a full sweep). */
+#define SBO_OPT_STREAM_SHARE 30
+/* SBO_OPT_STREAM_MAX_ROWS (R in [0, 65536], default 64): an sbo_tick_stream
+ * with more rows appended since its last tick than this takes the full sweep
+ * (0: every call after an append does). */
+#define SBO_OPT_STREAM_MAX_ROWS 31
 SBO_API sbo_status sbo_set_option(sbo_ctx *ctx, int option, int64_t value);
 
 /* The last inverse check (SBO_OPT_INV_CHECK) of the current fit, on m = 31
@@ -548,7 +633,8 @@ SBO_API sbo_status sbo_get_inverse_check(const sbo_ctx *ctx, sbo_inv_check *out)
  * packed operands -- about 2.1 GB at N = 16384, 8.5 GB at 32768 -- the inverse
  * check's, the append re-sort's staging copy and the precise sweep's K* table,
  * up to SBO_OPT_TABLE_MB); they are allocated again on the next call that
- * needs them.  The fitted state (factor, inverse, operands) stays.  Waits for
+ * needs them.  The fitted state (factor, inverse, operands) stays, and so does
+ * sbo_tick_stream's kept posterior (sbo_stream_reset frees that).  Waits for
  * the context's streams. */
 SBO_API sbo_status sbo_trim(sbo_ctx *ctx);
 

@@ -89,6 +89,33 @@ public:
     }
     // Serve a map over the given grid (row-major, width x height).
     TerrainMap grid(const std::vector<double> &gx, const std::vector<double> &gy, int width, int height) {
+        return serve(gx, gy, width, height, nullptr, 0.0, 0.0);
+    }
+    // The node's steady state, "a measurement arrived: append(), then the map
+    // and the grid argmax": the same map through sbo_tick_stream, which keeps
+    // the posterior of this grid between calls and after a block append adds
+    // only the appended rows' share (stream_info() says which path ran).
+    // *key: the argmax of the width Q(:,1) - Q(:,0) over the safe set for
+    // (beta, f_min), -1 when no cell is safe.
+    TerrainMap tick_stream(const std::vector<double> &gx, const std::vector<double> &gy, int width, int height,
+                           double beta, double f_min, sbo_key *key) {
+        sbo_key k{0.0, -1};
+        TerrainMap r = serve(gx, gy, width, height, &k, beta, f_min);
+        if (key) *key = k;
+        return r;
+    }
+    sbo_stream_info stream_info() const {
+        sbo_stream_info info{};
+        info.struct_size = (uint32_t)sizeof(info);
+        (void)sbo_get_stream(ctx_.get(), &info);
+        return info;
+    }
+    const std::string &last_error() const { return err_; }
+
+private:
+    // key null: sbo_predict; else sbo_tick_stream
+    TerrainMap serve(const std::vector<double> &gx, const std::vector<double> &gy, int width, int height,
+                     sbo_key *key, double beta, double f_min) {
         TerrainMap r;
         const size_t m = gx.size();
         if (m != gy.size() || m != (size_t)width * (size_t)height) {
@@ -98,8 +125,11 @@ public:
         std::vector<float> qx(gx.begin(), gx.end()), qy(gy.begin(), gy.end());
         r.values.resize(m);
         r.uncertainties.resize(m);
-        const sbo_status st = sbo_predict(ctx_.get(), qx.data(), qy.data(), (int64_t)m, r.values.data(),
-                                          r.uncertainties.data(), 0);
+        const sbo_status st =
+            key ? sbo_tick_stream(ctx_.get(), qx.data(), qy.data(), (int64_t)m, beta, f_min, SBO_SCORE_WIDTH, 0,
+                                  r.values.data(), r.uncertainties.data(), nullptr, nullptr, nullptr, key, 0)
+                : sbo_predict(ctx_.get(), qx.data(), qy.data(), (int64_t)m, r.values.data(), r.uncertainties.data(),
+                              0);
         if (st != SBO_OK) {
             r.message = ctx_.last_error();
             return r;
@@ -112,9 +142,6 @@ public:
         r.y_coords = gy;
         return r;
     }
-    const std::string &last_error() const { return err_; }
-
-private:
     bool ok(sbo_status s) {
         if (s == SBO_OK) return true;
         err_ = std::string(sbo_status_string(s)) + ": " + ctx_.last_error();

@@ -35,7 +35,10 @@ EXPORTS = (
     "sbo_polygon_correct", "sbo_polydist", "sbo_point_within", "sbo_project_subgoal", "sbo_get_precision",
     "sbo_kd_order", "sbo_get_probe", "sbo_keys_reduce", "sbo_get_inverse_check", "sbo_trim", "sbo_warmup",
     "sbo_debug_gz_gemm", "sbo_debug_gz_gemm_packed", "sbo_debug_x3_operand", "sbo_debug_plan",
+    "sbo_tick_stream", "sbo_get_stream", "sbo_stream_reset", "sbo_debug_stream_state",
 )
+# sbo_stream_reason (include/sbo.h, sbo_get_stream)
+STREAM_REASONS = ("FIRST", "UPDATED", "QUERIES_CHANGED", "REFIT", "NO_INVERSE", "ROWS_OVER_CAP", "BUDGET", "RESET")
 # the sliced GEMM's flags (include/sbo.h, sbo_debug_gz_gemm)
 SBO_GZ_TRI_A = 1
 SBO_GZ_TRANS_A = 2
@@ -74,6 +77,8 @@ SBO_OPT_PLAN_BLOCK = 26
 SBO_OPT_PROBE_SIZE = 27
 SBO_OPT_INV_OZ_MIN = 28
 SBO_OPT_INV_OZ_ADAPT = 29
+SBO_OPT_STREAM_SHARE = 30
+SBO_OPT_STREAM_MAX_ROWS = 31
 
 
 class SboError(RuntimeError):
@@ -108,6 +113,14 @@ class sbo_inv_check(ctypes.Structure):
                 ("err_fallback", ctypes.c_double), ("tol", ctypes.c_double), ("var_max", ctypes.c_double),
                 ("ms", ctypes.c_double), ("err_mean", ctypes.c_double), ("mean_max", ctypes.c_double),
                 ("err_mean_fallback", ctypes.c_double), ("kept_digits", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class sbo_stream_info(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("path", ctypes.c_int32), ("reason", ctypes.c_int32),
+                ("cutoff_log2", ctypes.c_int32), ("rows", ctypes.c_int64), ("n_map", ctypes.c_int64),
+                ("m", ctypes.c_int64), ("updates_since_full", ctypes.c_int64), ("tiles_total", ctypes.c_int64),
+                ("tiles_kept", ctypes.c_int64), ("err_var", ctypes.c_double), ("err_mean", ctypes.c_double),
+                ("budget_var", ctypes.c_double), ("budget_mean", ctypes.c_double)]
 
 
 _lib = None
@@ -159,6 +172,14 @@ def lib():
     L.sbo_argmax.restype = st
     L.sbo_tick.argtypes = [vp, vp, vp, i64, dbl, dbl, i32, i64, vp, vp, vp, vp, vp, vp, u32]
     L.sbo_tick.restype = st
+    L.sbo_tick_stream.argtypes = L.sbo_tick.argtypes
+    L.sbo_tick_stream.restype = st
+    L.sbo_get_stream.argtypes = [vp, ctypes.POINTER(sbo_stream_info)]
+    L.sbo_get_stream.restype = st
+    L.sbo_stream_reset.argtypes = [vp]
+    L.sbo_stream_reset.restype = st
+    L.sbo_debug_stream_state.argtypes = [vp, vp, vp, i64]
+    L.sbo_debug_stream_state.restype = st
     L.sbo_query_cost.argtypes = [vp, vp, vp, i64, vp, u32]
     L.sbo_query_cost.restype = st
     L.sbo_key_combine.argtypes = [sbo_key, sbo_key]

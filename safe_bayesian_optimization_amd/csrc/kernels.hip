@@ -2999,13 +2999,50 @@ __device__ __forceinline__ void compute_sets_one(T mu, T sd, double beta, double
     safe = lo > f_min;
 }
 
+// One position's acquisition from its variance before the clamp (f64) and its
+// mean (f32): the outputs at caller index o and the thread's argmax candidate.
+__device__ __forceinline__ void acquire_one(double vd, float mu, int64_t o, double beta, double f_min, int score_kind,
+                                            int64_t index_offset, float *__restrict__ mu_out,
+                                            float *__restrict__ sd_out, double *__restrict__ lo_out,
+                                            double *__restrict__ hi_out, uint8_t *__restrict__ safe_out, double &bs,
+                                            int64_t &bi) {
+    float var = vd > 0.0 ? (float)vd : 0.0f;
+    const float sd = __fsqrt_rn(var);
+    if (mu_out) mu_out[o] = mu;
+    if (sd_out) sd_out[o] = sd;
+    double lo, hi;
+    bool safe;
+    compute_sets_one(mu, sd, beta, f_min, lo, hi, safe);
+    if (lo_out) lo_out[o] = lo;
+    if (hi_out) hi_out[o] = hi;
+    if (safe_out) safe_out[o] = safe ? 1 : 0;
+    const double score = score_kind == SBO_SCORE_UCB ? hi : __dsub_rn(hi, lo);
+    if (safe && score == score) { bs = score; bi = index_offset + o; }
+}
+
+// The acquisition from a kept posterior (sbo_tick_stream's update path).
+__global__ __launch_bounds__(kAcqThreads) void acquire_kept_kernel(
+    const double *__restrict__ mu64, const double *__restrict__ var64, int64_t ms, double beta, double f_min,
+    int score_kind, int64_t index_offset, const int32_t *__restrict__ perm, float *__restrict__ mu_out,
+    float *__restrict__ sd_out, double *__restrict__ lo_out, double *__restrict__ hi_out,
+    uint8_t *__restrict__ safe_out, sbo_key *__restrict__ keys) {
+    const int64_t i = (int64_t)blockIdx.x * kAcqThreads + threadIdx.x;
+    double bs = 0.0;
+    int64_t bi = -1;
+    if (i < ms && perm[i] >= 0)
+        acquire_one(var64[i], (float)mu64[i], (int64_t)perm[i], beta, f_min, score_kind, index_offset, mu_out, sd_out,
+                    lo_out, hi_out, safe_out, bs, bi);
+    block_reduce_key(bs, bi, keys + blockIdx.x);
+}
+
 template <class PT>
 __global__ __launch_bounds__(kAcqThreads) void acquire_kernel(
     const PT *__restrict__ part, const PT *__restrict__ mean, int nI, int64_t ldp, int64_t m,
     double sf2, double beta, double f_min, int score_kind, int64_t index_offset,
     const int32_t *__restrict__ perm, float *__restrict__ mu_out, float *__restrict__ sd_out,
     double *__restrict__ lo_out, double *__restrict__ hi_out, uint8_t *__restrict__ safe_out,
-    sbo_key *__restrict__ keys, const unsigned long long *__restrict__ nemask) {
+    sbo_key *__restrict__ keys, const unsigned long long *__restrict__ nemask, double *__restrict__ keep_mu,
+    double *__restrict__ keep_var) {
     const int64_t i = (int64_t)blockIdx.x * kAcqThreads + threadIdx.x;
     double bs = 0.0;
     int64_t bi = -1;
@@ -3029,21 +3066,13 @@ __global__ __launch_bounds__(kAcqThreads) void acquire_kernel(
         }
         for (; I < nI; ++I)
             if (!ne || ((ne[I >> 6] >> (I & 63)) & 1ull)) s += (double)part[(int64_t)I * ldp + i];
-        double vd = sf2 - s;
-        float var = vd > 0.0 ? (float)vd : 0.0f;
-        const float sd = __fsqrt_rn(var);
-        const float mu = (float)mean[i];
+        const double vd = sf2 - s;
+        const PT mean_i = mean[i];
+        if (keep_var) keep_var[i] = vd;
+        if (keep_mu) keep_mu[i] = (double)mean_i;
         const int64_t o = perm ? (int64_t)perm[i] : i;  // caller's index of sweep position i
-        if (mu_out) mu_out[o] = mu;
-        if (sd_out) sd_out[o] = sd;
-        double lo, hi;
-        bool safe;
-        compute_sets_one(mu, sd, beta, f_min, lo, hi, safe);
-        if (lo_out) lo_out[o] = lo;
-        if (hi_out) hi_out[o] = hi;
-        if (safe_out) safe_out[o] = safe ? 1 : 0;
-        const double score = score_kind == SBO_SCORE_UCB ? hi : __dsub_rn(hi, lo);
-        if (safe && score == score) { bs = score; bi = index_offset + o; }
+        acquire_one(vd, (float)mean_i, o, beta, f_min, score_kind, index_offset, mu_out, sd_out, lo_out, hi_out,
+                    safe_out, bs, bi);
     }
     block_reduce_key(bs, bi, keys + blockIdx.x);
 }
@@ -3559,20 +3588,30 @@ hipError_t launch_predict(hipStream_t s, const float *aug, const float *kcoord, 
 hipError_t launch_acquire(hipStream_t s, const float *part, const float *mean, int nI, int64_t ldp,
                           int64_t m, float sf2, double beta, double f_min, int score_kind,
                           int64_t index_offset, const int32_t *perm, float *mu, float *sd, double *lo,
-                          double *hi, uint8_t *safe, sbo_key *block_keys, const unsigned long long *nonempty) {
+                          double *hi, uint8_t *safe, sbo_key *block_keys, const unsigned long long *nonempty,
+                          double *keep_mu, double *keep_var) {
     hipLaunchKernelGGL(acquire_kernel<float>, dim3((unsigned)acq_blocks(m)), dim3(kAcqThreads), 0, s, part, mean,
                        nI, ldp, m, (double)sf2, beta, f_min, score_kind, index_offset, perm, mu, sd, lo, hi, safe,
-                       block_keys, nonempty);
+                       block_keys, nonempty, keep_mu, keep_var);
     return hipGetLastError();
 }
 
 hipError_t launch_acquire(hipStream_t s, const double *part, const double *mean, int nI, int64_t ldp,
                           int64_t m, double sf2, double beta, double f_min, int score_kind,
                           int64_t index_offset, const int32_t *perm, float *mu, float *sd, double *lo,
-                          double *hi, uint8_t *safe, sbo_key *block_keys, const unsigned long long *nonempty) {
+                          double *hi, uint8_t *safe, sbo_key *block_keys, const unsigned long long *nonempty,
+                          double *keep_mu, double *keep_var) {
     hipLaunchKernelGGL(acquire_kernel<double>, dim3((unsigned)acq_blocks(m)), dim3(kAcqThreads), 0, s, part, mean,
                        nI, ldp, m, sf2, beta, f_min, score_kind, index_offset, perm, mu, sd, lo, hi, safe,
-                       block_keys, nonempty);
+                       block_keys, nonempty, keep_mu, keep_var);
+    return hipGetLastError();
+}
+
+hipError_t launch_acquire_kept(hipStream_t s, const double *mu64, const double *var64, int64_t ms, double beta,
+                               double f_min, int score_kind, int64_t index_offset, const int32_t *perm, float *mu,
+                               float *sd, double *lo, double *hi, uint8_t *safe, sbo_key *block_keys) {
+    hipLaunchKernelGGL(acquire_kept_kernel, dim3((unsigned)acq_blocks(ms)), dim3(kAcqThreads), 0, s, mu64, var64, ms,
+                       beta, f_min, score_kind, index_offset, perm, mu, sd, lo, hi, safe, block_keys);
     return hipGetLastError();
 }
 

@@ -731,6 +731,7 @@ struct TickRequest {
     Sweep sweep = Sweep::kCtx;
     QueryOrder order;
     bool quiet = false;          // no profile events, no counters (the probe is not a tick)
+    bool keep = false;           // sbo_tick_stream's full path: capture the posterior into ctx->keep
 };
 // What SBO_OPT_PRECISE_KERNEL's value selects: the operand's layout (0 f64
 // tiles, 1 int8 digit tiles, 2 int8 with exponents shared by k-tile pairs),
@@ -826,6 +827,7 @@ struct FitCommit {
     }
     ~FitCommit() {
         if (committed) return;
+        ++ctx->fit_epoch;   // (whatever follows is another model: a kept posterior is not updated into it)
         ctx->fitted = false;
         ctx->linv_n = 0;
         drain_guard(ctx);
@@ -2341,15 +2343,50 @@ sbo_status tick_acquire(sbo_ctx *ctx, const TickRequest &rq, const TickPlan &p) 
     const int64_t nb = sbo::acq_blocks(p.ms);
     sbo_key *bkeys = ctx->keys.as<sbo_key>();
     const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
+    double *kmu = rq.keep ? ctx->keep.mu64.as<double>() : nullptr;
+    double *kvar = rq.keep ? ctx->keep.var64.as<double>() : nullptr;
     if (p.precise)
         SBO_HIP(sbo::launch_acquire(ctx->stream, ctx->part.as<double>(), ctx->mean.as<double>(), (int)p.nI, p.ldp,
                                     p.ms, sf2, rq.beta, rq.f_min, rq.score, rq.index_offset, p.perm, rq.mu, rq.sd,
-                                    rq.lo, rq.hi, rq.safe, bkeys, nonempty));
+                                    rq.lo, rq.hi, rq.safe, bkeys, nonempty, kmu, kvar));
     else
         SBO_HIP(sbo::launch_acquire(ctx->stream, ctx->part.as<float>(), ctx->mean.as<float>(), (int)p.nI, p.ldp,
                                     p.ms, (float)sf2, rq.beta, rq.f_min, rq.score, rq.index_offset, p.perm, rq.mu,
-                                    rq.sd, rq.lo, rq.hi, rq.safe, bkeys, nonempty));
+                                    rq.sd, rq.lo, rq.hi, rq.safe, bkeys, nonempty, kmu, kvar));
     SBO_HIP(sbo::launch_reduce_keys(ctx->stream, bkeys, nb, rq.key ? rq.key : bkeys + nb));
+    return SBO_OK;
+}
+
+// The kept posterior's buffers for a full sweep of p (sbo_tick_stream), and,
+// after the acquisition wrote mu64 / var64, its sweep order, block boxes and
+// bookkeeping.  The state counts as kept only once both ran.
+sbo_status stream_reserve(sbo_ctx *ctx, const TickPlan &p) {
+    sbo::StreamKeep &k = ctx->keep;
+    k.valid = false;
+    const size_t ms = (size_t)p.ms;
+    SBO_HIP(k.mu64.reserve(sizeof(double) * ms));
+    SBO_HIP(k.var64.reserve(sizeof(double) * ms));
+    SBO_HIP(k.qx.reserve(sizeof(float) * ms));
+    SBO_HIP(k.qy.reserve(sizeof(float) * ms));
+    SBO_HIP(k.perm.reserve(sizeof(int32_t) * ms));
+    SBO_HIP(k.qbox.reserve(sizeof(float4) * (size_t)p.nQ));
+    SBO_HIP(k.head.reserve(sizeof(sbo::StreamHead) + sizeof(unsigned long long)));
+    // (padded positions, perm < 0, are never written by the acquisition and never read by anyone)
+    return SBO_OK;
+}
+sbo_status stream_capture(sbo_ctx *ctx, const TickRequest &rq, const TickPlan &p) {
+    sbo::StreamKeep &k = ctx->keep;
+    SBO_HIP(sbo::launch_stream_keep(ctx->stream, p.qx, p.qy, p.perm, p.ms, k.qx.as<float>(), k.qy.as<float>(),
+                                    k.perm.as<int32_t>(), k.qbox.as<float4>()));
+    k.m = rq.m;
+    k.ms = p.ms;
+    k.n_map = ctx->n;
+    k.epoch = ctx->fit_epoch;
+    k.precise = p.precise;
+    k.err_var = k.err_mean = 0.0;
+    k.updates = 0;
+    k.valid = true;
+    k.was_reset = false;
     return SBO_OK;
 }
 
@@ -2378,7 +2415,138 @@ sbo_status run_tick(sbo_ctx *ctx, const TickRequest &rq, TickPlan *plan_out) {
         st = sweep_fast_f32(ctx, p);
     }
     if (st != SBO_OK) return st;
-    return tick_acquire(ctx, rq, p);
+    if (!rq.keep) return tick_acquire(ctx, rq, p);
+    if ((st = stream_reserve(ctx, p)) != SBO_OK) return st;
+    if ((st = tick_acquire(ctx, rq, p)) != SBO_OK) return st;
+    return stream_capture(ctx, rq, p);
+}
+
+// ------------------------------------------------------------ streaming tick
+static_assert(sizeof(sbo_stream_info) == 96, "sbo_stream_info: the bindings mirror this layout");
+
+// The skip budget of the sweep in effect (absolute, on any variance / mean):
+// skip_budget_for's tolerance of the fast sweep and of the precise plan
+// (precise_budget).
+void stream_budget(const sbo_ctx *ctx, double &var, double &mean) {
+    const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
+    const double share = std::ldexp(1.0, -ctx->skip_budget);
+    var = share * (ctx->precise ? std::min(std::max(ctx->probe_vmin, 1e-12 * sf2), sf2) : sf2);
+    mean = share * std::sqrt(sf2);
+}
+
+// Worst-case effect of dropping K* entries below 2^-L on an update over rows
+// whose 1-norms give sum_l1sq and sum_l1z (sbo::StreamHead): with
+// d_r = sf2 2^-L |L^-1_r|_1 bounding |dv_r|, and |v|_2^2 <= var_old <= sf2,
+//   |d var| <= 2 sqrt(sf2) |d|_2 + |d|_2^2,   |d mu| <= sum_r d_r |z_r|.
+void stream_bounds(double sf2, int L, const sbo::StreamHead &h, double &var, double &mean) {
+    const double s = sf2 * std::ldexp(1.0, -L), d2 = s * s * h.sum_l1sq;
+    var = 2.0 * std::sqrt(sf2) * std::sqrt(d2) + d2;
+    mean = s * h.sum_l1z;
+}
+
+// The cutoff of one update and the bounds it spends: the context's fixed
+// cutoff, or (SBO_OPT_TILE_SKIP -1) the smallest L whose bounds stay within
+// 2^-SBO_OPT_STREAM_SHARE of the budget.  L = 0: dense (also where only
+// L >= 150 would do, which drops nothing but exact zeros).
+int stream_cutoff(const sbo_ctx *ctx, const sbo::StreamHead &h, double budget_var, double budget_mean, double &var,
+                  double &mean) {
+    const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
+    var = mean = 0.0;
+    if (ctx->skip_log2 >= 0) {
+        if (ctx->skip_log2 > 0 && ctx->skip_log2 < 150) stream_bounds(sf2, ctx->skip_log2, h, var, mean);
+        return ctx->skip_log2;
+    }
+    const double share = std::ldexp(1.0, -ctx->stream_share);
+    for (int L = 16; L < 150; ++L) {
+        stream_bounds(sf2, L, h, var, mean);
+        if (var <= share * budget_var && mean <= share * budget_mean) return L;
+    }
+    var = mean = 0.0;
+    return 0;
+}
+
+// sbo_tick_stream over queries already on the device: the path decision
+// (include/sbo.h), then either the update of the kept posterior and the
+// acquisition from it, or run_tick with the capture.
+sbo_status run_tick_stream(sbo_ctx *ctx, TickRequest rq) {
+    sbo::StreamKeep &k = ctx->keep;
+    const int64_t n = ctx->n;
+    const int64_t R = k.valid ? n - k.n_map : 0;
+    sbo_stream_info info{};
+    info.struct_size = (uint32_t)sizeof(info);
+    info.m = rq.m;
+    info.rows = std::max<int64_t>(R, 0);
+    info.n_map = k.valid ? k.n_map : 0;
+    stream_budget(ctx, info.budget_var, info.budget_mean);
+    int reason = SBO_STREAM_UPDATED;
+    if (!k.valid)
+        reason = k.was_reset ? SBO_STREAM_RESET : SBO_STREAM_FIRST;
+    else if (k.epoch != ctx->fit_epoch || k.precise != ctx->precise)
+        reason = SBO_STREAM_REFIT;
+    else if (k.m != rq.m)
+        reason = SBO_STREAM_QUERIES_CHANGED;
+    else if (!(ctx->has_factor && ctx->inverse_bits == 64 && ctx->linv_n == n && ctx->z_n == n && R >= 0))
+        reason = SBO_STREAM_NO_INVERSE;
+    else if (R > ctx->stream_max_rows)
+        reason = SBO_STREAM_ROWS_OVER_CAP;
+    sbo::StreamHead h{};
+    sbo::StreamHead *dh = k.head.as<sbo::StreamHead>();
+    double spend_var = 0.0, spend_mean = 0.0;
+    int L = 0;
+    if (reason == SBO_STREAM_UPDATED) {
+        // the queries against the kept ones and the appended rows' norms: one readback, one sync
+        SBO_HIP(hipMemsetAsync(dh, 0, sizeof(sbo::StreamHead) + sizeof(unsigned long long), ctx->stream));
+        SBO_HIP(sbo::launch_stream_compare(ctx->stream, rq.qx, rq.qy, k.qx.as<float>(), k.qy.as<float>(),
+                                           k.perm.as<int32_t>(), k.ms, dh));
+        if (R > 0) {
+            SBO_HIP(k.l1.reserve(sbo::update_l1_bytes(R)));
+            SBO_HIP(sbo::launch_update_bound_sums(ctx->stream, ctx->Linv.as<double>(), ctx->cap, k.n_map, n,
+                                                  ctx->zvec.as<double>(), k.l1.as<double>(), dh));
+        }
+        SBO_HIP(hipMemcpyAsync(&h, dh, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+        SBO_HIP(hipStreamSynchronize(ctx->stream));
+        if (h.mismatch) {
+            reason = SBO_STREAM_QUERIES_CHANGED;
+        } else if (R > 0) {
+            L = stream_cutoff(ctx, h, info.budget_var, info.budget_mean, spend_var, spend_mean);
+            if (k.err_var + spend_var > info.budget_var || k.err_mean + spend_mean > info.budget_mean)
+                reason = SBO_STREAM_BUDGET;
+        }
+    }
+    info.reason = reason;
+    if (reason != SBO_STREAM_UPDATED) {
+        rq.keep = true;
+        if (sbo_status st = run_tick(ctx, rq)) return st;
+        info.path = 0;
+        k.last = info;
+        return SBO_OK;
+    }
+    const int64_t nb = sbo::acq_blocks(k.ms);
+    SBO_HIP(ctx->keys.reserve(sizeof(sbo_key) * (size_t)(nb + 1)));
+    if (R > 0) {
+        const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
+        Bracket br(ctx, ctx->ev_predict);
+        SBO_HIP(sbo::launch_predict_update(ctx->stream, ctx->Linv.as<double>(), ctx->cap, k.n_map, n,
+                                           ctx->zvec.as<double>(), ctx->x.as<float>(), ctx->y.as<float>(),
+                                           ctx->kbox.as<float4>(), k.qbox.as<float4>(), k.qx.as<float>(),
+                                           k.qy.as<float>(), k.perm.as<int32_t>(), k.ms, ctx->hyper.length_scale, sf2,
+                                           L, k.mu64.as<double>(), k.var64.as<double>(),
+                                           reinterpret_cast<unsigned long long *>(dh + 1)));
+        info.tiles_total = (k.ms + sbo::kBN - 1) / sbo::kBN * ((n + sbo::kBK - 1) / sbo::kBK);
+    }
+    sbo_key *bkeys = ctx->keys.as<sbo_key>();
+    SBO_HIP(sbo::launch_acquire_kept(ctx->stream, k.mu64.as<double>(), k.var64.as<double>(), k.ms, rq.beta, rq.f_min,
+                                     rq.score, rq.index_offset, k.perm.as<int32_t>(), rq.mu, rq.sd, rq.lo, rq.hi,
+                                     rq.safe, bkeys));
+    SBO_HIP(sbo::launch_reduce_keys(ctx->stream, bkeys, nb, rq.key ? rq.key : bkeys + nb));
+    k.n_map = n;
+    k.err_var += spend_var;
+    k.err_mean += spend_mean;
+    ++k.updates;
+    info.path = 1;
+    info.cutoff_log2 = L;
+    k.last = info;
+    return SBO_OK;
 }
 
 // Host queries staged for a tick: hq sized for them and `rest` more bytes,
@@ -2517,6 +2685,7 @@ namespace {
 // variance without jitter.
 sbo_status fill_and_factor(sbo_ctx *ctx, double base_noise) {
     const int64_t n = ctx->n;
+    ++ctx->fit_epoch;   // a model from scratch (sbo_fit, the append's re-sort, each jitter retry)
     ctx->probe_n = 0;   // new data: the precision probe runs again (appends re-probe by growth)
     const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
     ctx->jitter = 0.0;
@@ -2793,9 +2962,11 @@ SBO_API sbo_status sbo_query_cost(sbo_ctx *ctx, const float *qx, const float *qy
     return SBO_OK;
 }
 
-SBO_API sbo_status sbo_tick(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, double beta, double f_min,
-                            sbo_score score, int64_t index_offset, float *mu, float *sd, double *lo, double *hi,
-                            uint8_t *safe, sbo_key *out, uint32_t flags) {
+// sbo_tick and sbo_tick_stream: one argument check, one staging of host
+// pointers; `stream` selects run_tick_stream over run_tick.
+static sbo_status tick_entry(bool stream, sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, double beta,
+                             double f_min, sbo_score score, int64_t index_offset, float *mu, float *sd, double *lo,
+                             double *hi, uint8_t *safe, sbo_key *out, uint32_t flags) {
     if (!ctx) return SBO_E_INVAL;
     SBO_CHECK(ctx->fitted, SBO_E_STATE, "sbo_tick: call sbo_fit first");
     SBO_CHECK(qx && qy, SBO_E_INVAL, "sbo_tick: null query coordinates");
@@ -2818,7 +2989,7 @@ SBO_API sbo_status sbo_tick(sbo_ctx *ctx, const float *qx, const float *qy, int6
         rq.hi = hi;
         rq.safe = safe;
         rq.key = out;
-        if (sbo_status st = run_tick(ctx, rq)) return st;
+        if (sbo_status st = stream ? run_tick_stream(ctx, rq) : run_tick(ctx, rq)) return st;
         return finish(ctx, flags);
     }
     // host pointers: stage through device scratch
@@ -2838,7 +3009,7 @@ SBO_API sbo_status sbo_tick(sbo_ctx *ctx, const float *qx, const float *qy, int6
     rq.hi = hi ? dhi : nullptr;
     rq.safe = safe ? dsafe : nullptr;
     rq.key = dkey;
-    if (sbo_status st = run_tick(ctx, rq)) return st;
+    if (sbo_status st = stream ? run_tick_stream(ctx, rq) : run_tick(ctx, rq)) return st;
     if (mu) SBO_HIP(hipMemcpyAsync(mu, dmu, sizeof(float) * m, hipMemcpyDeviceToHost, ctx->stream));
     if (sd) SBO_HIP(hipMemcpyAsync(sd, dsd, sizeof(float) * m, hipMemcpyDeviceToHost, ctx->stream));
     if (lo) SBO_HIP(hipMemcpyAsync(lo, dlo, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->stream));
@@ -2847,6 +3018,68 @@ SBO_API sbo_status sbo_tick(sbo_ctx *ctx, const float *qx, const float *qy, int6
     if (out) SBO_HIP(hipMemcpyAsync(ctx->host_key, dkey, sizeof(sbo_key), hipMemcpyDeviceToHost, ctx->stream));
     SBO_HIP(hipStreamSynchronize(ctx->stream));
     if (out) *out = *ctx->host_key;
+    return SBO_OK;
+}
+
+SBO_API sbo_status sbo_tick(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, double beta, double f_min,
+                            sbo_score score, int64_t index_offset, float *mu, float *sd, double *lo, double *hi,
+                            uint8_t *safe, sbo_key *out, uint32_t flags) {
+    return tick_entry(false, ctx, qx, qy, m, beta, f_min, score, index_offset, mu, sd, lo, hi, safe, out, flags);
+}
+
+SBO_API sbo_status sbo_tick_stream(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, double beta,
+                                   double f_min, sbo_score score, int64_t index_offset, float *mu, float *sd,
+                                   double *lo, double *hi, uint8_t *safe, sbo_key *out, uint32_t flags) {
+    return tick_entry(true, ctx, qx, qy, m, beta, f_min, score, index_offset, mu, sd, lo, hi, safe, out, flags);
+}
+
+SBO_API sbo_status sbo_get_stream(const sbo_ctx *ctx, sbo_stream_info *out) {
+    if (!ctx || !out || out->struct_size < sizeof(uint32_t)) return SBO_E_INVAL;
+    const sbo::StreamKeep &k = ctx->keep;
+    sbo_stream_info info = k.last;
+    info.struct_size = (uint32_t)std::min<size_t>(out->struct_size, sizeof(info));
+    info.updates_since_full = k.updates;
+    info.err_var = k.err_var;
+    info.err_mean = k.err_mean;
+    if (info.path == 1 && info.tiles_total > 0) {
+        // the update's own count of the tiles it multiplied (waits for the stream)
+        unsigned long long kept = 0;
+        if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
+            hipMemcpy(&kept, k.head.as<sbo::StreamHead>() + 1, sizeof(kept), hipMemcpyDeviceToHost) != hipSuccess)
+            return SBO_E_DEVICE;
+        info.tiles_kept = (int64_t)kept;
+    }
+    memcpy(out, &info, info.struct_size);
+    return SBO_OK;
+}
+
+SBO_API sbo_status sbo_stream_reset(sbo_ctx *ctx) {
+    if (!ctx) return SBO_E_INVAL;
+    SBO_HIP(hipSetDevice(ctx->device));
+    SBO_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->keep.release();
+    ctx->keep.was_reset = true;
+    ctx->keep.last = sbo_stream_info{};
+    ctx->keep.err_var = ctx->keep.err_mean = 0.0;
+    ctx->keep.updates = 0;
+    return SBO_OK;
+}
+
+SBO_API sbo_status sbo_debug_stream_state(sbo_ctx *ctx, double *mu64, double *var64, int64_t cap) {
+    if (!ctx) return SBO_E_INVAL;
+    SBO_CHECK(mu64 && var64, SBO_E_INVAL, "sbo_debug_stream_state: null output");
+    const sbo::StreamKeep &k = ctx->keep;
+    SBO_CHECK(k.valid, SBO_E_STATE, "sbo_debug_stream_state: no kept posterior (call sbo_tick_stream first)");
+    SBO_CHECK(cap >= k.m, SBO_E_INVAL, "sbo_debug_stream_state: cap below the kept posterior's m");
+    SBO_HIP(hipSetDevice(ctx->device));
+    const size_t bytes = sizeof(double) * (size_t)k.m;
+    SBO_HIP(ctx->hout.reserve(2 * bytes));
+    double *dmu = ctx->hout.as<double>(), *dvar = dmu + k.m;
+    SBO_HIP(sbo::launch_stream_scatter(ctx->stream, k.mu64.as<double>(), k.var64.as<double>(), k.perm.as<int32_t>(),
+                                       k.ms, dmu, dvar));
+    SBO_HIP(hipMemcpyAsync(mu64, dmu, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    SBO_HIP(hipMemcpyAsync(var64, dvar, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    SBO_HIP(hipStreamSynchronize(ctx->stream));
     return SBO_OK;
 }
 
@@ -3368,6 +3601,14 @@ SBO_API sbo_status sbo_set_option(sbo_ctx *ctx, int option, int64_t value) {
             }
             ctx->precision_opt = (int)value;
             return SBO_OK;
+        case SBO_OPT_STREAM_SHARE:
+            SBO_CHECK(value >= 0 && value <= 20, SBO_E_INVAL, "SBO_OPT_STREAM_SHARE must be in [0, 20]");
+            ctx->stream_share = (int)value;
+            return SBO_OK;
+        case SBO_OPT_STREAM_MAX_ROWS:
+            SBO_CHECK(value >= 0 && value <= 65536, SBO_E_INVAL, "SBO_OPT_STREAM_MAX_ROWS must be in [0, 65536]");
+            ctx->stream_max_rows = value;
+            return SBO_OK;
         case SBO_OPT_TILE_SKIP:
             SBO_CHECK(value == -1 || value == 0 || (value >= 16 && value <= 1000), SBO_E_INVAL,
                       "SBO_OPT_TILE_SKIP must be -1 (auto), 0 (dense) or a cutoff exponent in [16, 1000]");
@@ -3787,6 +4028,7 @@ SBO_API sbo_status sbo_import_state(sbo_ctx *ctx, const void *dev_buf, int64_t b
         }
     }
     FitCommit fc(ctx);
+    ++ctx->fit_epoch;
     ctx->has_factor = false;
     ctx->precise = false;   // no f64 inverse travels: an imported state ticks with the fast sweep
     ctx->probe_n = 0;

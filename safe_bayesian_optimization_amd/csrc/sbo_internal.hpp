@@ -86,6 +86,36 @@ private:
     size_t cap_ = 0;
 };
 
+// ------------------------------------------------------- streaming tick
+// What one sbo_tick_stream reads back before it decides its path, in one copy.
+struct StreamHead {
+    int mismatch;        // a caller's query differs from the kept one of its sweep position
+    int pad;
+    double sum_l1sq;     // sum over the new rows r of |L^-1_r|_1^2
+    double sum_l1z;      // sum over the new rows r of |L^-1_r|_1 |z_r|
+};
+// The kept posterior of sbo_tick_stream: state, not workspace (sbo_trim leaves
+// it; sbo_stream_reset frees it).  Everything per sweep position is in the
+// order tick_order_queries produced for the full sweep that captured it.
+struct StreamKeep {
+    DevBuf mu64, var64;          // f64 mean and variance (sf2 - sum of partials, unclamped), ms each
+    DevBuf qx, qy, perm;         // the ordered queries (f32) and their caller index (int32; -1: padding)
+    DevBuf qbox;                 // per 128-position block: bounding box (float4 x0, x1, y0, y1)
+    DevBuf l1;                   // the new rows' 1-norms of one update
+    DevBuf head;                 // StreamHead, then the kept-tile counter of the last update
+    bool valid = false, was_reset = false;
+    int64_t m = 0, ms = 0, n_map = 0;   // caller's queries, sweep positions, training rows the state has seen
+    uint64_t epoch = 0;          // ctx->fit_epoch at capture
+    bool precise = false;        // the sweep that captured it
+    double err_var = 0.0, err_mean = 0.0;   // cutoff bounds spent since the last full sweep
+    int64_t updates = 0;
+    sbo_stream_info last{};      // what the last call did (sbo_get_stream)
+    void release() {
+        for (DevBuf *b : {&mu64, &var64, &qx, &qy, &perm, &qbox, &l1, &head}) b->release();
+        valid = false;
+    }
+};
+
 }  // namespace sbo
 
 struct sbo_ctx {
@@ -235,6 +265,12 @@ struct sbo_ctx {
     sbo::DevBuf hout;            // host-output staging
     sbo::DevBuf keys;            // per-block argmax keys + final key
     sbo_key *host_key = nullptr; // pinned readback
+
+    // streaming tick (sbo_tick_stream, predict_update.hip)
+    uint64_t fit_epoch = 0;      // counts every event that rebuilds the model from scratch (a block append keeps it)
+    int stream_share = 10;       // SBO_OPT_STREAM_SHARE: an update's cutoff may spend 2^-s of the sweep's skip budget
+    int64_t stream_max_rows = 64;   // SBO_OPT_STREAM_MAX_ROWS: more appended rows than this take the full sweep
+    sbo::StreamKeep keep;
 
     // kernel timing (sbo_profile)
     bool prof = false;
@@ -443,17 +479,52 @@ hipError_t launch_tile_boxes(hipStream_t s, const float *x, const float *y, int6
 // key indices are written in the caller's order.  nonempty (may be null): the
 // non-empty items of the plan the partials were swept under (plan_item_views):
 // the partial of an empty item is not read (SkipPlan::zero_empty).
+// keep_mu / keep_var (may be null): the streaming tick's capture, per sweep
+// position the mean widened to f64 and sf2 - the summed partials before the
+// clamp at zero; the other outputs do not depend on them.
 hipError_t launch_acquire(hipStream_t s, const float *part, const float *mean, int nI, int64_t ldp,
                           int64_t m, float sf2, double beta, double f_min, int score_kind,
                           int64_t index_offset, const int32_t *perm, float *mu, float *sd, double *lo,
                           double *hi, uint8_t *safe, sbo_key *block_keys,
-                          const unsigned long long *nonempty = nullptr);
+                          const unsigned long long *nonempty = nullptr, double *keep_mu = nullptr,
+                          double *keep_var = nullptr);
 // the same over the precise sweep's f64 partials and mean (sf2 in f64)
 hipError_t launch_acquire(hipStream_t s, const double *part, const double *mean, int nI, int64_t ldp,
                           int64_t m, double sf2, double beta, double f_min, int score_kind,
                           int64_t index_offset, const int32_t *perm, float *mu, float *sd, double *lo,
                           double *hi, uint8_t *safe, sbo_key *block_keys,
-                          const unsigned long long *nonempty = nullptr);
+                          const unsigned long long *nonempty = nullptr, double *keep_mu = nullptr,
+                          double *keep_var = nullptr);
+// Acquisition from a kept posterior (sbo_tick_stream's update path): per sweep
+// position mu = (float)mu64, sd = sqrt((float)max(var64, 0)), then the sets
+// and the block argmax exactly as launch_acquire's; perm as there (never null).
+hipError_t launch_acquire_kept(hipStream_t s, const double *mu64, const double *var64, int64_t ms, double beta,
+                               double f_min, int score_kind, int64_t index_offset, const int32_t *perm, float *mu,
+                               float *sd, double *lo, double *hi, uint8_t *safe, sbo_key *block_keys);
+// Streaming tick (predict_update.hip).  launch_stream_keep: the sweep order of
+// a full tick copied into the kept buffers (perm null: identity) and each
+// 128-position block's bounding box.  launch_stream_compare: head->mismatch
+// |= 1 when a caller's query is not bitwise the kept one (head zeroed by the
+// caller).  launch_update_bound_sums: the 1-norms of rows n_map .. n - 1 of
+// the f64 inverse (l1: scratch of update_l1_bytes) and the two sums of StreamHead.
+// launch_predict_update: the rank-(n - n_map) update of mu64 / var64 in place;
+// skip_L 0: dense, else tiles whose K* entries are all below 2^-skip_L are
+// skipped; *tiles_kept += the (query block, k-tile) pairs multiplied.
+// launch_stream_scatter: the kept state in the caller's order.
+hipError_t launch_stream_keep(hipStream_t s, const float *qx, const float *qy, const int32_t *perm, int64_t ms,
+                              float *kqx, float *kqy, int32_t *kperm, float4 *qbox);
+hipError_t launch_stream_compare(hipStream_t s, const float *qx, const float *qy, const float *kqx, const float *kqy,
+                                 const int32_t *kperm, int64_t ms, StreamHead *head);
+size_t update_l1_bytes(int64_t R);   // launch_update_bound_sums' l1 scratch for R new rows
+hipError_t launch_update_bound_sums(hipStream_t s, const double *Linv, int64_t ld, int64_t n_map, int64_t n,
+                                    const double *z, double *l1, StreamHead *head);
+hipError_t launch_predict_update(hipStream_t s, const double *Linv, int64_t ld, int64_t n_map, int64_t n,
+                                 const double *z, const float *x, const float *y, const float4 *kbox,
+                                 const float4 *qbox, const float *kqx, const float *kqy, const int32_t *kperm,
+                                 int64_t ms, double ell, double sf2, int skip_L, double *mu64, double *var64,
+                                 unsigned long long *tiles_kept);
+hipError_t launch_stream_scatter(hipStream_t s, const double *mu64, const double *var64, const int32_t *kperm,
+                                 int64_t ms, double *mu_out, double *var_out);
 // Precise sweep (predict_f64.hip, SBO_OPT_PRECISION): A = sf2 L^-1 packed in
 // f64 from the fit's f64 inverse for row blocks >= I0 (tile (I, t) at
 // tile_start(I) + t, two 64 KiB stages in MFMA fragment order), and per k-tile

@@ -221,6 +221,19 @@ class TerrainMapper:
         ``outputs`` may hold preallocated mu/sd/lo/hi/safe arrays (None entries
         are skipped).  Host mode returns an ``sbo_key``; device mode writes the
         16-byte key into ``key_out`` (a device tensor) and returns it."""
+        return self._tick(self._lib.sbo_tick, qx, qy, beta, f_min, score, index_offset, outputs, key_out, async_)
+
+    def tick_stream(self, qx, qy, beta: float, f_min: float, *, score: int = N.SCORE_WIDTH, index_offset: int = 0,
+                    outputs: dict | None = None, key_out=None, async_: bool = False):
+        """``tick`` with a kept posterior (sbo_tick_stream): the first call
+        sweeps and keeps the f64 posterior; a call with the same queries after
+        block appends adds only the appended rows' share and runs the
+        acquisition from it.  Whatever else changed takes the full sweep
+        again; ``stream_info()`` says which path ran and why."""
+        return self._tick(self._lib.sbo_tick_stream, qx, qy, beta, f_min, score, index_offset, outputs, key_out,
+                          async_)
+
+    def _tick(self, fn, qx, qy, beta, f_min, score, index_offset, outputs, key_out, async_):
         (qx, qy), fl = _prep([qx, qy], np.float32, "float32")
         if async_:
             fl |= N.SBO_ASYNC
@@ -231,16 +244,37 @@ class TerrainMapper:
                 import torch
                 key_out = torch.empty(2, dtype=torch.int64, device=qx.device)
             kp = ctypes.cast(ctypes.c_void_p(key_out.data_ptr()), ctypes.POINTER(N.sbo_key))
-            self.ctx.check(self._lib.sbo_tick(self.ctx.handle, _ptr(qx), _ptr(qy), m, float(beta), float(f_min),
-                                              int(score), int(index_offset), _ptr(o.get("mu")), _ptr(o.get("sd")),
-                                              _ptr(o.get("lo")), _ptr(o.get("hi")), _ptr(o.get("safe")), kp, fl))
+            self.ctx.check(fn(self.ctx.handle, _ptr(qx), _ptr(qy), m, float(beta), float(f_min),
+                              int(score), int(index_offset), _ptr(o.get("mu")), _ptr(o.get("sd")),
+                              _ptr(o.get("lo")), _ptr(o.get("hi")), _ptr(o.get("safe")), kp, fl))
             return key_out
         key = N.sbo_key()
-        self.ctx.check(self._lib.sbo_tick(self.ctx.handle, _ptr(qx), _ptr(qy), m, float(beta), float(f_min),
-                                          int(score), int(index_offset), _ptr(o.get("mu")), _ptr(o.get("sd")),
-                                          _ptr(o.get("lo")), _ptr(o.get("hi")), _ptr(o.get("safe")),
-                                          ctypes.byref(key), fl))
+        self.ctx.check(fn(self.ctx.handle, _ptr(qx), _ptr(qy), m, float(beta), float(f_min),
+                          int(score), int(index_offset), _ptr(o.get("mu")), _ptr(o.get("sd")),
+                          _ptr(o.get("lo")), _ptr(o.get("hi")), _ptr(o.get("safe")),
+                          ctypes.byref(key), fl))
         return key
+
+    def stream_info(self) -> dict:
+        """What the last ``tick_stream`` did (sbo_get_stream): ``path`` (0 full
+        sweep, 1 update), ``reason`` as its name, the appended rows, the tiles
+        the update kept, and the cutoff bounds spent against their budget."""
+        r = N.sbo_stream_info()
+        r.struct_size = ctypes.sizeof(r)
+        self.ctx.check(self._lib.sbo_get_stream(self.ctx.handle, ctypes.byref(r)))
+        d = {f: getattr(r, f) for f, _ in N.sbo_stream_info._fields_ if f != "struct_size"}
+        d["reason"] = N.STREAM_REASONS[d["reason"]]
+        return d
+
+    def stream_reset(self) -> None:
+        """Drop the kept posterior and free its memory (sbo_stream_reset)."""
+        self.ctx.check(self._lib.sbo_stream_reset(self.ctx.handle))
+
+    def stream_state(self, m: int):
+        """Test access: the kept f64 (mu, var), var not clamped, in the caller's order."""
+        mu, var = np.empty(m, np.float64), np.empty(m, np.float64)
+        self.ctx.check(self._lib.sbo_debug_stream_state(self.ctx.handle, _ptr(mu), _ptr(var), int(m)))
+        return mu, var
 
     def query_cost(self, qx, qy):
         """Sweep work of each query under the current fit (sbo_query_cost):

@@ -110,6 +110,14 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "tick failed: %s\n", ctx.last_error().c_str());
         return 1;
     }
+    // the same through the mapper's kept-posterior tick: its first call is the full tick
+    sbo_key skey{0.0, -1};
+    const sbo::TerrainMap smap = mapper.tick_stream(gx, gy, gw, gh, 2.0, f_min, &skey);
+    if (!smap.success || skey.idx != key.idx || skey.score != key.score || smap.values != map.values ||
+        mapper.stream_info().reason != SBO_STREAM_FIRST) {
+        std::fprintf(stderr, "tick_stream differs from the tick: %s\n", smap.message.c_str());
+        return 1;
+    }
     int64_t best = -1;
     double bw = 0.0;
     for (size_t i = 0; i < node.S().size(); ++i)
