@@ -221,6 +221,69 @@ SBO_API sbo_status sbo_stream_reset(sbo_ctx *ctx);
  * without a kept posterior. */
 SBO_API sbo_status sbo_debug_stream_state(sbo_ctx *ctx, double *mu64, double *var64, int64_t cap);
 
+/* Model evidence of the current fit: the log marginal likelihood of the
+ * training data under the fitted hyper-parameters, its gradient, and the
+ * leave-one-out predictive -- whether length_scale / sigma_f / noise_level
+ * suit the data (no reference counterpart: the node copies them from
+ * config/lpsc.yaml:35-37).  Read off what sbo_fit / sbo_append leave on the
+ * device: the f32 factor L, the f64 inverse X = L^-1, z = X (y - m0) and
+ * alpha = X^T z.  With r = y - m0, s = noise_level + jitter (the jitter held
+ * constant in the derivatives), c_i = (K^-1)_ii = sum_{k >= i} X_ki^2:
+ *   lml      = -1/2 z'z - sum_i log L_ii - n/2 log 2 pi
+ *   grad[0]  = 1/2 sum_ij (alpha_i alpha_j - (X'X)_ij) G_ij,
+ *              G_ij = sf2 exp(-d_ij^2 / 2 l^2) d_ij^2 / l^2
+ *   grad[1]  = (alpha'r - s alpha'alpha) - (n - s sum_i c_i)
+ *   grad[2]  = 1/2 noise_level (alpha'alpha - sum_i c_i)
+ *   grad[3]  = sum_i alpha_i
+ *   loo_mean_i = y_i - alpha_i / c_i,  loo_var_i = 1 / c_i,
+ *   loo_log_pred = sum_i -1/2 log(2 pi / c_i) - 1/2 alpha_i^2 / c_i.
+ * grad[0]'s trace is a contraction of K^-1 = X'X with a matrix that decays as
+ * exp(-d^2 / 2 l^2): per pair of 64-point k-tiles (I <= J) a tall-skinny f64
+ * Gram product on the f64 matrix cores.  With SBO_OPT_EVIDENCE_BUDGET B > 0 a
+ * pair whose bounding boxes are at least sqrt(2) l apart may be dropped: by
+ * |K^-1_ij| <= sqrt(c_i c_j) that moves grad[0] by at most
+ * g(d_min) (sum_I |alpha| sum_J |alpha| + sum_I sqrt(c) sum_J sqrt(c)) for both
+ * orders of the pair; pairs are dropped smallest bound first while the bounds
+ * sum to at most 2^-B n (grad_budget); the sum spent is grad_err_bound.  Every
+ * other field, and the LOO arrays, do not depend on the cutoff.  All sums run
+ * in a fixed order (no floating-point atomics): two calls on the same state
+ * agree bitwise.
+ *
+ * loo_mean / loo_var: n doubles each in the caller's training order
+ * (sbo_get_order), or NULL; host pointers, device pointers with
+ * SBO_DEVICE_PTRS.  The caller sets out->struct_size to
+ * sizeof(sbo_evidence_info); the library writes no more than that many bytes.
+ * Synchronous (the per-tile norms are read back; SBO_ASYNC is ignored).
+ * Needs a fit with a factor and a current f64 inverse and z: SBO_E_STATE
+ * before a fit, after a failed one, on an imported state and with
+ * SBO_OPT_INVERSE_BITS 32.  Alters no fitted state; its workspace is freed by
+ * sbo_trim. */
+typedef struct sbo_evidence_info {
+    uint32_t struct_size;          /* caller sets; the library writes no more than this many bytes */
+    int32_t  dropped;              /* 1 if the cutoff dropped at least one tile pair */
+    int64_t  n;
+    double   lml;                  /* log p(y | X, theta) = data_fit - log_det - n/2 log 2pi */
+    double   data_fit;             /* -1/2 z'z */
+    double   log_det;              /* sum_i log L_ii  (the f32 factor's diagonal, widened) */
+    double   grad[4];              /* d lml / d (log length_scale, log sigma_f, log noise_level, prior_mean) */
+    double   grad_err_bound;       /* rigorous bound on |error of grad[0]| from dropped pairs (0 when dense) */
+    double   grad_budget;          /* what the bound was allowed to be */
+    int64_t  pairs_total, pairs_kept;   /* k-tile pairs I <= J */
+    double   loo_log_pred;         /* sum_i log p(y_i | y_-i) */
+    double   ms;                   /* device time of the call's kernels */
+} sbo_evidence_info;
+SBO_API sbo_status sbo_evidence(sbo_ctx *ctx, sbo_evidence_info *out,
+                                double *loo_mean, double *loo_var, uint32_t flags);
+
+/* Test accessor: sbo_evidence's pair cutoff alone, on the host (no context, no
+ * device).  boxes: per k-tile x0, x1, y0, y1; alpha_l1 / sqrtc_l1: per k-tile
+ * sum |alpha_i| / sum sqrt(c_i); budget: what the summed bound may be (<= 0:
+ * nothing is dropped).  drop[I * T + J] = 1 for a dropped pair (symmetric, the
+ * diagonal never); *bound = the dropped pairs' summed bound, both orders. */
+SBO_API sbo_status sbo_debug_evidence_pairs(const float *boxes /* 4 T: x0,x1,y0,y1 */,
+        const double *alpha_l1, const double *sqrtc_l1, int64_t T, sbo_hyper hyper,
+        double budget, uint8_t *drop /* T*T, row-major, symmetric */, double *bound);
+
 /* Sweep work of each query under the current fit: builds the tick's tile
  * plan for these queries (no sweep) and writes cost[i] = the k-tiles its
  * 128-query block multiplies, summed over row blocks and weighted by their
@@ -597,6 +660,10 @@ SBO_API sbo_status sbo_kd_order(const float *x, const float *y, int64_t n, int64
  * with more rows appended since its last tick than this takes the full sweep
  * (0: every call after an append does). */
 #define SBO_OPT_STREAM_MAX_ROWS 31
+/* SBO_OPT_EVIDENCE_BUDGET (B in [10, 60], default 20; 0: dense): sbo_evidence's
+ * k-tile pair cutoff may move grad[0] by at most 2^-B n (grad_err_bound says
+ * what it spent). */
+#define SBO_OPT_EVIDENCE_BUDGET 32
 SBO_API sbo_status sbo_set_option(sbo_ctx *ctx, int option, int64_t value);
 
 /* The last inverse check (SBO_OPT_INV_CHECK) of the current fit, on m = 31
@@ -631,11 +698,11 @@ SBO_API sbo_status sbo_get_inverse_check(const sbo_ctx *ctx, sbo_inv_check *out)
 /* Release the fit-time and tick-time workspaces the context keeps between
  * calls for speed (the recursive inverse's scratch and the int8-sliced GEMM's
  * packed operands -- about 2.1 GB at N = 16384, 8.5 GB at 32768 -- the inverse
- * check's, the append re-sort's staging copy and the precise sweep's K* table,
- * up to SBO_OPT_TABLE_MB); they are allocated again on the next call that
- * needs them.  The fitted state (factor, inverse, operands) stays, and so does
- * sbo_tick_stream's kept posterior (sbo_stream_reset frees that).  Waits for
- * the context's streams. */
+ * check's, the append re-sort's staging copy, sbo_evidence's column norms and
+ * work items and the precise sweep's K* table, up to SBO_OPT_TABLE_MB); they
+ * are allocated again on the next call that needs them.  The fitted state
+ * (factor, inverse, operands) stays, and so does sbo_tick_stream's kept
+ * posterior (sbo_stream_reset frees that).  Waits for the context's streams. */
 SBO_API sbo_status sbo_trim(sbo_ctx *ctx);
 
 /* Startup warm-up for the node's first map (no reference counterpart: the

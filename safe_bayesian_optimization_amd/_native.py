@@ -36,6 +36,7 @@ EXPORTS = (
     "sbo_kd_order", "sbo_get_probe", "sbo_keys_reduce", "sbo_get_inverse_check", "sbo_trim", "sbo_warmup",
     "sbo_debug_gz_gemm", "sbo_debug_gz_gemm_packed", "sbo_debug_x3_operand", "sbo_debug_plan",
     "sbo_tick_stream", "sbo_get_stream", "sbo_stream_reset", "sbo_debug_stream_state",
+    "sbo_evidence", "sbo_debug_evidence_pairs",
 )
 # sbo_stream_reason (include/sbo.h, sbo_get_stream)
 STREAM_REASONS = ("FIRST", "UPDATED", "QUERIES_CHANGED", "REFIT", "NO_INVERSE", "ROWS_OVER_CAP", "BUDGET", "RESET")
@@ -79,6 +80,7 @@ SBO_OPT_INV_OZ_MIN = 28
 SBO_OPT_INV_OZ_ADAPT = 29
 SBO_OPT_STREAM_SHARE = 30
 SBO_OPT_STREAM_MAX_ROWS = 31
+SBO_OPT_EVIDENCE_BUDGET = 32
 
 
 class SboError(RuntimeError):
@@ -121,6 +123,14 @@ class sbo_stream_info(ctypes.Structure):
                 ("m", ctypes.c_int64), ("updates_since_full", ctypes.c_int64), ("tiles_total", ctypes.c_int64),
                 ("tiles_kept", ctypes.c_int64), ("err_var", ctypes.c_double), ("err_mean", ctypes.c_double),
                 ("budget_var", ctypes.c_double), ("budget_mean", ctypes.c_double)]
+
+
+class sbo_evidence_info(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("dropped", ctypes.c_int32), ("n", ctypes.c_int64),
+                ("lml", ctypes.c_double), ("data_fit", ctypes.c_double), ("log_det", ctypes.c_double),
+                ("grad", ctypes.c_double * 4), ("grad_err_bound", ctypes.c_double), ("grad_budget", ctypes.c_double),
+                ("pairs_total", ctypes.c_int64), ("pairs_kept", ctypes.c_int64), ("loo_log_pred", ctypes.c_double),
+                ("ms", ctypes.c_double)]
 
 
 _lib = None
@@ -180,6 +190,10 @@ def lib():
     L.sbo_stream_reset.restype = st
     L.sbo_debug_stream_state.argtypes = [vp, vp, vp, i64]
     L.sbo_debug_stream_state.restype = st
+    L.sbo_evidence.argtypes = [vp, ctypes.POINTER(sbo_evidence_info), vp, vp, u32]
+    L.sbo_evidence.restype = st
+    L.sbo_debug_evidence_pairs.argtypes = [vp, vp, vp, i64, sbo_hyper, dbl, vp, ctypes.POINTER(dbl)]
+    L.sbo_debug_evidence_pairs.restype = st
     L.sbo_query_cost.argtypes = [vp, vp, vp, i64, vp, u32]
     L.sbo_query_cost.restype = st
     L.sbo_key_combine.argtypes = [sbo_key, sbo_key]

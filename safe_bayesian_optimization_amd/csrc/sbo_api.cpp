@@ -3083,6 +3083,156 @@ SBO_API sbo_status sbo_debug_stream_state(sbo_ctx *ctx, double *mu64, double *va
     return SBO_OK;
 }
 
+// Model evidence (csrc/evidence.hip): two device phases with one readback
+// between them -- the column norms, per-tile sums and LOO outputs; then, after
+// the host has chosen the kept k-tile pairs from the tiles' norms and boxes,
+// the Gram contraction of grad[0] over (pair, row chunk) items.  Reads the
+// fitted state only; evws / evitems are its own workspaces.
+static sbo_status evidence_run(sbo_ctx *ctx, sbo_evidence_info *out, double *loo_mean, double *loo_var,
+                               uint32_t flags);
+
+SBO_API sbo_status sbo_evidence(sbo_ctx *ctx, sbo_evidence_info *out, double *loo_mean, double *loo_var,
+                                uint32_t flags) {
+    if (!ctx || !out) return SBO_E_INVAL;
+    try {
+        return evidence_run(ctx, out, loo_mean, loo_var, flags);
+    } catch (const std::bad_alloc &) {   // (the host-side tile and item lists)
+        ctx->err = "sbo_evidence: host allocation failed";
+        return SBO_E_OOM;
+    }
+}
+
+static sbo_status evidence_run(sbo_ctx *ctx, sbo_evidence_info *out, double *loo_mean, double *loo_var,
+                               uint32_t flags) {
+    SBO_CHECK(out->struct_size >= sizeof(uint32_t), SBO_E_INVAL, "sbo_evidence: struct_size not set");
+    const int64_t n = ctx->n;
+    SBO_CHECK(ctx->fitted && n > 0, SBO_E_STATE, "sbo_evidence: call sbo_fit first");
+    SBO_CHECK(ctx->has_factor && ctx->inverse_bits == 64 && ctx->linv_n == n && ctx->z_n == n, SBO_E_STATE,
+              "sbo_evidence: needs the fit's factor, f64 inverse and z (not an imported state, SBO_OPT_INVERSE_BITS 64)");
+    SBO_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const int64_t T = (n + sbo::kBK - 1) / sbo::kBK;
+    const bool want_loo = loo_mean || loo_var, host_loo = want_loo && !dev(flags);
+    SBO_HIP(ctx->evws.reserve(Carve::need(n, 8) + Carve::need(T * sbo::kEvSums, 8) + Carve::need(1, 8) +
+                              (want_loo ? Carve::need(n, 8) : 0) + (host_loo ? 2 * Carve::need(n, 8) : 0)));
+    Carve cv(ctx->evws.as<void>());
+    double *dc = cv.take<double>(n), *dsums = cv.take<double>(T * sbo::kEvSums), *dres = cv.take<double>(1);
+    const double *X = ctx->Linv.as<double>(), *dalpha = ctx->alpha64.as<double>();
+    hipEvent_t ev[4] = {take_event(ctx), take_event(ctx), take_event(ctx), take_event(ctx)};
+    struct Give {   // the events go back to the pool on every path
+        sbo_ctx *c;
+        hipEvent_t *e;
+        ~Give() {
+            for (int i = 0; i < 4; ++i)
+                if (e[i]) c->ev_pool.push_back(e[i]);
+        }
+    } give{ctx, ev};
+    SBO_CHECK(ev[0] && ev[1] && ev[2] && ev[3], SBO_E_DEVICE, "sbo_evidence: hipEventCreate failed");
+
+    // phase 1: c_i, the per-tile sums, the LOO outputs
+    SBO_HIP(hipEventRecord(ev[0], s));
+    SBO_HIP(sbo::launch_evidence_norms(s, X, ctx->cap, n, dalpha, ctx->zvec.as<double>(), ctx->obs.as<float>(),
+                                       ctx->L.as<float>(), ctx->cap, ctx->hyper.prior_mean, dc, dsums));
+    if (want_loo) {
+        int64_t *dorder = cv.take<int64_t>(n);
+        double *dm = loo_mean, *dv = loo_var;
+        if (host_loo) {
+            dm = cv.take<double>(n);
+            dv = cv.take<double>(n);
+        }
+        SBO_HIP(hipMemcpyAsync(dorder, ctx->order.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, s));
+        SBO_HIP(sbo::launch_evidence_loo(s, dc, dalpha, ctx->obs.as<float>(), dorder, n, loo_mean ? dm : nullptr,
+                                         loo_var ? dv : nullptr));
+        if (host_loo && loo_mean) SBO_HIP(hipMemcpyAsync(loo_mean, dm, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+        if (host_loo && loo_var) SBO_HIP(hipMemcpyAsync(loo_var, dv, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    }
+    SBO_HIP(hipEventRecord(ev[1], s));
+    std::vector<double> sums((size_t)T * sbo::kEvSums), al1(T), sl1(T);
+    std::vector<float> boxes((size_t)4 * T);
+    SBO_HIP(hipMemcpyAsync(sums.data(), dsums, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, s));
+    SBO_HIP(hipMemcpyAsync(boxes.data(), ctx->kbox.as<void>(), sizeof(float) * boxes.size(), hipMemcpyDeviceToHost, s));
+    SBO_HIP(hipStreamSynchronize(s));
+
+    // the totals in tile order
+    double tot[sbo::kEvSums] = {};
+    for (int64_t t = 0; t < T; ++t) {
+        for (int j = 0; j < sbo::kEvSums; ++j) tot[j] += sums[t * sbo::kEvSums + j];
+        al1[t] = sums[t * sbo::kEvSums];
+        sl1[t] = sums[t * sbo::kEvSums + 1];
+    }
+    const double sum_c = tot[2], aa = tot[3], ar = tot[4];
+    const double sn = ctx->hyper.noise_level, noise = sn - ctx->jitter;   // (hyper.noise_level holds the jitter too)
+    const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
+    sbo_evidence_info r{};
+    r.n = n;
+    r.data_fit = -0.5 * tot[7];
+    r.log_det = tot[6];
+    r.lml = r.data_fit - r.log_det - 0.5 * (double)n * sbo::kEvLog2Pi;
+    r.grad[1] = (ar - sn * aa) - ((double)n - sn * sum_c);
+    r.grad[2] = 0.5 * noise * (aa - sum_c);
+    r.grad[3] = tot[5];
+    r.loo_log_pred = tot[8];
+
+    // the cutoff, then the items: kept pair I <= J x chunk of kEvChunk rows from 64 J
+    r.grad_budget = ctx->evidence_budget > 0 ? std::ldexp((double)n, -ctx->evidence_budget) : 0.0;
+    // host cost per call, T = n / 64: the T x T drop map (64 KiB at n = 16384, 1 MiB at 65536), inside
+    // evidence_pairs up to T^2 / 2 candidates of 16 B (0.5 / 8 MiB) and their sort, and 16 B per item below
+    // (about n^2 / 1400 items: 3 MiB at 16384, 47 MiB at 65536)
+    std::vector<uint8_t> drop((size_t)T * T);
+    sbo::evidence_pairs(boxes.data(), al1.data(), sl1.data(), T, ctx->hyper.length_scale, sf2, r.grad_budget,
+                        drop.data(), &r.grad_err_bound);
+    std::vector<int4> items;
+    r.pairs_total = T * (T + 1) / 2;
+    for (int64_t J = 0; J < T; ++J)
+        for (int64_t I = 0; I <= J; ++I) r.pairs_kept += drop[I * T + J] ? 0 : 1;
+    // items grouped by the band of kEvChunk rows their chunk starts in (then J, then I): the
+    // workgroups in flight read one band of X -- kEvChunk x n doubles, which the last-level
+    // cache holds -- and share the J block
+    constexpr int64_t kBand = sbo::kEvChunk / sbo::kBK;   // k-tiles per chunk
+    for (int64_t g = 0; g * sbo::kEvChunk < n; ++g)
+        for (int64_t J = 0; J < T && J / kBand <= g; ++J) {
+            const int64_t k0 = J * sbo::kBK + (g - J / kBand) * sbo::kEvChunk;
+            if (k0 >= n) continue;
+            for (int64_t I = 0; I <= J; ++I)
+                if (!drop[I * T + J]) items.push_back(make_int4((int)I, (int)J, (int)k0, k0 == J * sbo::kBK ? 1 : 0));
+        }
+    r.dropped = r.pairs_kept < r.pairs_total ? 1 : 0;
+    const int64_t ni = (int64_t)items.size();
+    SBO_HIP(ctx->evitems.reserve(Carve::need(ni, sizeof(int4)) + Carve::need(ni, 8)));
+    Carve ci(ctx->evitems.as<void>());
+    int4 *ditems = ci.take<int4>(ni);
+    double *dslots = ci.take<double>(ni);
+    SBO_HIP(hipMemcpyAsync(ditems, items.data(), sizeof(int4) * (size_t)ni, hipMemcpyHostToDevice, s));
+    SBO_HIP(hipEventRecord(ev[2], s));
+    SBO_HIP(sbo::launch_evidence_gram(s, X, ctx->cap, n, ctx->x.as<float>(), ctx->y.as<float>(), dalpha, ditems, ni,
+                                      ctx->hyper.length_scale, sf2, dslots, dres));
+    SBO_HIP(hipEventRecord(ev[3], s));
+    double g0 = 0.0;
+    SBO_HIP(hipMemcpyAsync(&g0, dres, sizeof(double), hipMemcpyDeviceToHost, s));
+    SBO_HIP(hipStreamSynchronize(s));
+    r.grad[0] = g0;   // (the slots carry the 1/2: a diagonal pair halved, an off-diagonal one standing for both orders)
+    float ms1 = 0.0f, ms2 = 0.0f;
+    SBO_HIP(hipEventElapsedTime(&ms1, ev[0], ev[1]));
+    SBO_HIP(hipEventElapsedTime(&ms2, ev[2], ev[3]));
+    r.ms = (double)ms1 + (double)ms2;
+    r.struct_size = (uint32_t)std::min<size_t>(out->struct_size, sizeof(r));
+    memcpy(out, &r, r.struct_size);
+    return SBO_OK;
+}
+
+SBO_API sbo_status sbo_debug_evidence_pairs(const float *boxes, const double *alpha_l1, const double *sqrtc_l1,
+                                            int64_t T, sbo_hyper hyper, double budget, uint8_t *drop, double *bound) {
+    if (T < 0 || !bound || (T > 0 && (!boxes || !alpha_l1 || !sqrtc_l1 || !drop))) return SBO_E_INVAL;
+    if (!(hyper.length_scale > 0.0) || !(hyper.sigma_f > 0.0)) return SBO_E_INVAL;
+    try {
+        sbo::evidence_pairs(boxes, alpha_l1, sqrtc_l1, T, hyper.length_scale, hyper.sigma_f * hyper.sigma_f, budget,
+                            drop, bound);
+    } catch (...) {
+        return SBO_E_OOM;
+    }
+    return SBO_OK;
+}
+
 
 SBO_API sbo_status sbo_compute_sets(sbo_ctx *ctx, const float *mu, const float *sd, int64_t m, double beta,
                                     double f_min, double *lo, double *hi, uint8_t *safe, uint32_t flags) {
@@ -3609,6 +3759,11 @@ SBO_API sbo_status sbo_set_option(sbo_ctx *ctx, int option, int64_t value) {
             SBO_CHECK(value >= 0 && value <= 65536, SBO_E_INVAL, "SBO_OPT_STREAM_MAX_ROWS must be in [0, 65536]");
             ctx->stream_max_rows = value;
             return SBO_OK;
+        case SBO_OPT_EVIDENCE_BUDGET:
+            SBO_CHECK(value == 0 || (value >= 10 && value <= 60), SBO_E_INVAL,
+                      "SBO_OPT_EVIDENCE_BUDGET must be 0 (dense) or in [10, 60]");
+            ctx->evidence_budget = (int)value;
+            return SBO_OK;
         case SBO_OPT_TILE_SKIP:
             SBO_CHECK(value == -1 || value == 0 || (value >= 16 && value <= 1000), SBO_E_INVAL,
                       "SBO_OPT_TILE_SKIP must be -1 (auto), 0 (dense) or a cutoff exponent in [16, 1000]");
@@ -3638,7 +3793,7 @@ SBO_API sbo_status sbo_trim(sbo_ctx *ctx) {
     if (ctx->inv_stream) SBO_HIP(hipStreamSynchronize(ctx->inv_stream));
     if (ctx->chk_stream) SBO_HIP(hipStreamSynchronize(ctx->chk_stream));
     for (sbo::DevBuf *b : {&ctx->scratch, &ctx->gzws, &ctx->gzws_aux, &ctx->chk, &ctx->restage, &ctx->kzt, &ctx->qcost,
-                           &ctx->awork,
+                           &ctx->awork, &ctx->evws, &ctx->evitems,
                            &ctx->cholx3[0], &ctx->cholx3[1]})
         b->release();
     return SBO_OK;

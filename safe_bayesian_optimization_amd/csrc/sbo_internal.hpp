@@ -272,6 +272,10 @@ struct sbo_ctx {
     int64_t stream_max_rows = 64;   // SBO_OPT_STREAM_MAX_ROWS: more appended rows than this take the full sweep
     sbo::StreamKeep keep;
 
+    // model evidence (sbo_evidence, evidence.hip): workspaces only (sbo_trim frees them)
+    int evidence_budget = 20;    // SBO_OPT_EVIDENCE_BUDGET: the pair cutoff may move grad[0] by 2^-B n (0: dense)
+    sbo::DevBuf evws, evitems;   // column norms, tile sums, order, LOO staging; the work items and their slots
+
     // kernel timing (sbo_profile)
     bool prof = false;
     std::vector<hipEvent_t> ev_pool;               // free events
@@ -637,6 +641,32 @@ hipError_t launch_argmax_blocks(hipStream_t s, const double *score, const uint8_
                                 int64_t index_offset, sbo_key *block_keys);
 // Reduce nblocks keys into *out (device pointer).
 hipError_t launch_reduce_keys(hipStream_t s, const sbo_key *keys, int64_t nblocks, sbo_key *out);
+
+// Model evidence (evidence.hip).  launch_evidence_norms: c[i] = (K^-1)_ii =
+// sum_{k >= i} X_ki^2 from the f64 inverse X (lower, lda ld), and per 64-point
+// k-tile t the kEvSums sums at sums[t kEvSums ..]: |alpha|, sqrt(c), c, alpha^2,
+// alpha r, alpha, log L_ii (L: the f32 factor, lda ldl), z^2 and the LOO log
+// predictive, r = obs - m0.  launch_evidence_loo: y_i - alpha_i / c_i and 1 / c_i
+// at order[i] (device array; either output may be null).  launch_evidence_gram:
+// per item (int4: k-tile I, k-tile J >= I, first row k0, k0 == 64 J) the
+// contraction of (alpha_I alpha_J^T [k0 == 64 J] - X[k0 .. k0 + kEvChunk, I]^T
+// X[.., J]) with G_ij = sf2 exp(-d^2 / 2 l^2) d^2 / l^2 into slots[item] (halved
+// for I == J), then *out = the slots' sum in a fixed order.
+// evidence_pairs (host): the cutoff's drop set (T x T, symmetric) over the
+// k-tile boxes (x0, x1, y0, y1) under `budget`, and the summed bound.
+constexpr int kEvSums = 9;
+constexpr int kEvChunk = 1024;
+constexpr double kEvLog2Pi = 1.8378770664093454836;   // log 2 pi
+hipError_t launch_evidence_norms(hipStream_t s, const double *X, int64_t ld, int64_t n, const double *alpha,
+                                 const double *z, const float *obs, const float *L, int64_t ldl, double m0, double *c,
+                                 double *sums);
+hipError_t launch_evidence_loo(hipStream_t s, const double *c, const double *alpha, const float *obs,
+                               const int64_t *order, int64_t n, double *loo_mean, double *loo_var);
+hipError_t launch_evidence_gram(hipStream_t s, const double *X, int64_t ld, int64_t n, const float *x, const float *y,
+                                const double *alpha, const int4 *items, int64_t n_items, double ell, double sf2,
+                                double *slots, double *out);
+void evidence_pairs(const float *boxes, const double *alpha_l1, const double *sqrtc_l1, int64_t T, double ell,
+                    double sf2, double budget, uint8_t *drop, double *bound);
 
 inline int64_t acq_blocks(int64_t m) { return (m + kAcqThreads - 1) / kAcqThreads; }
 

@@ -194,6 +194,68 @@ class TerrainMapper:
     def n(self) -> int:
         return int(self._lib.sbo_num_train(self.ctx.handle))
 
+    # ------------------------------------------------------------- evidence
+    def evidence(self, loo: bool = False) -> dict:
+        """Model evidence of the current fit (sbo_evidence): ``lml``, its parts
+        ``data_fit`` and ``log_det``, ``grad`` = d lml / d (log length_scale,
+        log sigma_f, log noise_level, prior_mean), ``loo_log_pred``, and what
+        the k-tile pair cutoff of grad[0] did (``dropped``, ``pairs_kept`` of
+        ``pairs_total``, ``grad_err_bound`` within ``grad_budget``).  With
+        ``loo`` also ``loo_mean`` / ``loo_var``: the leave-one-out predictive
+        of every training point, in the caller's order (host f64 arrays)."""
+        r = N.sbo_evidence_info()
+        r.struct_size = ctypes.sizeof(r)
+        n = self.n
+        mean = np.empty(n, np.float64) if loo else None
+        var = np.empty(n, np.float64) if loo else None
+        self.ctx.check(self._lib.sbo_evidence(self.ctx.handle, ctypes.byref(r), _ptr(mean), _ptr(var), 0))
+        d = {f: getattr(r, f) for f, _ in N.sbo_evidence_info._fields_ if f not in ("struct_size", "grad")}
+        d["grad"] = np.array(r.grad[:], np.float64)
+        if loo:
+            d["loo_mean"], d["loo_var"] = mean, var
+        return d
+
+    def fit_hyper(self, x, y, obs, *, bounds=None, max_iter: int = 50) -> Hyper:
+        """Maximise the log marginal likelihood over (length_scale, sigma_f,
+        noise_level) by scipy's L-BFGS-B on their logarithms, starting at
+        ``self.hyper`` (the prior mean stays as it is).  Every evaluation is a
+        ``fit`` plus ``evidence`` on the device; a fit that is not positive
+        definite counts as a very low evidence.  ``bounds``: three (low, high)
+        pairs; by default [1/20, 20] x the starting value of each parameter,
+        the noise not below 1e-4 x the starting sf2.  Leaves the mapper fitted
+        at the returned hyper-parameters, which also become ``self.hyper``."""
+        from scipy.optimize import minimize
+        h0 = self.hyper
+        start = np.array([h0.length_scale, h0.sigma_f, h0.noise_level], np.float64)
+        if bounds is None:
+            bounds = [(v / 20.0, v * 20.0) for v in start]
+            bounds[2] = (max(bounds[2][0], 1e-4 * h0.sf2), max(bounds[2][1], 2e-4 * h0.sf2))
+        lb = [(float(np.log(lo)), float(np.log(hi))) for lo, hi in bounds]
+        last = {"theta": None}
+
+        def hyper_at(theta):
+            ell, sf, noise = np.exp(theta)
+            return Hyper(float(ell), float(sf), float(noise), h0.prior_mean)
+
+        def neg_lml(theta):
+            self.hyper = hyper_at(theta)
+            last["theta"] = None
+            try:
+                self.fit(x, y, obs)
+            except N.NotSPDError:
+                return 1e25, np.zeros(3)
+            last["theta"] = np.array(theta, np.float64)
+            e = self.evidence()
+            return -e["lml"], -e["grad"][:3]
+
+        t0 = np.clip(np.log(start), [b[0] for b in lb], [b[1] for b in lb])
+        res = minimize(neg_lml, t0, jac=True, method="L-BFGS-B", bounds=lb, options={"maxiter": int(max_iter)})
+        best = np.asarray(res.x, np.float64)
+        self.hyper = hyper_at(best)
+        if last["theta"] is None or not np.array_equal(last["theta"], best):
+            self.fit(x, y, obs)
+        return self.hyper
+
     # ----------------------------------------------------------- prediction
     def predict(self, qx, qy, *, out=None, async_: bool = False):
         """Posterior mean and latent std at the queries (f32)."""
