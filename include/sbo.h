@@ -409,6 +409,22 @@ SBO_API sbo_status sbo_get_factor(sbo_ctx *ctx, float *L, float *alpha, uint32_t
  * batch starts at the current N).  Host pointers, no context, no device. */
 SBO_API sbo_status sbo_kd_order(const float *x, const float *y, int64_t n, int64_t first_offset, int64_t *perm);
 
+/* The layout of the recursive f64 inverse of an n-column factor (leading
+ * dimension ld) as the fit plans it, for base size `base`, `panels`, leaves
+ * mode 0 / 1 / 2 (SBO_OPT_INV_LEAVES), `digits` wanted, the effective smallest
+ * sliced split oz_min and 1 or 2 lanes: int64 records of 12 values.  Record 0:
+ * {nodes, scratch doubles, leaves-by-doubling scratch doubles, leaves by
+ * doubling, first 128-column info slot, info slots, workspace bytes of lane 0,
+ * of lane 1, info slots of the top node's first half, two-lane top, 0, 0};
+ * then one record per node in the recursion's order: {first column, n, split
+ * h (0: a base case), offset of its S in the scratch (-1: none), first info
+ * slot, sliced, lane, left child, right child (node indices, -1: none),
+ * workspace bytes its products need, 0, 0}.  *count: the values the plan
+ * takes; they are written when cap >= *count (cap 0 only asks for the count).
+ * No context, no device. */
+SBO_API sbo_status sbo_debug_inverse_plan(int64_t n, int64_t ld, int64_t base, int64_t panels, int leaves, int digits,
+                                          int64_t oz_min, int lanes, int64_t *out, int64_t cap, int64_t *count);
+
 /* Options.  SBO_OPT_INVERSE_BITS (32 | 64, default 64): precision in which
  * L^-1 is computed before sf2 * L^-1 is rounded to f32 for the predictive
  * sweep (64 = widen L, rocsolver_dtrtri; 32 = rocsolver_strtri).  Takes

@@ -36,7 +36,7 @@ EXPORTS = (
     "sbo_kd_order", "sbo_get_probe", "sbo_keys_reduce", "sbo_get_inverse_check", "sbo_trim", "sbo_warmup",
     "sbo_debug_gz_gemm", "sbo_debug_gz_gemm_packed", "sbo_debug_x3_operand", "sbo_debug_plan",
     "sbo_tick_stream", "sbo_get_stream", "sbo_stream_reset", "sbo_debug_stream_state",
-    "sbo_evidence", "sbo_debug_evidence_pairs",
+    "sbo_evidence", "sbo_debug_evidence_pairs", "sbo_debug_inverse_plan",
 )
 # sbo_stream_reason (include/sbo.h, sbo_get_stream)
 STREAM_REASONS = ("FIRST", "UPDATED", "QUERIES_CHANGED", "REFIT", "NO_INVERSE", "ROWS_OVER_CAP", "BUDGET", "RESET")
@@ -245,6 +245,8 @@ def lib():
     L.sbo_get_order.restype = st
     L.sbo_kd_order.argtypes = [vp, vp, i64, i64, vp]
     L.sbo_kd_order.restype = st
+    L.sbo_debug_inverse_plan.argtypes = [i64, i64, i64, i64, ctypes.c_int, ctypes.c_int, i64, ctypes.c_int, vp, i64, vp]
+    L.sbo_debug_inverse_plan.restype = st
     L.sbo_get_inverse.argtypes = [vp, vp]
     L.sbo_get_inverse.restype = st
     L.sbo_profile.argtypes = [vp, i32]

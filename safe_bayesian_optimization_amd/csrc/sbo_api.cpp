@@ -16,39 +16,17 @@
 #include <thread>
 #include <vector>
 
+#include "inverse.hpp"
+#include "sbo_host.hpp"
 #include "sbo_internal.hpp"
 
 using sbo::DevBuf;
+using sbo::kAppendInvGemm;
+using sbo::kAppendInvRows;
 
 namespace {
 
 constexpr const char *kVersion = "sbo-mi355x 0.1.0";
-
-#define SBO_HIP(expr)                                                                   \
-    do {                                                                                \
-        hipError_t e_ = (expr);                                                         \
-        if (e_ != hipSuccess) {                                                         \
-            ctx->err = std::string(#expr) + ": " + hipGetErrorString(e_);               \
-            return e_ == hipErrorOutOfMemory ? SBO_E_OOM : SBO_E_DEVICE;                \
-        }                                                                               \
-    } while (0)
-
-#define SBO_BLAS(expr)                                                                  \
-    do {                                                                                \
-        rocblas_status s_ = (expr);                                                     \
-        if (s_ != rocblas_status_success) {                                             \
-            ctx->err = std::string(#expr) + ": " + rocblas_status_to_string(s_);        \
-            return s_ == rocblas_status_memory_error ? SBO_E_OOM : SBO_E_DEVICE;        \
-        }                                                                               \
-    } while (0)
-
-#define SBO_CHECK(cond, code, msg)                                                      \
-    do {                                                                                \
-        if (!(cond)) {                                                                  \
-            ctx->err = (msg);                                                           \
-            return (code);                                                              \
-        }                                                                               \
-    } while (0)
 
 bool dev(uint32_t flags) { return (flags & SBO_DEVICE_PTRS) != 0; }
 
@@ -58,94 +36,15 @@ sbo_status finish(sbo_ctx *ctx, uint32_t flags) {
     return SBO_OK;
 }
 
-// rocSOLVER info slots: slot 0 for single calls, 1.. for the base cases of
-// the recursive inverse (one each, so a later success cannot overwrite an
-// earlier singular block); refresh_operand reads them all.  The recursion
-// splits on multiples of the base size b = SBO_OPT_INV_BASE >= 1024
-// (inverse_split), so an n-column inverse has ceil(n / b) base cases (the last
-// one possibly a single column), and ceil(n / b) + 1 <= n/512 + 2 slots
-// always suffice.  After them, one slot per 128-column diagonal block for the
-// batched leaves by doubling (SBO_OPT_INV_LEAVES 2, inverse_leaves).
-int64_t info_leaf128(int64_t n) { return std::max<int64_t>(64, n / 512 + 2); }
 #ifndef SBO_FUSED_TN
 #define SBO_FUSED_TN 1
 #endif
-int64_t info_slots(int64_t n) { return info_leaf128(n) + n / 128 + 1; }
 
-// Appends of at most kAppendInvRows points solve their factor rows and extend
-// the inverse by matrix-vector products with the kept f64 inverse
-// (bandwidth-bound, one pass over its lower triangle per point); up to
-// kAppendInvGemm points the factor rows by one f64 GEMM with it (rocBLAS strsm
-// of a b x n block ran as hundreds of small launches); alpha is updated from
-// the kept z = L^-1 r up to kAppendInvGemm points too.  Larger batches: the
-// blocked level-3 forms.
-constexpr int64_t kAppendInvRows = 8;
-constexpr int64_t kAppendInvGemm = 256;
+// The fit's f64 inverse holds exactly n rows: L^-1 in Linv, computed in f64
+// (SBO_OPT_INVERSE_BITS 64), current for the first n training points.
+bool inverse_current(const sbo_ctx *ctx, int64_t n) { return ctx->inverse_bits == 64 && ctx->linv_n == n; }
 
-// X = L^-1 in place for the lower-triangular f64 matrix at Li (column-major,
-// lda ld; its strictly upper part is zero), by the block recursion
-//     [A 0; B C]^-1 = [A^-1 0; -C^-1 B A^-1  C^-1].
-// rocSOLVER's dtrtri forms the two products with the triangular inverses as
-// full dgemms (2n^3/3 flops at the top of its recursion); here each product
-// is a row of dgemms over panels of width nb that leave out the zero part
-// of the triangle (n^3/3 + O(n^2 nb) flops):
-//     S[:, p] = B[:, p0:h] Ainv[p0:h, p]          (column panels p of A^-1)
-//     X21[p, :] = -Cinv[p, 0:p1] S[0:p1, :]       (row panels p of C^-1)
-// Each panel's diagonal block is multiplied in full; its strictly upper part
-// is zero (widen() writes it, neither rocSOLVER nor this recursion touches
-// it).  The first half (A^-1, then S) reads only the factor's left h
-// columns, so the fit can run it beside the Cholesky's last steps
-// (blocked_potrf, SBO_OPT_INV_OVERLAP); the second half (C^-1, X21) follows
-// the factor.  S: (n - h) x h doubles of scratch, C^-1's own scratch after
-// it (inverse_scratch).  hb: the rocBLAS handle (and so the stream) to run on;
-// slot: the next free info slot (one per dtrtri base case).
-// (SBO_OPT_INV_BASE: the dtrtri base-case size, default 2048, >= 1024 so
-// that info_slots holds; SBO_OPT_INV_PANELS: the products' panels per half,
-// default 16, at least 512 columns each: C4 warm fit 58.0 ms at 8 panels,
-// 56.0 at 16; a 256-column floor: 59.8 at 16, 68 at 32, profiles/r3_fit_invtune*.log)
-// The split lands on a multiple of the base size b (SBO_OPT_INV_BASE, a
-// multiple of 128): every base case is then a b x b diagonal block at a
-// multiple of b (the last one partial), so all of them can be inverted up
-// front in one batched rocSOLVER call (inverse_leaves).
-int64_t inverse_split(int64_t n, int64_t b) { return ((n + b - 1) / b + 1) / 2 * b; }
-
-int64_t inverse_scratch(int64_t n, int64_t base) {
-    if (n <= base) return 0;
-    const int64_t h = inverse_split(n, base), m = n - h;
-    return h * m + std::max(inverse_scratch(h, base), inverse_scratch(m, base));
-}
-// with the two halves' inverses side by side (inverse_lower_f64_par)
-int64_t inverse_scratch_par(int64_t n, int64_t base) {
-    if (n <= base) return 0;
-    const int64_t h = inverse_split(n, base), m = n - h;
-    return h * m + inverse_scratch(h, base) + inverse_scratch(m, base);
-}
-// dtrtri base cases of an n-column recursion (one info slot each)
-int inverse_base_cases(int64_t n, int64_t base) {
-    if (n <= base) return 1;
-    const int64_t h = inverse_split(n, base);
-    return inverse_base_cases(h, base) + inverse_base_cases(n - h, base);
-}
-
-// How one inverse runs its recursion: the digits of its int8-sliced products
-// (0: every product a dgemm), and whether its base cases are already inverted
-// (inverse_leaves ran: the recursion then only counts their info slots).
-struct InvMode {
-    int digits = 0;
-    bool leaves_done = false;
-};
-sbo_status inverse_lower_f64(sbo_ctx *ctx, rocblas_handle hb, double *Li, int64_t n, int64_t ld, double *S,
-                             int &slot, InvMode mode, sbo::DevBuf *ozws = nullptr);
-// SBO_OPT_INV_OZ: a level of the recursion whose split is at least
-// SBO_OPT_INV_OZ_MIN runs its two products as the sliced GEMM (K <= 16384);
-// the levels below keep dgemms.  Automatic (0, default): 2048 in the inverses
-// of N >= 12288 (C4: fit 42.0 -> 41.3 ms, profiles/r5_inv_oz_min_gz16.log),
-// else 4096 (below that the 2048 level's products are too small to pay for
-// their packs, and a sliced inverse brings the guard's check)
-bool oz_level(const sbo_ctx *ctx, int digits, int64_t h, int64_t m) {
-    const int64_t mn = ctx->inv_oz_min > 0 ? ctx->inv_oz_min : (ctx->n >= 12288 ? 2048 : 4096);
-    return digits != 0 && h >= mn && h <= 16384 && m <= 16384;
-}
+// The guard's policy for the f64 inverse (inverse.cpp runs the inverse itself).
 // The digits of the current fit's sliced products (SBO_OPT_INV_OZ_ADAPT:
 // chosen per fit by choose_inv_digits; 0 with SBO_OPT_INV_OZ 0)
 int inv_digits(const sbo_ctx *ctx) {
@@ -236,238 +135,6 @@ void record_inv_digits(sbo_ctx *ctx, const sbo_inv_check &r) {
             break;
         }
     ctx->inv_oz_next = nd;
-}
-
-// Has a blocked factorization run on this context?  Its set-up (chol_streams)
-// leaves aux_stream, its rocBLAS handle and the events ev_panel, ev_trail,
-// ev_pack, ev_poz, which the inverse's two-stream top level and the refresh's
-// side work use without making them.  The four events are created together,
-// so ev_panel stands for all of them.  The answer depends on history, not on
-// the options now: a context whose fits so far all ran rocSOLVER's spotrf
-// (SBO_OPT_CHOLESKY 0) has no aux stream and its refresh stays single-stream;
-// one that has run the blocked factorization once keeps it.
-bool aux_ready(const sbo_ctx *ctx) { return ctx->blas_aux && ctx->aux_stream && ctx->ev_panel; }
-
-// does the recursive inverse of n columns slice any of its products?  The
-// same gate as inverse_lower_f64_par's: the sliced GEMM's workspaces are handed
-// down only when the top split slices (the levels below slice with them
-// where oz_level allows; with the top split over 16384 it is all dgemm), and
-// only on the two-stream path.
-bool inverse_sliced(const sbo_ctx *ctx, int digits, int64_t n) {
-    if (n <= ctx->inv_base || !aux_ready(ctx)) return false;
-    const int64_t h = inverse_split(n, ctx->inv_base);
-    return oz_level(ctx, digits, h, n - h);
-}
-
-// A^-1 (recursion scratch scr), then S = B A^-1
-// dgemm panel width of a product of the recursion at split h: h / panels,
-// at least 512 columns -- and at least 1024 for 2048 < h <= 6144, where
-// rocBLAS dgemm with ~4096 rows and fewer than 1024 columns at K > 2048 ran
-// at half speed (38.5 vs 76.5 TF at 4096 x 512 x 4096 against 4096 x 1024 x
-// 4096, tools/r3_dgemm_probe.cpp, profiles/r3_dgemm_probe.log)
-int64_t inverse_panel(const sbo_ctx *ctx, int64_t h) {
-    int64_t nb = std::max<int64_t>(512, sbo::round_up(h / ctx->inv_panels, 128));
-    if (h > 2048 && h <= 6144) nb = std::max<int64_t>(nb, 1024);
-    return nb;
-}
-
-sbo_status inverse_first_half(sbo_ctx *ctx, rocblas_handle hb, double *Li, int64_t n, int64_t ld, double *S,
-                              double *scr, int &slot, InvMode mode, bool a_done = false,
-                              sbo::DevBuf *ozws = nullptr) {
-    const int64_t h = inverse_split(n, ctx->inv_base), m = n - h;
-    if (!a_done)
-        if (sbo_status st = inverse_lower_f64(ctx, hb, Li, h, ld, scr, slot, mode, ozws); st != SBO_OK) return st;
-    if (ozws && oz_level(ctx, mode.digits, h, m)) {   // S = L21 A^-1 in one sliced GEMM (A^-1 lower triangular)
-        hipStream_t st;
-        SBO_BLAS(rocblas_get_stream(hb, &st));
-        SBO_HIP(ozws->reserve(sbo::gz_workspace_bytes(m, h, h, mode.digits)));
-        SBO_HIP(sbo::launch_gz_gemm(st, mode.digits, Li + h, ld, Li, ld, m, h, h, 1.0, S, m, sbo::kGzTriBLower,
-                                    ozws->as<char>()));
-        return SBO_OK;
-    }
-    SBO_BLAS(rocblas_set_pointer_mode(hb, rocblas_pointer_mode_host));
-    const double one = 1.0, zero = 0.0;
-    const int64_t nb = inverse_panel(ctx, h);
-    for (int64_t p0 = 0; p0 < h; p0 += nb) {
-        const int64_t w = std::min(nb, h - p0);
-        SBO_BLAS(rocblas_dgemm(hb, rocblas_operation_none, rocblas_operation_none, (rocblas_int)m, (rocblas_int)w,
-                               (rocblas_int)(h - p0), &one, Li + h + p0 * ld, (rocblas_int)ld, Li + p0 + p0 * ld,
-                               (rocblas_int)ld, &zero, S + p0 * m, (rocblas_int)m));
-    }
-    return SBO_OK;
-}
-
-// C^-1 (recursion scratch scr; skipped when c_done), then X21 = -C^-1 S
-sbo_status inverse_second_half(sbo_ctx *ctx, rocblas_handle hb, double *Li, int64_t n, int64_t ld, double *S,
-                               double *scr, int &slot, InvMode mode, bool c_done = false,
-                               sbo::DevBuf *ozws = nullptr) {
-    const int64_t h = inverse_split(n, ctx->inv_base), m = n - h;
-    double *B = Li + h, *C = Li + h + h * ld;
-    if (!c_done)
-        if (sbo_status st = inverse_lower_f64(ctx, hb, C, m, ld, scr, slot, mode, ozws); st != SBO_OK) return st;
-    if (ozws && oz_level(ctx, mode.digits, h, m)) {
-        // X21 = -C^-1 S in one sliced GEMM, as X21^T = -S^T C^-T: the
-        // triangular operand then bounds the k loop per column tile, so the
-        // workgroups of one column run in step as in S = L21 A^-1 (the direct
-        // form, C^-1 as a lower-triangular op(A): 7.4 vs 5.x ms at C4)
-        hipStream_t st;
-        SBO_BLAS(rocblas_get_stream(hb, &st));
-        SBO_HIP(ozws->reserve(sbo::gz_workspace_bytes(h, m, m, mode.digits)));
-        SBO_HIP(sbo::launch_gz_gemm(st, mode.digits, S, m, C, ld, h, m, m, -1.0, B, ld,
-                                    sbo::kGzTransA | sbo::kGzTransB | sbo::kGzTriBUpper | sbo::kGzTransC,
-                                    ozws->as<char>()));
-        return SBO_OK;
-    }
-    SBO_BLAS(rocblas_set_pointer_mode(hb, rocblas_pointer_mode_host));
-    const double minus_one = -1.0, zero = 0.0;
-    const int64_t nb = inverse_panel(ctx, h);
-    for (int64_t p0 = 0; p0 < m; p0 += nb) {
-        const int64_t w = std::min(nb, m - p0);
-        SBO_BLAS(rocblas_dgemm(hb, rocblas_operation_none, rocblas_operation_none, (rocblas_int)w, (rocblas_int)h,
-                               (rocblas_int)(p0 + w), &minus_one, C + p0, (rocblas_int)ld, S, (rocblas_int)m, &zero,
-                               B + p0, (rocblas_int)ld));
-    }
-    return SBO_OK;
-}
-
-sbo_status inverse_lower_f64(sbo_ctx *ctx, rocblas_handle hb, double *Li, int64_t n, int64_t ld, double *S,
-                             int &slot, InvMode mode, sbo::DevBuf *ozws) {
-    if (n <= ctx->inv_base) {
-        rocblas_int *info = ctx->info.as<rocblas_int>() + 1 + slot++;
-        if (!mode.leaves_done)
-            SBO_BLAS(rocsolver_dtrtri(hb, rocblas_fill_lower, rocblas_diagonal_non_unit, (rocblas_int)n, Li,
-                                      (rocblas_int)ld, info));
-        return SBO_OK;
-    }
-    const int64_t h = inverse_split(n, ctx->inv_base), m = n - h;
-    if (sbo_status st = inverse_first_half(ctx, hb, Li, n, ld, S, S + h * m, slot, mode, false, ozws); st != SBO_OK)
-        return st;
-    return inverse_second_half(ctx, hb, Li, n, ld, S, S + h * m, slot, mode, false, ozws);
-}
-
-// Every base case of the recursion over the n columns at Li -- the b x b
-// diagonal blocks at multiples of b = inv_base, the last one partial -- in
-// one strided-batched rocSOLVER dtrtri (+ one call for the partial block),
-// info slots in the recursion's order (block k: slot k).  One at a time
-// inside the recursion each 2048 block took ~0.46 ms of mostly idle chip
-// (C4: eight of them; profiles/r3_fit_timeline_leaves.txt).
-// SBO_OPT_INV_LEAVES 2 (b a power-of-two multiple of 128): the full leaves
-// by doubling instead -- every 128-column diagonal block of them in one
-// batched dtrtri, then per level s = 128, 256, .., b/2 all the 2s-column
-// blocks at once, [A 0; B C]^-1 from A^-1 and C^-1 by two strided-batched
-// dgemms through scratch T (T = B A^-1, X21 = -C^-1 T).  From s = 512 up
-// each product is two dgemms that leave out the triangular factor's zero
-// quarter (3/4 of the flops).  rocSOLVER's batched dtrtri runs its own
-// doubling as ~100 launches with a copy of the leaves and mostly small
-// tiles (C4: 1.74 ms for 8 leaves of 2048).  Warm fits: C4 29.1 -> 28.4 ms,
-// C3 9.7 -> 9.5; with fewer than four leaves the batches are too small to
-// fill the chip (C2's one leaf: 2.0 -> 2.3 ms) and rocSOLVER keeps them
-// (profiles/r6_inv_leaves_doubling.log).  Scratch: leaf_scratch(n) doubles.
-bool leaves_by_doubling(const sbo_ctx *ctx, int64_t n) {
-    const int64_t b = ctx->inv_base;
-    return ctx->inv_leaves_own && n / b >= 4 && b % 128 == 0 && ((b / 128) & (b / 128 - 1)) == 0;
-}
-int64_t leaf_scratch(const sbo_ctx *ctx, int64_t n) {
-    return leaves_by_doubling(ctx, n) ? (n / ctx->inv_base) * ctx->inv_base * ctx->inv_base / 4 : 0;
-}
-sbo_status leaves_doubling(sbo_ctx *ctx, rocblas_handle hb, double *Li, int64_t n, int64_t ld, double *T) {
-    const int64_t b = ctx->inv_base, nf = n / b, nb128 = nf * b / 128;
-    rocblas_int *info128 = ctx->info.as<rocblas_int>() + info_leaf128(n);
-    SBO_BLAS(rocsolver_dtrtri_strided_batched(hb, rocblas_fill_lower, rocblas_diagonal_non_unit, 128, Li,
-                                              (rocblas_int)ld, (rocblas_stride)(128 * (ld + 1)), info128,
-                                              (rocblas_int)nb128));
-    SBO_BLAS(rocblas_set_pointer_mode(hb, rocblas_pointer_mode_host));
-    const double one = 1.0, minus_one = -1.0, zero = 0.0;
-    const auto N_ = rocblas_operation_none;
-    for (int64_t s = 128; s < b; s *= 2) {
-        const rocblas_int cnt = (rocblas_int)(nf * b / (2 * s)), is = (rocblas_int)s, il = (rocblas_int)ld;
-        const rocblas_stride st = (rocblas_stride)(2 * s * (ld + 1)), sT = (rocblas_stride)(s * s);
-        const double *Ainv = Li, *Cinv = Li + s * (ld + 1);
-        double *B = Li + s;
-        if (s < 512) {
-            SBO_BLAS(rocblas_dgemm_strided_batched(hb, N_, N_, is, is, is, &one, B, il, st, Ainv, il, st, &zero, T, is,
-                                                   sT, cnt));
-            SBO_BLAS(rocblas_dgemm_strided_batched(hb, N_, N_, is, is, is, &minus_one, Cinv, il, st, T, is, sT, &zero,
-                                                   B, il, st, cnt));
-            continue;
-        }
-        const int64_t h = s / 2;
-        const rocblas_int ih = (rocblas_int)h;
-        // T[:, 0:h] = B A^-1[:, 0:h]; T[:, h:s] = B[:, h:s] A^-1[h:s, h:s]
-        SBO_BLAS(rocblas_dgemm_strided_batched(hb, N_, N_, is, ih, is, &one, B, il, st, Ainv, il, st, &zero, T, is, sT,
-                                               cnt));
-        SBO_BLAS(rocblas_dgemm_strided_batched(hb, N_, N_, is, ih, ih, &one, B + h * ld, il, st, Ainv + h * (ld + 1),
-                                               il, st, &zero, T + h * s, is, sT, cnt));
-        // X21[0:h, :] = -C^-1[0:h, 0:h] T[0:h, :]; X21[h:s, :] = -C^-1[h:s, :] T
-        SBO_BLAS(rocblas_dgemm_strided_batched(hb, N_, N_, ih, is, ih, &minus_one, Cinv, il, st, T, is, sT, &zero, B,
-                                               il, st, cnt));
-        SBO_BLAS(rocblas_dgemm_strided_batched(hb, N_, N_, ih, is, is, &minus_one, Cinv + h, il, st, T, is, sT, &zero,
-                                               B + h, il, st, cnt));
-    }
-    return SBO_OK;
-}
-
-sbo_status inverse_leaves(sbo_ctx *ctx, rocblas_handle hb, double *Li, int64_t n, int64_t ld, double *T) {
-    const int64_t b = ctx->inv_base, nf = n / b, r = n - nf * b;
-    rocblas_int *info = ctx->info.as<rocblas_int>() + 1;
-    if (leaves_by_doubling(ctx, n)) {
-        if (sbo_status st = leaves_doubling(ctx, hb, Li, n, ld, T); st != SBO_OK) return st;
-    } else if (nf > 0)
-        SBO_BLAS(rocsolver_dtrtri_strided_batched(hb, rocblas_fill_lower, rocblas_diagonal_non_unit, (rocblas_int)b,
-                                                  Li, (rocblas_int)ld, (rocblas_stride)(b * (ld + 1)), info,
-                                                  (rocblas_int)nf));
-    if (r > 0)
-        SBO_BLAS(rocsolver_dtrtri(hb, rocblas_fill_lower, rocblas_diagonal_non_unit, (rocblas_int)r,
-                                  Li + nf * b * (ld + 1), (rocblas_int)ld, info + nf));
-    return SBO_OK;
-}
-
-// The top of the recursion with its two independent halves side by side:
-// C^-1 on aux_stream (the Cholesky's look-ahead stream and rocBLAS handle,
-// idle by now) while `stream` computes A^-1 and S = B A^-1, then X21 once
-// both are done.  The lower levels' GEMMs are too small to fill the chip on
-// their own.  Enqueue order: A^-1 first, then C^-1, then S -- the host spends
-// ~3 ms issuing a half's ~90 rocSOLVER/rocBLAS launches, and C^-1 is needed
-// only after S (C4 trace: with C^-1 issued first, `stream` sat idle for
-// those 3 ms; profiles/r3_fit_timeline_invorder.txt).  Scratch:
-// inverse_scratch_par(n); info slots as the sequential recursion's (C's base
-// cases after A's).
-// mode.digits != 0: the top split slices (inverse_sliced; the refresh plan
-// decides it once).
-sbo_status inverse_lower_f64_par(sbo_ctx *ctx, double *Li, int64_t n, int64_t ld, double *S, InvMode mode) {
-    int slot = 0;
-    if (n <= ctx->inv_base || !aux_ready(ctx))
-        return inverse_lower_f64(ctx, ctx->blas, Li, n, ld, S, slot, mode);
-    const int64_t h = inverse_split(n, ctx->inv_base), m = n - h;
-    double *scrA = S + h * m, *scrC = scrA + inverse_scratch(h, ctx->inv_base);
-    int slotC = inverse_base_cases(h, ctx->inv_base);
-    // SBO_OPT_INV_OZ: the products of the levels with splits >= 4096 on the
-    // int8 matrix cores (oz_level), one workspace per stream, sized up front
-    // (a reserve that reallocates mid-fit would wait for the device)
-    sbo::DevBuf *ozA = nullptr, *ozC = nullptr;
-    if (mode.digits != 0) {
-        SBO_HIP(ctx->gzws.reserve(std::max(sbo::gz_workspace_bytes(m, h, h, mode.digits),
-                                           sbo::gz_workspace_bytes(h, m, m, mode.digits))));
-        SBO_HIP(ctx->gzws_aux.reserve(sbo::gz_workspace_bytes(m, m, m, mode.digits)));
-        ozA = &ctx->gzws;
-        ozC = &ctx->gzws_aux;
-    }
-    SBO_HIP(hipEventRecord(ctx->ev_panel, ctx->stream));            // Li widened
-    if (sbo_status st = inverse_lower_f64(ctx, ctx->blas, Li, h, ld, scrA, slot, mode, ozA); st != SBO_OK) return st;
-    SBO_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_panel, 0));
-    SBO_BLAS(rocblas_set_pointer_mode(ctx->blas_aux, rocblas_pointer_mode_host));
-    if (sbo_status st = inverse_lower_f64(ctx, ctx->blas_aux, Li + h + h * ld, m, ld, scrC, slotC, mode, ozC);
-        st != SBO_OK) {
-        (void)hipStreamSynchronize(ctx->aux_stream);
-        return st;
-    }
-    SBO_HIP(hipEventRecord(ctx->ev_trail, ctx->aux_stream));
-    if (sbo_status st = inverse_first_half(ctx, ctx->blas, Li, n, ld, S, scrA, slot, mode, true, ozA); st != SBO_OK) {
-        (void)hipStreamSynchronize(ctx->aux_stream);
-        return st;
-    }
-    SBO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_trail, 0));
-    return inverse_second_half(ctx, ctx->blas, Li, n, ld, S, nullptr, slot, mode, true, ozA);
 }
 
 sbo_status check_hyper(sbo_ctx *ctx, const sbo_hyper &h) {
@@ -983,8 +650,8 @@ sbo_status inverse_check_read(sbo_ctx *ctx, sbo_inv_check &r) {
 // What blocked_potrf hands to the refresh of the factor it just wrote.
 struct FactorHandover {
     int64_t widened_n = 0;   // the factor (n columns) is already widened into Linv
-    int64_t half_n = 0;      // n of a factor whose inverse's first half is done (inverse_finish_half ends it)
-    int half_slots = 0;      // the info slots that half used (1 .. half_slots)
+    int64_t half_n = 0;      // n of a factor whose inverse's first half is done (inverse_finish_half ends it) ...
+    sbo::InvPlan half;       // ... by this plan: its layout, its reservation, the info slots that half used
     rocblas_int *info = nullptr;   // the info slots the factorization wrote (slot 0: the leading minor)
 };
 
@@ -1003,6 +670,8 @@ struct RefreshPlan {
     size_t old_tiles;    // packed tiles of the row blocks below I0, kept
     bool half_done;      // the inverse's first half ran beside the Cholesky (blocked_potrf) ...
     int half_slots;      // ... its info slots 1 .. half_slots stay, the rest are cleared
+    sbo::InvPlan inv;    // the recursion's plan (half_done: the one that half ran by; empty: no recursion)
+    int64_t info_slots;  // the rocSOLVER info slots of an n-column refresh
     bool widened;        // the factor is already widened into Linv
     int digits;          // of this inverse's sliced products (0: dgemm)
     bool guard;          // the accuracy guard runs on this inverse
@@ -1020,15 +689,20 @@ RefreshPlan plan_refresh(const sbo_ctx *ctx, int64_t n_old, const FactorHandover
     p.nI = p.npad / sbo::kBM;
     p.sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
     p.f64 = ctx->inverse_bits == 64;
-    p.incr = n_old > 0 && p.f64 && ctx->linv_n == n_old && ctx->npad > 0;
+    p.incr = n_old > 0 && inverse_current(ctx, n_old) && ctx->npad > 0;
     p.n_old = p.incr ? n_old : 0;
     p.I0 = p.n_old / sbo::kBM;
     p.old_tiles = (size_t)sbo::total_tiles(p.I0);
     p.half_done = p.f64 && ctx->inverse_rec && !p.incr && ho.half_n == p.n;
-    p.half_slots = ho.half_slots;
     p.widened = ho.widened_n == p.n;
     const int want = attempt == kInvDgemm ? 0 : attempt == kInvFullDigits ? ctx->inv_oz : inv_digits(ctx);
-    const bool sliced = p.f64 && !p.incr && ctx->inverse_rec && !p.half_done && inverse_sliced(ctx, want, p.n);
+    if (p.half_done)
+        p.inv = ho.half;
+    else if (p.f64 && !p.incr && ctx->inverse_rec)
+        p.inv = sbo::plan_inverse(inv_config(ctx, want), p.n, p.ld);
+    p.half_slots = p.half_done ? p.inv.half_slots() : 0;
+    p.info_slots = sbo::inv_info(p.n).total;
+    const bool sliced = p.inv.sliced();
     p.digits = sliced ? want : 0;
     p.guard = p.f64 && !p.incr &&
               (ctx->inv_check == 2 || attempt == kInvDgemm || (ctx->inv_check == 1 && sliced));
@@ -1045,7 +719,7 @@ RefreshPlan plan_refresh(const sbo_ctx *ctx, int64_t n_old, const FactorHandover
 // The buffers every refresh writes, and the rocSOLVER info slots cleared (a
 // first half that ran beside the Cholesky keeps its own).
 sbo_status refresh_begin(sbo_ctx *ctx, const RefreshPlan &p) {
-    const int64_t nslots = info_slots(p.n);
+    const int64_t nslots = p.info_slots;
     SBO_HIP(ctx->info.reserve(sizeof(rocblas_int) * (size_t)nslots));
     rocblas_int *info = ctx->info.as<rocblas_int>();
     SBO_HIP(grow_keep(ctx, ctx->aug, sizeof(float) * (size_t)sbo::total_tiles(p.nI) * sbo::kTileFloats,
@@ -1061,95 +735,6 @@ sbo_status refresh_begin(sbo_ctx *ctx, const RefreshPlan &p) {
     return SBO_OK;
 }
 
-// An append of rows n_old..n-1 to an unchanged leading factor: with the f64
-// inverse of the leading block kept from the last refresh, only the new rows
-// of L^-1 are computed,
-//     [L11  0 ]^-1   [ L11^-1                  0     ]
-//     [L21 L22]    = [ -L22^-1 L21 L11^-1   L22^-1 ]
-// (one b x b dtrtri and two dtrmm, O(b n^2) instead of O(n^3)).
-sbo_status inverse_incremental(sbo_ctx *ctx, const RefreshPlan &p) {
-    const int64_t n = p.n, ld = p.ld, n_old = p.n_old, b = n - n_old;
-    float *L = ctx->L.as<float>();
-    double *Li = ctx->Linv.as<double>();
-    const double one = 1.0, minus_one = -1.0;
-    double *T = Li + n_old;                      // rows n_old.., columns 0..n_old-1
-    double *L22i = Li + n_old + n_old * ld;      // rows n_old.., columns n_old..
-    SBO_HIP(sbo::launch_widen(ctx->stream, L + n_old, ld, b, n_old, false, T, ld));
-    SBO_HIP(sbo::launch_widen(ctx->stream, L + n_old + n_old * ld, ld, b, b, true, L22i, ld));
-    SBO_BLAS(rocsolver_dtrtri(ctx->blas, rocblas_fill_lower, rocblas_diagonal_non_unit, (rocblas_int)b, L22i,
-                              (rocblas_int)ld, ctx->info.as<rocblas_int>()));
-    SBO_BLAS(rocblas_set_pointer_mode(ctx->blas, rocblas_pointer_mode_host));
-    // S = L21 L11^-1, then T = -L22^-1 S, as two dgemms on the
-    // triangles with their zero halves (one f64 MFMA GEMM each:
-    // rocBLAS's in-place dtrmm ran as ~200 small launches per append).
-    // The strictly upper part of L^-1 is zero: widen() writes it for
-    // the initial inverse and for L22^-1, rocSOLVER dtrtri leaves it,
-    // and the columns an append adds are zeroed above the new rows here.
-    SBO_HIP(hipMemset2DAsync(Li + n_old * ld, sizeof(double) * (size_t)ld, 0, sizeof(double) * (size_t)n_old,
-                             (size_t)b, ctx->stream));
-    // (sized by the capacity, so that the appends of a streaming loop do not regrow it)
-    SBO_HIP(ctx->scratch.reserve(sizeof(double) * (size_t)sbo::round_up(b, 256) * (size_t)ld));
-    double *S = ctx->scratch.as<double>();
-    const double zero = 0.0;
-    if (b <= kAppendInvRows) {
-        // row by row: S[r,:]^T = Li^T T[r,:]^T, one dtrmv over the
-        // lower triangle (the dgemm read the whole n_old^2 square)
-        for (int64_t r = 0; r < b; ++r) {
-            SBO_BLAS(rocblas_dcopy(ctx->blas, (rocblas_int)n_old, T + r, (rocblas_int)ld, S + r, (rocblas_int)b));
-            SBO_BLAS(rocblas_dtrmv(ctx->blas, rocblas_fill_lower, rocblas_operation_transpose,
-                                   rocblas_diagonal_non_unit, (rocblas_int)n_old, Li, (rocblas_int)ld, S + r,
-                                   (rocblas_int)b));
-        }
-    } else {
-        SBO_BLAS(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_none, (rocblas_int)b,
-                               (rocblas_int)n_old, (rocblas_int)n_old, &one, T, (rocblas_int)ld, Li,
-                               (rocblas_int)ld, &zero, S, (rocblas_int)b));
-    }
-    SBO_BLAS(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_none, (rocblas_int)b,
-                           (rocblas_int)n_old, (rocblas_int)b, &minus_one, L22i, (rocblas_int)ld, S,
-                           (rocblas_int)b, &zero, T, (rocblas_int)ld));
-    return SBO_OK;
-}
-
-// The inverse whose first half ran beside the Cholesky (blocked_potrf):
-// A^-1 and S = B A^-1 are done: widen the right columns (their rows 0..h-1
-// zero), then C^-1 and X21 = -C^-1 S
-sbo_status inverse_finish_half(sbo_ctx *ctx, const RefreshPlan &p) {
-    const int64_t n = p.n, ld = p.ld, h = inverse_split(n, ctx->inv_base);
-    float *L = ctx->L.as<float>();
-    double *Li = ctx->Linv.as<double>();
-    SBO_HIP(sbo::launch_widen(ctx->stream, L + h + h * ld, ld, n - h, n - h, true, Li + h + h * ld, ld));
-    SBO_HIP(hipMemset2DAsync(Li + h * ld, sizeof(double) * (size_t)ld, 0, sizeof(double) * (size_t)h,
-                             (size_t)(n - h), ctx->stream));
-    int slot = p.half_slots;
-    return inverse_second_half(ctx, ctx->blas, Li, n, ld, ctx->scratch.as<double>(),
-                               ctx->scratch.as<double>() + h * (n - h), slot, InvMode{});
-}
-
-// The library's own recursion (SBO_OPT_INVERSE 1): the factor widened unless
-// blocked_potrf did it, the base cases up front (SBO_OPT_INV_LEAVES), then
-// the two halves side by side.
-sbo_status inverse_recursive(sbo_ctx *ctx, const RefreshPlan &p) {
-    const int64_t n = p.n, ld = p.ld;
-    double *Li = ctx->Linv.as<double>();
-    if (!p.widened) SBO_HIP(sbo::launch_widen(ctx->stream, ctx->L.as<float>(), ld, n, n, true, Li, ld));
-    SBO_HIP(ctx->scratch.reserve(
-        sizeof(double) * (size_t)std::max({inverse_scratch_par(n, ctx->inv_base), leaf_scratch(ctx, n), (int64_t)1})));
-    if (ctx->inv_batched)
-        if (sbo_status st = inverse_leaves(ctx, ctx->blas, Li, n, ld, ctx->scratch.as<double>()); st != SBO_OK)
-            return st;
-    return inverse_lower_f64_par(ctx, Li, n, ld, ctx->scratch.as<double>(), InvMode{p.digits, ctx->inv_batched});
-}
-
-// rocSOLVER's dtrtri on the widened factor (SBO_OPT_INVERSE 0)
-sbo_status inverse_rocsolver(sbo_ctx *ctx, const RefreshPlan &p) {
-    double *Li = ctx->Linv.as<double>();
-    SBO_HIP(sbo::launch_widen(ctx->stream, ctx->L.as<float>(), p.ld, p.n, p.n, true, Li, p.ld));
-    SBO_BLAS(rocsolver_dtrtri(ctx->blas, rocblas_fill_lower, rocblas_diagonal_non_unit, (rocblas_int)p.n, Li,
-                              (rocblas_int)p.ld, ctx->info.as<rocblas_int>()));
-    return SBO_OK;
-}
-
 // L^-1 (lower, non-unit) in f64: widen L and invert (f64 MFMA), then round
 // sf2 * L^-1 to f32 once while packing -- the f32 strtri path adds its own
 // inversion error on top of the f32 representation error
@@ -1157,12 +742,13 @@ sbo_status inverse_rocsolver(sbo_ctx *ctx, const RefreshPlan &p) {
 sbo_status refresh_inverse(sbo_ctx *ctx, const RefreshPlan &p) {
     sbo_status st;
     if (p.incr) {
-        st = inverse_incremental(ctx, p);
+        st = inverse_incremental(ctx, p.n, p.ld, p.n_old);
+    } else if (!p.inv.nodes.empty()) {
+        if (sbo_status sr = inverse_reserve(ctx, p.inv)) return sr;
+        st = p.half_done ? inverse_finish_half(ctx, p.inv) : inverse_full(ctx, p.inv, p.widened);
     } else {
         SBO_HIP(ctx->Linv.reserve(sizeof(double) * (size_t)p.ld * (size_t)p.ld));
-        st = p.half_done ? inverse_finish_half(ctx, p)
-             : ctx->inverse_rec ? inverse_recursive(ctx, p)
-                                : inverse_rocsolver(ctx, p);
+        st = inverse_rocsolver(ctx, p.n, p.ld);
     }
     if (st != SBO_OK) return st;
     ctx->linv_n = p.n;
@@ -1391,7 +977,7 @@ sbo_status refresh_read_info(sbo_ctx *ctx, const RefreshPlan &p) {
     SBO_HIP(ctx->kbox.reserve(sizeof(float4) * (size_t)(p.npad / sbo::kBK)));
     SBO_HIP(sbo::launch_tile_boxes(ctx->stream, ctx->x.as<float>(), ctx->y.as<float>(), p.n, p.npad,
                                    ctx->kbox.as<float4>()));
-    const int64_t nslots = info_slots(p.n);
+    const int64_t nslots = p.info_slots;
     std::vector<rocblas_int> hinfos((size_t)nslots);
     SBO_HIP(hipMemcpyAsync(hinfos.data(), ctx->info.as<rocblas_int>(), sizeof(rocblas_int) * (size_t)nslots,
                            hipMemcpyDeviceToHost, ctx->stream));
@@ -1539,7 +1125,7 @@ void precise_budget(sbo_ctx *ctx) {
 constexpr double kPreciseTol = 5e-6;
 constexpr int kProbeRefBits = 24;
 sbo_status probe_precision(sbo_ctx *ctx) {
-    const bool avail = ctx->inverse_bits == 64 && ctx->has_factor && ctx->linv_n == ctx->n;
+    const bool avail = ctx->has_factor && inverse_current(ctx, ctx->n);
     if (!avail || ctx->precision_opt == 0) {
         ctx->precise = false;
         if (!avail) ctx->probe_n = 0;
@@ -1646,7 +1232,8 @@ struct CholPlan {
     int chain;           // SBO_OPT_CHOL_DIAG: the version of the chain's two kernels
     bool own_trsm;       // the panel solve by chol_trsm_kernel (SBO_OPT_CHOLESKY 1), else rocBLAS strsm (2)
     bool early;          // the inverse's first half runs beside the last steps (SBO_OPT_INV_OVERLAP) ...
-    int64_t h_inv;       // ... once the factor's left h_inv columns are final (-1: never)
+    int64_t h_inv;       // ... once the factor's left h_inv columns are final (-1: never) ...
+    sbo::InvPlan inv;    // ... by this plan (the refresh finishes it: FactorHandover)
     bool widen;          // the f64 copy of the factor is written panel by panel into Linv
     rocblas_int *info;   // rocSOLVER-style info: slot 0 the leading minor, with `early` the first half's after it
     int64_t info_slots;
@@ -1708,9 +1295,10 @@ sbo_status chol_plan(sbo_ctx *ctx, int64_t n, int64_t ld, bool early_inv, CholPl
     // the Cholesky with SBO_OPT_INV_OVERLAP = R > 0; otherwise the factor is
     // widened for it on the way.
     p.early = early_inv && ctx->inv_overlap > 0 && n > ctx->inv_base;
-    p.h_inv = p.early ? inverse_split(n, ctx->inv_base) : -1;
+    if (p.early) p.inv = sbo::plan_inverse(inv_config_early(ctx), n, ld);
+    p.h_inv = p.early ? p.inv.nodes[0].h : -1;
     p.widen = early_inv && !p.early;
-    p.info_slots = p.early ? info_slots(n) : 1;
+    p.info_slots = p.early ? p.inv.info_total : 1;
     SBO_HIP(ctx->info.reserve(sizeof(rocblas_int) * (size_t)p.info_slots));
     p.info = ctx->info.as<rocblas_int>();
     return SBO_OK;
@@ -1772,8 +1360,7 @@ sbo_status chol_streams(sbo_ctx *ctx, const CholPlan &p) {
 // Every buffer the early half touches, sized before it starts (a reserve that
 // reallocates later would free memory in use), and its info slots cleared.
 sbo_status chol_reserve_early(sbo_ctx *ctx, const CholPlan &p) {
-    SBO_HIP(ctx->Linv.reserve(sizeof(double) * (size_t)p.ld * (size_t)p.ld));
-    SBO_HIP(ctx->scratch.reserve(sizeof(double) * (size_t)std::max<int64_t>(inverse_scratch(p.n, ctx->inv_base), 1)));
+    if (sbo_status st = inverse_reserve(ctx, p.inv)) return st;
     SBO_HIP(hipMemsetAsync(p.info, 0, sizeof(rocblas_int) * (size_t)p.info_slots, ctx->stream));
     return SBO_OK;
 }
@@ -1851,16 +1438,13 @@ struct CholJoin {
 // (widen them, A^-1, S = B A^-1: half its flops) beside the Cholesky's last
 // steps, which leave most CUs idle.  refresh_operand finishes the inverse.
 sbo_status chol_early_half(sbo_ctx *ctx, const CholPlan &p, const float *L, CholJoin &join, FactorHandover &ho) {
-    double *Li = ctx->Linv.as<double>(), *S = ctx->scratch.as<double>();
+    double *Li = ctx->Linv.as<double>();
     CHOL_HIP(hipEventRecord(ctx->ev_half, ctx->stream));
     CHOL_HIP(hipStreamWaitEvent(ctx->inv_stream, ctx->ev_half, 0));
     CHOL_HIP(sbo::launch_widen(ctx->inv_stream, L, p.ld, p.n, p.h_inv, true, Li, p.ld));
     join.early_started = true;
-    int slot = 0;
-    if (sbo_status st = inverse_first_half(ctx, ctx->blas_inv, Li, p.n, p.ld, S, S + p.h_inv * (p.n - p.h_inv), slot,
-                                           InvMode{}))
-        return st;
-    ho.half_slots = slot;
+    if (sbo_status st = inverse_early_half(ctx, p.inv)) return st;
+    ho.half = p.inv;
     CHOL_HIP(hipEventRecord(ctx->ev_inv, ctx->inv_stream));
     return SBO_OK;
 }
@@ -2122,7 +1706,7 @@ void diag_skip_overrides(sbo::SkipPlan &s) {
 // before the queries are looked at.
 sbo_status tick_plan(sbo_ctx *ctx, const TickRequest &rq, TickPlan &p) {
     const Sweep sweep = rq.sweep != Sweep::kCtx ? rq.sweep : ctx->precise ? Sweep::kPrecise : Sweep::kFast;
-    SBO_CHECK(sweep == Sweep::kFast || (ctx->has_factor && ctx->linv_n == ctx->n && ctx->inverse_bits == 64),
+    SBO_CHECK(sweep == Sweep::kFast || (ctx->has_factor && inverse_current(ctx, ctx->n)),
               SBO_E_STATE, "precise sweep: needs the fit's f64 inverse (not an imported state, INVERSE_BITS 64)");
     const bool full = rq.want == TickWant::kTick;
     p.nI = ctx->npad / sbo::kBM;
@@ -2485,7 +2069,7 @@ sbo_status run_tick_stream(sbo_ctx *ctx, TickRequest rq) {
         reason = SBO_STREAM_REFIT;
     else if (k.m != rq.m)
         reason = SBO_STREAM_QUERIES_CHANGED;
-    else if (!(ctx->has_factor && ctx->inverse_bits == 64 && ctx->linv_n == n && ctx->z_n == n && R >= 0))
+    else if (!(ctx->has_factor && inverse_current(ctx, n) && ctx->z_n == n && R >= 0))
         reason = SBO_STREAM_NO_INVERSE;
     else if (R > ctx->stream_max_rows)
         reason = SBO_STREAM_ROWS_OVER_CAP;
@@ -2778,7 +2362,7 @@ sbo_status append_grow(sbo_ctx *ctx, int64_t n1) {
     SBO_HIP(hipMemcpy2DAsync(nL.as<float>(), sizeof(float) * ncap, ctx->L.as<float>(), sizeof(float) * ctx->cap,
                              sizeof(float) * n0, n0, hipMemcpyDeviceToDevice, ctx->stream));
     SBO_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->linv_n == n0 && ctx->inverse_bits == 64) {  // keep the f64 inverse for the incremental refresh
+    if (inverse_current(ctx, n0)) {  // keep the f64 inverse for the incremental refresh
         DevBuf nLi;
         SBO_HIP(nLi.reserve(sizeof(double) * (size_t)ncap * (size_t)ncap));
         SBO_HIP(hipMemcpy2DAsync(nLi.as<double>(), sizeof(double) * ncap, ctx->Linv.as<double>(),
@@ -2816,7 +2400,7 @@ sbo_status append_fill(sbo_ctx *ctx, int64_t n0, int64_t b) {
 sbo_status append_panel(sbo_ctx *ctx, int64_t n0, int64_t b) {
     const int64_t ld = ctx->cap;
     float *L21 = append_L21(ctx, n0);
-    const bool inv_kept = ctx->inverse_bits == 64 && ctx->linv_n == n0;
+    const bool inv_kept = inverse_current(ctx, n0);
     SBO_BLAS(rocblas_set_pointer_mode(ctx->blas, rocblas_pointer_mode_host));
     if (inv_kept && b <= kAppendInvRows) {
         // a few points (the node's one per change): L21 row by row from the
@@ -3107,7 +2691,7 @@ static sbo_status evidence_run(sbo_ctx *ctx, sbo_evidence_info *out, double *loo
     SBO_CHECK(out->struct_size >= sizeof(uint32_t), SBO_E_INVAL, "sbo_evidence: struct_size not set");
     const int64_t n = ctx->n;
     SBO_CHECK(ctx->fitted && n > 0, SBO_E_STATE, "sbo_evidence: call sbo_fit first");
-    SBO_CHECK(ctx->has_factor && ctx->inverse_bits == 64 && ctx->linv_n == n && ctx->z_n == n, SBO_E_STATE,
+    SBO_CHECK(ctx->has_factor && inverse_current(ctx, n) && ctx->z_n == n, SBO_E_STATE,
               "sbo_evidence: needs the fit's factor, f64 inverse and z (not an imported state, SBO_OPT_INVERSE_BITS 64)");
     SBO_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
@@ -3737,7 +3321,7 @@ SBO_API sbo_status sbo_set_option(sbo_ctx *ctx, int option, int64_t value) {
             SBO_CHECK(value >= -1 && value <= 1, SBO_E_INVAL, "SBO_OPT_PRECISION must be -1 (auto), 0 or 1");
             if (ctx->fitted) {
                 // takes effect at once: a first auto probe now, or the forced choice
-                const bool avail = ctx->has_factor && ctx->linv_n == ctx->n && ctx->inverse_bits == 64;
+                const bool avail = ctx->has_factor && inverse_current(ctx, ctx->n);
                 SBO_CHECK(value != 1 || avail, SBO_E_STATE,
                           "SBO_OPT_PRECISION 1: needs the fit's f64 inverse (not an imported state)");
                 ctx->precision_opt = (int)value;
@@ -3842,7 +3426,7 @@ SBO_API sbo_status sbo_warmup(sbo_ctx *ctx, int64_t n_cap, int64_t m_cap, sbo_hy
     }
     const int popt = ctx->precision_opt;
     for (int prec = 0; prec <= 1 && st == SBO_OK; ++prec) {
-        if (prec == 1 && !(ctx->inverse_bits == 64 && ctx->linv_n == ctx->n)) break;
+        if (prec == 1 && !inverse_current(ctx, ctx->n)) break;
         ctx->precision_opt = prec;
         if ((st = probe_precision(ctx)) != SBO_OK) break;
         st = sbo_tick(ctx, dq.as<float>(), dq.as<float>() + m, m, 2.0, 0.0, SBO_SCORE_WIDTH, 0, nullptr, nullptr,

@@ -1229,6 +1229,94 @@ def test_recursive_inverse_matches_dtrtri(mapper, n):
     gm.set_option(N.SBO_OPT_INV_LEAVES, 2)
 
 
+@pytest.mark.parametrize("n", [1025, 2049, 3073])
+def test_inverse_tree_edges(mapper, n):
+    """The recursion's tree at its edges, at base 1024 so that small n has depth:
+    n = 1025 a one-column lower block at the top, 2049 two levels with a
+    one-column block, 3073 a split lower-right block.  Base cases one by one,
+    batched and by doubling (below four full leaves the batch stays rocSOLVER's), 1
+    and 64 panels per product, dgemm products: every mode equals sf2 * inv(L) of
+    the device factor, leaves the strict upper part zero, and agrees with the
+    others to f64 rounding."""
+    from scipy.linalg import solve_triangular
+    wl = synthetic(n, 24, 20, seed=n + 7)
+    gm = TerrainMapper(0, wl.hyper, ctx=mapper.ctx)
+    try:
+        gm.set_option(N.SBO_OPT_INV_BASE, 1024)
+        gm.set_option(N.SBO_OPT_INV_OZ, 0)
+        ref, first = None, None
+        for leaves in (0, 1, 2):
+            for panels in (1, 64):
+                gm.set_option(N.SBO_OPT_INV_LEAVES, leaves)
+                gm.set_option(N.SBO_OPT_INV_PANELS, panels)
+                gm.fit(wl.x, wl.y, wl.obs)
+                A = np.zeros((n, n), np.float32)
+                gm.ctx.check(N.lib().sbo_get_inverse(gm.ctx.handle, A.ctypes.data))
+                if ref is None:   # the factor does not depend on the inverse's options
+                    L, _ = gm.factor()
+                    ref = wl.hyper.sf2 * solve_triangular(L.astype(np.float64), np.eye(n), lower=True)
+                err = np.abs(np.tril(A) - ref).max() / np.abs(ref).max()
+                print(f"n={n} leaves={leaves} panels={panels}: max rel err {err:.2e}")
+                assert err < 1e-6, (leaves, panels, err)
+                assert not np.triu(A, 1).any()
+                if first is None:
+                    first = np.tril(A)
+                assert np.abs(np.tril(A) - first).max() <= 2e-6 * np.abs(first).max(), (leaves, panels)
+    finally:
+        gm.set_option(N.SBO_OPT_INV_BASE, 2048)
+        gm.set_option(N.SBO_OPT_INV_OZ, 6)
+        gm.set_option(N.SBO_OPT_INV_LEAVES, 2)
+        gm.set_option(N.SBO_OPT_INV_PANELS, 16)
+
+
+@pytest.mark.parametrize("digits", [6, 5])
+def test_smallest_sliced_inverse(mapper, digits):
+    """The smallest shape that slices: n = 3000 at base 1024 with
+    SBO_OPT_INV_OZ_MIN 2048 splits at h = 2048, m = 952 (no multiple of a tile),
+    and only the top node passes the level test.  The guard (SBO_OPT_INV_CHECK 1
+    runs after sliced inverses only) reports that it ran on an inverse of
+    `digits` digits, so the products were sliced; L^-1 and the posterior hold
+    test_sliced_inverse's bounds."""
+    from scipy.linalg import solve_triangular
+    n = 3000
+    wl = synthetic(n, 24, 20, seed=n + 7)
+    gm = TerrainMapper(0, wl.hyper, ctx=mapper.ctx)
+    try:
+        gm.set_option(N.SBO_OPT_INV_BASE, 1024)
+        gm.set_option(N.SBO_OPT_INV_OZ_MIN, 2048)
+        gm.set_option(N.SBO_OPT_INV_OZ, 0)
+        gm.fit(wl.x, wl.y, wl.obs)
+        assert gm.inverse_check()["ran"] == 0
+        mu_ref, _ = gm.predict(wl.qx, wl.qy)
+        gm.set_option(N.SBO_OPT_INV_CHECK, 1)
+        gm.set_option(N.SBO_OPT_INV_OZ, digits)
+        gm.fit(wl.x, wl.y, wl.obs)
+        chk = gm.inverse_check()
+        print(f"n={n} digits={digits}: guard {chk}")
+        assert chk["ran"] == 1 and chk["digits"] == digits
+        L, _ = gm.factor()
+        A = np.zeros((n, n), np.float32)
+        gm.ctx.check(N.lib().sbo_get_inverse(gm.ctx.handle, A.ctypes.data))
+        ref = wl.hyper.sf2 * solve_triangular(L.astype(np.float64), np.eye(n), lower=True)
+        err = np.abs(np.tril(A) - ref).max() / np.abs(ref).max()
+        print(f"n={n} digits={digits}: L^-1 max rel err {err:.2e}")
+        assert err < 1e-6
+        assert not np.triu(A, 1).any()
+        gm.set_option(N.SBO_OPT_PRECISION, 0)
+        mu, sd = gm.predict(wl.qx, wl.qy)
+        omu, ovar = oracle_given_factor(gm, wl)
+        emu, evar = nrel(mu, omu), nrel(sd.astype(np.float64) ** 2, ovar)
+        print(f"  mu {emu:.2e} var {evar:.2e}")
+        assert emu < REL_TOL and evar < REL_TOL
+        assert nrel(mu, mu_ref.astype(np.float64)) < 1e-6
+    finally:
+        gm.set_option(N.SBO_OPT_INV_BASE, 2048)
+        gm.set_option(N.SBO_OPT_INV_OZ_MIN, 0)
+        gm.set_option(N.SBO_OPT_INV_OZ, 6)
+        gm.set_option(N.SBO_OPT_INV_CHECK, 1)
+        gm.set_option(N.SBO_OPT_PRECISION, -1)
+
+
 @pytest.mark.parametrize("n,box,digits", [(4100, False, 6), (5000, False, 6), (5000, False, 5), (6000, True, 6),
                                           (9000, True, 6)])
 def test_sliced_inverse(mapper, n, box, digits):
@@ -1335,6 +1423,51 @@ def test_inverse_overlap_is_bitwise(mapper, n):
     gm.set_option(N.SBO_OPT_CHOLESKY, 1)
     gm.set_option(N.SBO_OPT_INV_OVERLAP, 0)
     gm.set_option(N.SBO_OPT_INV_OZ, 6)
+
+
+def test_overlap_finishes_a_split_block(mapper):
+    """The early half's other half with a lower-right block that is itself
+    split: n = 3073 at base 1024 splits at h = 2048, m = 1025, so finishing the
+    inverse recurses into C (1024 + 1) with its info slots after the early
+    half's two.  Inverse, alpha and posterior bitwise the serial fit's; a
+    singular K with the overlap on is NOT_SPD and the refit after it clean."""
+    n = 3073
+    wl = synthetic(n, 24, 20, seed=n + 11)
+    try:
+        mapper.set_option(N.SBO_OPT_INV_BASE, 1024)
+        mapper.set_option(N.SBO_OPT_INV_OZ, 0)
+        got = {}
+        for ov in (0, 32, 0):
+            gm = TerrainMapper(0, wl.hyper, ctx=mapper.ctx)
+            gm.set_option(N.SBO_OPT_INV_OVERLAP, ov)
+            gm.fit(wl.x, wl.y, wl.obs)
+            A = np.zeros((n, n), np.float32)
+            gm.ctx.check(N.lib().sbo_get_inverse(gm.ctx.handle, A.ctypes.data))
+            L, alpha = gm.factor()
+            mu, sd = gm.predict(wl.qx, wl.qy)
+            if ov in got:
+                assert np.array_equal(got[ov][0], A)
+            got[ov] = (A, alpha, mu, sd)
+        for a, b in zip(got[0], got[32]):
+            assert np.array_equal(a, b)
+        assert not np.triu(got[32][0], 1).any()
+        omu, ovar = oracle_given_factor(gm, wl)
+        assert nrel(mu, omu) < REL_TOL and nrel(sd.astype(np.float64) ** 2, ovar) < REL_TOL
+        # a singular K (duplicated point, no noise) with the overlap on, then a clean refit
+        x, y = f32(wl.x).copy(), f32(wl.y).copy()
+        x[n - 7], y[n - 7] = x[5], y[5]
+        bad = TerrainMapper(0, Hyper(noise_level=0.0), ctx=mapper.ctx)
+        bad.set_option(N.SBO_OPT_INV_OVERLAP, 32)
+        with pytest.raises(N.NotSPDError):
+            bad.fit(x, y, wl.obs)
+        gm = TerrainMapper(0, wl.hyper, ctx=mapper.ctx)
+        gm.fit(wl.x, wl.y, wl.obs)
+        mu2, sd2 = gm.predict(wl.qx, wl.qy)
+        assert np.array_equal(mu2, got[0][2]) and np.array_equal(sd2, got[0][3])
+    finally:
+        mapper.set_option(N.SBO_OPT_INV_OVERLAP, 0)
+        mapper.set_option(N.SBO_OPT_INV_BASE, 2048)
+        mapper.set_option(N.SBO_OPT_INV_OZ, 6)
 
 
 # ------------------------------------------------------ full-size properties

@@ -3,7 +3,8 @@ in its own process (SBO_LIB), writes the fit's tile bounds, mu/sd/lo/hi/S and th
 workloads, and the outputs are compared element by element.
 
   python tools/compare_libs.py LIB_A LIB_B [--configs C4 C2 box]
-  python tools/compare_libs.py LIB_A LIB_B --factor-matrix   (fits under the Cholesky's options, appends)"""
+  python tools/compare_libs.py LIB_A LIB_B --factor-matrix   (fits under the Cholesky's options, appends)
+  python tools/compare_libs.py LIB_A LIB_B --inverse-matrix  (fits under the f64 inverse's options, appends)"""
 import argparse
 import os
 import subprocess
@@ -108,6 +109,60 @@ np.savez({path!r}, **out)
 print("ok", N.LIB_PATH, len(out), "arrays")
 '''
 
+# --inverse-matrix: the f64 inverse's options at sizes that give its tree every shape (base 1024 and 2048: a
+# one-column block, two levels, the smallest sliced top, a split lower-right block, a sliced second level),
+# then the append paths.  Per case L, alpha, the f32 view of the inverse, mu and sd, as --factor-matrix.
+INVERSE_CHILD = r'''
+import hashlib, sys, numpy as np
+sys.path.insert(0, {root!r})
+from safe_bayesian_optimization_amd import TerrainMapper, synthetic
+from safe_bayesian_optimization_amd import _native as N
+out = {{}}
+DEFAULTS = ((N.SBO_OPT_INVERSE, 1), (N.SBO_OPT_INVERSE_BITS, 64), (N.SBO_OPT_INV_LEAVES, 2), (N.SBO_OPT_INV_PANELS, 16),
+            (N.SBO_OPT_INV_OZ, 6), (N.SBO_OPT_INV_OZ_MIN, 0), (N.SBO_OPT_INV_OVERLAP, 0), (N.SBO_OPT_INV_CHECK, 1))
+CASES = [("default", ()), ("inverse0", ((N.SBO_OPT_INVERSE, 0),)),
+         ("leaves0", ((N.SBO_OPT_INV_LEAVES, 0),)), ("leaves1", ((N.SBO_OPT_INV_LEAVES, 1),)),
+         ("leaves2", ((N.SBO_OPT_INV_LEAVES, 2),)), ("panels4", ((N.SBO_OPT_INV_PANELS, 4),)),
+         ("oz0", ((N.SBO_OPT_INV_OZ_MIN, 2048), (N.SBO_OPT_INV_OZ, 0))),
+         ("oz5", ((N.SBO_OPT_INV_OZ_MIN, 2048), (N.SBO_OPT_INV_OZ, 5))),
+         ("oz6", ((N.SBO_OPT_INV_OZ_MIN, 2048), (N.SBO_OPT_INV_OZ, 6))),
+         ("overlap32", ((N.SBO_OPT_INV_OVERLAP, 32),)), ("overlap32_oz0", ((N.SBO_OPT_INV_OVERLAP, 32), (N.SBO_OPT_INV_OZ, 0))),
+         ("check2", ((N.SBO_OPT_INV_CHECK, 2),)), ("bits32", ((N.SBO_OPT_INVERSE_BITS, 32),)), ("default_again", ())]
+gm = None
+def record(name, wl):
+    L, alpha = gm.factor()
+    A = np.zeros((gm.n, gm.n), np.float32)
+    gm.ctx.check(N.lib().sbo_get_inverse(gm.ctx.handle, A.ctypes.data))
+    mu, sd = gm.predict(wl.qx, wl.qy)
+    for k, v in (("L", L), ("alpha", alpha), ("inv", A), ("mu", mu), ("sd", sd)):
+        v = np.ascontiguousarray(v)     # (arrays past 1 MiB: their SHA-256)
+        out[name + "_" + k] = v if v.nbytes <= 1 << 20 else np.frombuffer(hashlib.sha256(v).digest(), np.uint8)
+for n in (1025, 2049, 3000, 3073, 4100, 9000):
+    wl = synthetic(n, 24, 20, seed=n + 3)
+    for base in (1024, 2048):
+        gm = TerrainMapper(0, wl.hyper)      # one context per tree: every case after the first runs on used streams
+        gm.set_option(N.SBO_OPT_INV_BASE, base)
+        for name, options in CASES:
+            for k, v in DEFAULTS + tuple(options):
+                gm.set_option(k, v)
+            gm.fit(wl.x, wl.y, wl.obs)
+            record(f"n{{n}}_base{{base}}_{{name}}", wl)
+        gm.close()
+wl = synthetic(6600, 24, 20, seed=17)
+for base in (1024, 2048):
+    gm = TerrainMapper(0, wl.hyper)
+    gm.set_option(N.SBO_OPT_INV_BASE, base)
+    gm.fit(wl.x[:4352], wl.y[:4352], wl.obs[:4352])
+    a = 4352
+    for b in (1, 300, 1900):
+        gm.append(wl.x[a:a + b], wl.y[a:a + b], wl.obs[a:a + b])
+        a += b
+        record(f"append{{b}}_base{{base}}", wl)
+    gm.close()
+np.savez({path!r}, **out)
+print("ok", N.LIB_PATH, len(out), "arrays")
+'''
+
 
 def run(lib, configs, path, child=CHILD):
     env = dict(os.environ, SBO_LIB=os.path.abspath(lib))
@@ -126,8 +181,11 @@ def main():
     p.add_argument("--configs", nargs="+", default=["C4", "C2", "box"])
     p.add_argument("--factor-matrix", action="store_true",
                    help="the factorization's option matrix and the append paths instead of the ticks")
+    p.add_argument("--inverse-matrix", action="store_true",
+                   help="the f64 inverse's option matrix and the append paths instead of the ticks")
     a = p.parse_args()
-    child = FACTOR_CHILD if a.factor_matrix else CHILD
+    child = FACTOR_CHILD if a.factor_matrix else INVERSE_CHILD if a.inverse_matrix else CHILD
+    a.factor_matrix |= a.inverse_matrix      # (reported alike)
     A = run(a.lib_a, a.configs, os.environ.get("CMP_OUT", "/tmp") + "/cmp_a.npz", child)
     B = run(a.lib_b, a.configs, os.environ.get("CMP_OUT", "/tmp") + "/cmp_b.npz", child)
     same = sorted(A) == sorted(B)
