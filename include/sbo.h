@@ -284,6 +284,77 @@ SBO_API sbo_status sbo_debug_evidence_pairs(const float *boxes /* 4 T: x0,x1,y0,
         const double *alpha_l1, const double *sqrtc_l1, int64_t T, sbo_hyper hyper,
         double budget, uint8_t *drop /* T*T, row-major, symmetric */, double *bound);
 
+/* What-if posterior: for p candidate points c_j, the posterior cross-covariance
+ * Cov(f(q), f(c_j)) with every query q of the kept posterior, and each
+ * candidate's expander count -- the currently unsafe queries whose lower bound
+ * would clear f_min after an optimistic observation at c_j (SafeOpt's
+ * GP-defined expanders, Berkenkamp et al. 2016; the reference node ranks its
+ * frontier by distance and width instead, node.cpp:499-550).  Nothing is
+ * appended.  Read off what a streaming tick leaves on the device: the f64
+ * inverse X = L^-1, z = X (y - m0), and sbo_tick_stream's kept f64 posterior
+ * (mu, var).  With s = noise_level + jitter:
+ *   k_j = k(train, c_j),  u_j = X k_j,  w_j = X^T u_j  (= K^-1 k_j)
+ *   mu_c = m0 + u_j . z,  var_c = sf2 - |u_j|^2,  d_j = var_c + s
+ *   cov(q, c_j) = k(q, c_j) - k*(q) . w_j
+ * and, conditioning on y_j = mu_c + beta sd_c, sd_c = sqrt(max(var_c, 0)):
+ *   mu'(q)  = mu(q) + cov(q, c_j) beta sd_c / d_j
+ *   var'(q) = var(q) - cov(q, c_j)^2 / d_j
+ *   lo'(q)  = mu'(q) - beta sqrt(max(var'(q), 0))                  (all f64)
+ *   gain_j  = #{ q : not safe(q) and lo'(q) > f_min }
+ * safe(q) is recomputed from the kept state exactly as sbo_tick_stream forms
+ * its `safe` output (for the same beta and f_min).  That is the posterior of a
+ * refit with (c_j, y_j) added, without the refit.
+ *
+ * cx, cy: p candidates, 1 <= p <= 1024.  gain: p counts.  cand_mu, cand_var:
+ * p doubles each, or NULL.  cov, lo_new: p x m row-major in the caller's query
+ * order (m = the kept posterior's), or NULL.  Host pointers; device pointers
+ * (every array) with SBO_DEVICE_PTRS.  Synchronous (var_c and |w_j|_1 are read
+ * back for the cutoff; SBO_ASYNC is ignored).  info may be NULL; the caller
+ * sets info->struct_size to sizeof(sbo_whatif_info) and the library writes no
+ * more than that many bytes.
+ *
+ * The sweep skips a (128-query block, 64-column k-tile) pair when the two
+ * bounding boxes put every K* entry below 2^-L, which moves cov(q, c_j) by at
+ * most e_j = sf2 2^-L |w_j|_1.  SBO_OPT_TILE_SKIP 0: dense; a fixed L spends
+ * its own bound; L >= 150 drops only exact zeros (bitwise the dense result);
+ * -1 (auto): the smallest L in [16, 149] for which every candidate keeps
+ *   mean:     beta sd_c e_j / d_j                                  <= budget_mean
+ *   variance: (2 sqrt(sf2 max(var_c, 0)) e_j + e_j^2) / d_j        <= budget_var
+ * (the budgets sbo_get_stream reports; nothing accumulates, so a call may use
+ * all of them), else 150.  err_cov = max_j e_j.  All floating-point sums run in
+ * a fixed order and the counts are integer sums: two calls agree bitwise.
+ *
+ * SBO_E_STATE without a kept posterior, when the kept posterior has not seen
+ * every fitted row (an append without a following sbo_tick_stream, another fit
+ * epoch), and without a current f64 inverse and z (SBO_OPT_INVERSE_BITS 32, an
+ * imported state).  SBO_E_INVAL for p <= 0, p > 1024 or a NULL gain.  Alters
+ * no fitted or kept state; its workspace is freed by sbo_trim. */
+typedef struct sbo_whatif_info {
+    uint32_t struct_size;      /* caller sets; no more than this many bytes are written */
+    int32_t  cutoff_log2;      /* L (0: dense) */
+    int64_t  p, m, n;
+    int64_t  tiles_total, tiles_kept;   /* (query block, k-tile) pairs */
+    double   err_cov;          /* rigorous bound on |cov error| from the cutoff (0 when dense) */
+    int64_t  best;             /* argmax gain, lowest j on ties */
+    int64_t  best_gain;
+    double   ms;               /* device time of the call's kernels */
+} sbo_whatif_info;
+SBO_API sbo_status sbo_whatif(sbo_ctx *ctx, const float *cx, const float *cy, int64_t p,
+                              double beta, double f_min,
+                              int64_t *gain,                        /* p */
+                              double *cand_mu, double *cand_var,    /* p each, may be NULL */
+                              double *cov, double *lo_new,          /* p x m row-major, caller's query order, may be NULL */
+                              sbo_whatif_info *info, uint32_t flags);
+
+/* Test accessor: sbo_whatif's auto cutoff alone, on the host (no context, no
+ * device).  w_l1 / cand_var: per candidate |w_j|_1 / var_c; s = noise_level +
+ * jitter.  *cutoff_log2 = the smallest L in [16, 149] within both budgets, 150
+ * if none is, 0 (dense) when a budget is <= 0; *err_cov = max_j sf2 2^-L |w_j|_1
+ * (0 when dense). */
+SBO_API sbo_status sbo_debug_whatif_cutoff(int64_t p, const double *w_l1, const double *cand_var, double s,
+                                           double beta, double sf2, double budget_var, double budget_mean,
+                                           int32_t *cutoff_log2, double *err_cov);
+
 /* Sweep work of each query under the current fit: builds the tick's tile
  * plan for these queries (no sweep) and writes cost[i] = the k-tiles its
  * 128-query block multiplies, summed over row blocks and weighted by their
@@ -680,6 +751,11 @@ SBO_API sbo_status sbo_debug_inverse_plan(int64_t n, int64_t ld, int64_t base, i
  * k-tile pair cutoff may move grad[0] by at most 2^-B n (grad_err_bound says
  * what it spent). */
 #define SBO_OPT_EVIDENCE_BUDGET 32
+/* SBO_OPT_WHATIF_GEMM (0 default, 1): sbo_whatif's two products with the
+ * triangular inverse run as rocBLAS dtrmm (0) or as dgemm over the stored zero
+ * half (1: twice the arithmetic, rocBLAS's general kernels; measured slower at
+ * N = 16384 for p = 16 .. 256, 3.5-4.1 against 2.5-3.5 ms). */
+#define SBO_OPT_WHATIF_GEMM 33
 SBO_API sbo_status sbo_set_option(sbo_ctx *ctx, int option, int64_t value);
 
 /* The last inverse check (SBO_OPT_INV_CHECK) of the current fit, on m = 31
@@ -715,7 +791,7 @@ SBO_API sbo_status sbo_get_inverse_check(const sbo_ctx *ctx, sbo_inv_check *out)
  * calls for speed (the recursive inverse's scratch and the int8-sliced GEMM's
  * packed operands -- about 2.1 GB at N = 16384, 8.5 GB at 32768 -- the inverse
  * check's, the append re-sort's staging copy, sbo_evidence's column norms and
- * work items and the precise sweep's K* table, up to SBO_OPT_TABLE_MB); they
+ * work items, sbo_whatif's candidate weights and the precise sweep's K* table, up to SBO_OPT_TABLE_MB); they
  * are allocated again on the next call that needs them.  The fitted state
  * (factor, inverse, operands) stays, and so does sbo_tick_stream's kept
  * posterior (sbo_stream_reset frees that).  Waits for the context's streams. */

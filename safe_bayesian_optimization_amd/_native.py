@@ -37,6 +37,7 @@ EXPORTS = (
     "sbo_debug_gz_gemm", "sbo_debug_gz_gemm_packed", "sbo_debug_x3_operand", "sbo_debug_plan",
     "sbo_tick_stream", "sbo_get_stream", "sbo_stream_reset", "sbo_debug_stream_state",
     "sbo_evidence", "sbo_debug_evidence_pairs", "sbo_debug_inverse_plan",
+    "sbo_whatif", "sbo_debug_whatif_cutoff",
 )
 # sbo_stream_reason (include/sbo.h, sbo_get_stream)
 STREAM_REASONS = ("FIRST", "UPDATED", "QUERIES_CHANGED", "REFIT", "NO_INVERSE", "ROWS_OVER_CAP", "BUDGET", "RESET")
@@ -81,6 +82,7 @@ SBO_OPT_INV_OZ_ADAPT = 29
 SBO_OPT_STREAM_SHARE = 30
 SBO_OPT_STREAM_MAX_ROWS = 31
 SBO_OPT_EVIDENCE_BUDGET = 32
+SBO_OPT_WHATIF_GEMM = 33
 
 
 class SboError(RuntimeError):
@@ -131,6 +133,13 @@ class sbo_evidence_info(ctypes.Structure):
                 ("grad", ctypes.c_double * 4), ("grad_err_bound", ctypes.c_double), ("grad_budget", ctypes.c_double),
                 ("pairs_total", ctypes.c_int64), ("pairs_kept", ctypes.c_int64), ("loo_log_pred", ctypes.c_double),
                 ("ms", ctypes.c_double)]
+
+
+class sbo_whatif_info(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("cutoff_log2", ctypes.c_int32), ("p", ctypes.c_int64),
+                ("m", ctypes.c_int64), ("n", ctypes.c_int64), ("tiles_total", ctypes.c_int64),
+                ("tiles_kept", ctypes.c_int64), ("err_cov", ctypes.c_double), ("best", ctypes.c_int64),
+                ("best_gain", ctypes.c_int64), ("ms", ctypes.c_double)]
 
 
 _lib = None
@@ -194,6 +203,11 @@ def lib():
     L.sbo_evidence.restype = st
     L.sbo_debug_evidence_pairs.argtypes = [vp, vp, vp, i64, sbo_hyper, dbl, vp, ctypes.POINTER(dbl)]
     L.sbo_debug_evidence_pairs.restype = st
+    L.sbo_whatif.argtypes = [vp, vp, vp, i64, dbl, dbl, vp, vp, vp, vp, vp, ctypes.POINTER(sbo_whatif_info), u32]
+    L.sbo_whatif.restype = st
+    L.sbo_debug_whatif_cutoff.argtypes = [i64, vp, vp, dbl, dbl, dbl, dbl, dbl, ctypes.POINTER(ctypes.c_int32),
+                                          ctypes.POINTER(dbl)]
+    L.sbo_debug_whatif_cutoff.restype = st
     L.sbo_query_cost.argtypes = [vp, vp, vp, i64, vp, u32]
     L.sbo_query_cost.restype = st
     L.sbo_key_combine.argtypes = [sbo_key, sbo_key]

@@ -2817,6 +2817,178 @@ SBO_API sbo_status sbo_debug_evidence_pairs(const float *boxes, const double *al
     return SBO_OK;
 }
 
+// What-if posterior (csrc/whatif.hip): the candidate weights W = K^-1 K_c by
+// two triangular products on the f64 inverse, the candidates' sums, one
+// readback (var_c and |w_j|_1: the host chooses the cutoff from them), then the
+// sweep over the kept posterior.  Reads the fitted and the kept state only;
+// wiws is its own workspace.
+static_assert(sizeof(sbo_whatif_info) == 80, "sbo_whatif_info: the bindings mirror this layout");
+
+static sbo_status whatif_run(sbo_ctx *ctx, const float *cx, const float *cy, int64_t p, double beta, double f_min,
+                             int64_t *gain, double *cand_mu, double *cand_var, double *cov, double *lo_new,
+                             sbo_whatif_info *info, uint32_t flags);
+
+SBO_API sbo_status sbo_whatif(sbo_ctx *ctx, const float *cx, const float *cy, int64_t p, double beta, double f_min,
+                              int64_t *gain, double *cand_mu, double *cand_var, double *cov, double *lo_new,
+                              sbo_whatif_info *info, uint32_t flags) {
+    if (!ctx) return SBO_E_INVAL;
+    try {
+        return whatif_run(ctx, cx, cy, p, beta, f_min, gain, cand_mu, cand_var, cov, lo_new, info, flags);
+    } catch (const std::bad_alloc &) {   // (the host copies of the candidates' sums and counts)
+        ctx->err = "sbo_whatif: host allocation failed";
+        return SBO_E_OOM;
+    }
+}
+
+static sbo_status whatif_run(sbo_ctx *ctx, const float *cx, const float *cy, int64_t p, double beta, double f_min,
+                             int64_t *gain, double *cand_mu, double *cand_var, double *cov, double *lo_new,
+                             sbo_whatif_info *info, uint32_t flags) {
+    SBO_CHECK(cx && cy && gain, SBO_E_INVAL, "sbo_whatif: null candidates or gain");
+    SBO_CHECK(p > 0 && p <= 1024, SBO_E_INVAL, "sbo_whatif: p must be in [1, 1024]");
+    SBO_CHECK(std::isfinite(beta) && !std::isnan(f_min), SBO_E_INVAL, "sbo_whatif: beta/f_min must be finite");
+    SBO_CHECK(!info || info->struct_size >= sizeof(uint32_t), SBO_E_INVAL, "sbo_whatif: struct_size not set");
+    const sbo::StreamKeep &k = ctx->keep;
+    const int64_t n = ctx->n;
+    SBO_CHECK(ctx->fitted && n > 0, SBO_E_STATE, "sbo_whatif: call sbo_fit first");
+    SBO_CHECK(k.valid, SBO_E_STATE, "sbo_whatif: no kept posterior (call sbo_tick_stream first)");
+    SBO_CHECK(k.epoch == ctx->fit_epoch && k.n_map == n, SBO_E_STATE,
+              "sbo_whatif: the kept posterior has not seen every fitted row (call sbo_tick_stream again)");
+    SBO_CHECK(ctx->has_factor && inverse_current(ctx, n) && ctx->z_n == n, SBO_E_STATE,
+              "sbo_whatif: needs the fit's f64 inverse and z (not an imported state, SBO_OPT_INVERSE_BITS 64)");
+    SBO_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const int64_t pp = sbo::round_up(p, 16), m = k.m;
+    const bool host = !dev(flags);
+    const size_t mat = (size_t)p * (size_t)m;
+    SBO_HIP(ctx->wiws.reserve(2 * Carve::need((size_t)pp * (size_t)n, 8) + Carve::need(sbo::whatif_part_bytes(pp), 1) +
+                              3 * Carve::need(p, 8) + Carve::need(2 * pp, 8) + Carve::need(p + 1, 8) +
+                              (host ? 2 * Carve::need(p, 4) + (cov ? Carve::need(mat, 8) : 0) +
+                                          (lo_new ? Carve::need(mat, 8) : 0)
+                                    : 0)));
+    Carve cv(ctx->wiws.as<void>());
+    double *Kt = cv.take<double>((size_t)pp * (size_t)n), *Ut = cv.take<double>((size_t)pp * (size_t)n), *Wt = Kt;
+    double *part = cv.take<double>(sbo::whatif_part_bytes(pp) / 8);
+    double *dmu = cv.take<double>(p), *dvar = cv.take<double>(p), *dl1 = cv.take<double>(p);
+    double *dpar = cv.take<double>(2 * pp);
+    unsigned long long *dgain = cv.take<unsigned long long>(p + 1), *dkept = dgain + p;
+    const float *dcx = cx, *dcy = cy;
+    double *dcov = cov, *dlo = lo_new;
+    if (host) {
+        float *sx = cv.take<float>(p), *sy = cv.take<float>(p);
+        SBO_HIP(hipMemcpyAsync(sx, cx, sizeof(float) * p, hipMemcpyHostToDevice, s));
+        SBO_HIP(hipMemcpyAsync(sy, cy, sizeof(float) * p, hipMemcpyHostToDevice, s));
+        dcx = sx;
+        dcy = sy;
+        if (cov) dcov = cv.take<double>(mat);
+        if (lo_new) dlo = cv.take<double>(mat);
+    }
+    hipEvent_t ev[4] = {take_event(ctx), take_event(ctx), take_event(ctx), take_event(ctx)};
+    struct Give {   // the events go back to the pool on every path
+        sbo_ctx *c;
+        hipEvent_t *e;
+        ~Give() {
+            for (int i = 0; i < 4; ++i)
+                if (e[i]) c->ev_pool.push_back(e[i]);
+        }
+    } give{ctx, ev};
+    SBO_CHECK(ev[0] && ev[1] && ev[2] && ev[3], SBO_E_DEVICE, "sbo_whatif: hipEventCreate failed");
+
+    // the weights: K_c^T, U^T = K_c^T X^T, W^T = U^T X (over K_c^T), the candidates' sums
+    const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f, noise = ctx->hyper.noise_level;   // (holds the jitter too)
+    const double *X = ctx->Linv.as<double>();
+    const double one = 1.0, zero = 0.0;
+    SBO_HIP(hipEventRecord(ev[0], s));
+    {
+        Bracket br(ctx, ctx->ev_fill);
+        SBO_HIP(sbo::launch_whatif_fill(s, ctx->x.as<float>(), ctx->y.as<float>(), n, dcx, dcy, p, pp,
+                                        ctx->hyper.length_scale, sf2, Kt));
+        SBO_BLAS(rocblas_set_pointer_mode(ctx->blas, rocblas_pointer_mode_host));
+        if (ctx->whatif_gemm) {   // (the inverse's strict upper half is stored as zeros)
+            SBO_BLAS(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_transpose, (rocblas_int)pp,
+                                   (rocblas_int)n, (rocblas_int)n, &one, Kt, (rocblas_int)pp, X, (rocblas_int)ctx->cap,
+                                   &zero, Ut, (rocblas_int)pp));
+            SBO_BLAS(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_none, (rocblas_int)pp,
+                                   (rocblas_int)n, (rocblas_int)n, &one, Ut, (rocblas_int)pp, X, (rocblas_int)ctx->cap,
+                                   &zero, Wt, (rocblas_int)pp));
+        } else {
+            SBO_BLAS(rocblas_dtrmm(ctx->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_transpose,
+                                   rocblas_diagonal_non_unit, (rocblas_int)pp, (rocblas_int)n, &one, X,
+                                   (rocblas_int)ctx->cap, Kt, (rocblas_int)pp, Ut, (rocblas_int)pp));
+            SBO_BLAS(rocblas_dtrmm(ctx->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_none,
+                                   rocblas_diagonal_non_unit, (rocblas_int)pp, (rocblas_int)n, &one, X,
+                                   (rocblas_int)ctx->cap, Ut, (rocblas_int)pp, Wt, (rocblas_int)pp));
+        }
+        SBO_HIP(sbo::launch_whatif_stats(s, Ut, Wt, p, pp, n, ctx->zvec.as<double>(), ctx->hyper.prior_mean, sf2, noise,
+                                         beta, part, dmu, dvar, dl1, dpar));
+    }
+    SBO_HIP(hipEventRecord(ev[1], s));
+    std::vector<double> hvar((size_t)p), hl1((size_t)p);
+    SBO_HIP(hipMemcpyAsync(hvar.data(), dvar, sizeof(double) * p, hipMemcpyDeviceToHost, s));
+    SBO_HIP(hipMemcpyAsync(hl1.data(), dl1, sizeof(double) * p, hipMemcpyDeviceToHost, s));
+    SBO_HIP(hipStreamSynchronize(s));
+
+    // the cutoff: the context's fixed one, or the smallest L within the sweep's budgets
+    sbo_whatif_info r{};
+    int L = ctx->skip_log2;
+    if (L < 0) {
+        double bvar = 0.0, bmean = 0.0;
+        stream_budget(ctx, bvar, bmean);
+        sbo::whatif_cutoff(p, hl1.data(), hvar.data(), noise, beta, sf2, bvar, bmean, &L, &r.err_cov);
+    } else {
+        r.err_cov = sbo::whatif_err_cov(L, sf2, *std::max_element(hl1.begin(), hl1.end()));
+    }
+
+    // the sweep
+    SBO_HIP(hipMemsetAsync(dgain, 0, sizeof(unsigned long long) * (size_t)(p + 1), s));
+    SBO_HIP(hipEventRecord(ev[2], s));
+    {
+        Bracket br(ctx, ctx->ev_predict);
+        SBO_HIP(sbo::launch_whatif(s, Wt, pp, p, n, ctx->x.as<float>(), ctx->y.as<float>(), ctx->kbox.as<float4>(),
+                                   k.qbox.as<float4>(), k.qx.as<float>(), k.qy.as<float>(), k.perm.as<int32_t>(), k.ms,
+                                   m, ctx->hyper.length_scale, sf2, L, k.mu64.as<double>(), k.var64.as<double>(), dcx,
+                                   dcy, dpar, beta, f_min, dgain, dcov, dlo, dkept));
+    }
+    SBO_HIP(hipEventRecord(ev[3], s));
+    std::vector<unsigned long long> hgain((size_t)p + 1);
+    SBO_HIP(hipMemcpyAsync(hgain.data(), dgain, sizeof(unsigned long long) * (size_t)(p + 1), hipMemcpyDeviceToHost, s));
+    const hipMemcpyKind out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (!host) SBO_HIP(hipMemcpyAsync(gain, dgain, sizeof(int64_t) * p, out, s));
+    if (cand_mu) SBO_HIP(hipMemcpyAsync(cand_mu, dmu, sizeof(double) * p, out, s));
+    if (cand_var) SBO_HIP(hipMemcpyAsync(cand_var, dvar, sizeof(double) * p, out, s));
+    if (host && cov) SBO_HIP(hipMemcpyAsync(cov, dcov, sizeof(double) * mat, out, s));
+    if (host && lo_new) SBO_HIP(hipMemcpyAsync(lo_new, dlo, sizeof(double) * mat, out, s));
+    SBO_HIP(hipStreamSynchronize(s));
+    r.best = 0;
+    for (int64_t j = 0; j < p; ++j) {
+        if (host) gain[j] = (int64_t)hgain[(size_t)j];
+        if (hgain[(size_t)j] > hgain[(size_t)r.best]) r.best = j;   // (the lowest j on ties)
+    }
+    if (!info) return SBO_OK;
+    r.best_gain = (int64_t)hgain[(size_t)r.best];
+    r.cutoff_log2 = L;
+    r.p = p;
+    r.m = m;
+    r.n = n;
+    r.tiles_total = (k.ms + sbo::kBN - 1) / sbo::kBN * ((n + sbo::kBK - 1) / sbo::kBK);
+    r.tiles_kept = (int64_t)hgain[(size_t)p];
+    float ms1 = 0.0f, ms2 = 0.0f;
+    SBO_HIP(hipEventElapsedTime(&ms1, ev[0], ev[1]));
+    SBO_HIP(hipEventElapsedTime(&ms2, ev[2], ev[3]));
+    r.ms = (double)ms1 + (double)ms2;
+    r.struct_size = (uint32_t)std::min<size_t>(info->struct_size, sizeof(r));
+    memcpy(info, &r, r.struct_size);
+    return SBO_OK;
+}
+
+SBO_API sbo_status sbo_debug_whatif_cutoff(int64_t p, const double *w_l1, const double *cand_var, double s,
+                                           double beta, double sf2, double budget_var, double budget_mean,
+                                           int32_t *cutoff_log2, double *err_cov) {
+    if (p <= 0 || !w_l1 || !cand_var || !cutoff_log2 || !err_cov || !(sf2 > 0.0)) return SBO_E_INVAL;
+    int L = 0;
+    sbo::whatif_cutoff(p, w_l1, cand_var, s, beta, sf2, budget_var, budget_mean, &L, err_cov);
+    *cutoff_log2 = L;
+    return SBO_OK;
+}
 
 SBO_API sbo_status sbo_compute_sets(sbo_ctx *ctx, const float *mu, const float *sd, int64_t m, double beta,
                                     double f_min, double *lo, double *hi, uint8_t *safe, uint32_t flags) {
@@ -3348,6 +3520,10 @@ SBO_API sbo_status sbo_set_option(sbo_ctx *ctx, int option, int64_t value) {
                       "SBO_OPT_EVIDENCE_BUDGET must be 0 (dense) or in [10, 60]");
             ctx->evidence_budget = (int)value;
             return SBO_OK;
+        case SBO_OPT_WHATIF_GEMM:
+            SBO_CHECK(value == 0 || value == 1, SBO_E_INVAL, "SBO_OPT_WHATIF_GEMM must be 0 (dtrmm) or 1 (dgemm)");
+            ctx->whatif_gemm = (int)value;
+            return SBO_OK;
         case SBO_OPT_TILE_SKIP:
             SBO_CHECK(value == -1 || value == 0 || (value >= 16 && value <= 1000), SBO_E_INVAL,
                       "SBO_OPT_TILE_SKIP must be -1 (auto), 0 (dense) or a cutoff exponent in [16, 1000]");
@@ -3377,7 +3553,7 @@ SBO_API sbo_status sbo_trim(sbo_ctx *ctx) {
     if (ctx->inv_stream) SBO_HIP(hipStreamSynchronize(ctx->inv_stream));
     if (ctx->chk_stream) SBO_HIP(hipStreamSynchronize(ctx->chk_stream));
     for (sbo::DevBuf *b : {&ctx->scratch, &ctx->gzws, &ctx->gzws_aux, &ctx->chk, &ctx->restage, &ctx->kzt, &ctx->qcost,
-                           &ctx->awork, &ctx->evws, &ctx->evitems,
+                           &ctx->awork, &ctx->evws, &ctx->evitems, &ctx->wiws,
                            &ctx->cholx3[0], &ctx->cholx3[1]})
         b->release();
     return SBO_OK;

@@ -276,6 +276,10 @@ struct sbo_ctx {
     int evidence_budget = 20;    // SBO_OPT_EVIDENCE_BUDGET: the pair cutoff may move grad[0] by 2^-B n (0: dense)
     sbo::DevBuf evws, evitems;   // column norms, tile sums, order, LOO staging; the work items and their slots
 
+    // what-if posterior (sbo_whatif, whatif.hip): workspace only (sbo_trim frees it)
+    int whatif_gemm = 0;         // SBO_OPT_WHATIF_GEMM: the candidate weights' two products by 0 dtrmm, 1 dgemm over the zero half
+    sbo::DevBuf wiws;            // K_c^T / W^T, U^T, the candidates' sums and factors, counts, host staging
+
     // kernel timing (sbo_profile)
     bool prof = false;
     std::vector<hipEvent_t> ev_pool;               // free events
@@ -529,6 +533,32 @@ hipError_t launch_predict_update(hipStream_t s, const double *Linv, int64_t ld, 
                                  unsigned long long *tiles_kept);
 hipError_t launch_stream_scatter(hipStream_t s, const double *mu64, const double *var64, const int32_t *kperm,
                                  int64_t ms, double *mu_out, double *var_out);
+// What-if posterior (whatif.hip, sbo_whatif), pp = p rounded up to 16.
+// launch_whatif_fill: Kt = K_c^T (pp x n column-major, padding rows zero).
+// launch_whatif_stats: from U^T and W^T (pp x n each) the candidates' mu_c,
+// var_c, |w_j|_1 and the sweep's per-candidate factors cpar (2 pp doubles:
+// beta sd_c / d_j, 1 / d_j, d_j = var_c + noise); part: scratch of
+// whatif_part_bytes(pp).  launch_whatif: the sweep over the kept posterior --
+// gain[j] += candidate j's newly safe positions (zeroed by the caller), cov /
+// lo_new (p x m row-major, the caller's query order; either may be null),
+// *tiles_kept += the (query block, k-tile) pairs multiplied; skip_L as
+// launch_predict_update's.  whatif_cutoff (host): the auto cutoff L and its
+// bound on |cov error| (whatif_err_cov of the largest |w_j|_1).
+size_t whatif_part_bytes(int64_t pp);
+hipError_t launch_whatif_fill(hipStream_t s, const float *x, const float *y, int64_t n, const float *cx,
+                              const float *cy, int64_t p, int64_t pp, double ell, double sf2, double *Kt);
+hipError_t launch_whatif_stats(hipStream_t s, const double *Ut, const double *Wt, int64_t p, int64_t pp, int64_t n,
+                               const double *z, double m0, double sf2, double noise, double beta, double *part,
+                               double *cand_mu, double *cand_var, double *w_l1, double *cpar);
+hipError_t launch_whatif(hipStream_t s, const double *Wt, int64_t pp, int64_t p, int64_t n, const float *x,
+                         const float *y, const float4 *kbox, const float4 *qbox, const float *kqx, const float *kqy,
+                         const int32_t *kperm, int64_t ms, int64_t m, double ell, double sf2, int skip_L,
+                         const double *mu64, const double *var64, const float *cx, const float *cy, const double *cpar,
+                         double beta, double f_min, unsigned long long *gain, double *cov, double *lo_new,
+                         unsigned long long *tiles_kept);
+void whatif_cutoff(int64_t p, const double *w_l1, const double *cand_var, double s, double beta, double sf2,
+                   double budget_var, double budget_mean, int *L_out, double *err_cov);
+double whatif_err_cov(int L, double sf2, double l1max);
 // Precise sweep (predict_f64.hip, SBO_OPT_PRECISION): A = sf2 L^-1 packed in
 // f64 from the fit's f64 inverse for row blocks >= I0 (tile (I, t) at
 // tile_start(I) + t, two 64 KiB stages in MFMA fragment order), and per k-tile

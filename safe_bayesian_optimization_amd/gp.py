@@ -338,6 +338,60 @@ class TerrainMapper:
         self.ctx.check(self._lib.sbo_debug_stream_state(self.ctx.handle, _ptr(mu), _ptr(var), int(m)))
         return mu, var
 
+    # -------------------------------------------------------------- what-if
+    def whatif(self, cx, cy, beta: float, f_min: float, *, cov: bool = False, lo_new: bool = False) -> dict:
+        """What an optimistic observation at each candidate (cx, cy) would do
+        to the kept posterior of the last ``tick_stream`` (sbo_whatif), without
+        appending anything: ``gain`` (int64, p) = the currently unsafe queries
+        whose lower bound would clear ``f_min`` (SafeOpt's expander count),
+        ``cand_mu`` / ``cand_var`` (f64, p), and with ``cov`` / ``lo_new`` the
+        p x m posterior cross-covariance and new lower bounds in the caller's
+        query order; plus the fields of ``sbo_whatif_info`` (``best`` is the
+        argmax of ``gain``, the lowest index on ties).  Device tensors in,
+        device tensors out; host arrays otherwise."""
+        (cx, cy), fl = _prep([cx, cy], np.float32, "float32")
+        p = int(cx.numel() if _is_dev(cx) else cx.size)
+        r = N.sbo_whatif_info()
+        r.struct_size = ctypes.sizeof(r)
+        m = self.stream_info()["m"]
+        if fl & N.SBO_DEVICE_PTRS:
+            import torch
+
+            def new(shape, dt):
+                return torch.empty(shape, dtype=getattr(torch, dt), device=cx.device)
+        else:
+            def new(shape, dt):
+                return np.empty(shape, getattr(np, dt))
+        out = {"gain": new(p, "int64"), "cand_mu": new(p, "float64"), "cand_var": new(p, "float64")}
+        if cov:
+            out["cov"] = new((p, m), "float64")
+        if lo_new:
+            out["lo_new"] = new((p, m), "float64")
+        self.ctx.check(self._lib.sbo_whatif(self.ctx.handle, _ptr(cx), _ptr(cy), p, float(beta), float(f_min),
+                                            _ptr(out["gain"]), _ptr(out["cand_mu"]), _ptr(out["cand_var"]),
+                                            _ptr(out.get("cov")), _ptr(out.get("lo_new")), ctypes.byref(r), fl))
+        out.update({f: getattr(r, f) for f, _ in N.sbo_whatif_info._fields_ if f != "struct_size"})
+        return out
+
+    def expander_subgoal(self, Dx, Dy, lo, hi, safe, width: int, height: int, goal, beta: float, f_min: float) -> int:
+        """The next subgoal by expander count: the node's candidate set (the
+        quarter of the frontier nearest the goal, ``node.subgoal_candidates``;
+        at most 1024), each candidate's ``whatif`` gain over the kept posterior
+        of the last ``tick_stream`` on this grid, and ``node.select_expander``.
+        Returns a grid index, or -1 without a frontier; with every gain zero
+        it is ``next_subgoal``'s choice."""
+        from . import node
+        Dx, Dy = np.asarray(Dx, np.float64), np.asarray(Dy, np.float64)
+        frontier = node.find_safety_contour_indices(Dx, Dy, safe, width, height)
+        cands, _ = node.subgoal_candidates(Dx, Dy, frontier, goal)
+        if cands.size == 0:
+            return -1
+        if cands.size > 1024:
+            raise ValueError(f"expander_subgoal: {cands.size} candidates (at most 1024)")
+        gains = self.whatif(Dx[cands].astype(np.float32), Dy[cands].astype(np.float32), beta, f_min)["gain"]
+        widths = np.asarray(hi, np.float64)[cands] - np.asarray(lo, np.float64)[cands]
+        return int(cands[node.select_expander(cands, gains, widths)])
+
     def query_cost(self, qx, qy):
         """Sweep work of each query under the current fit (sbo_query_cost):
         the k-tiles its 128-query block multiplies, per query.  Deterministic,

@@ -158,6 +158,41 @@ def next_subgoal(Dx, Dy, lo, hi, safe, width: int, height: int, gx: float = 0.0,
                                         int(height), float(gx), float(gy)))
 
 
+# ---- subgoal by expander count (TerrainMapper.whatif / expander_subgoal) ----
+def subgoal_candidates(Dx, Dy, frontier, goal):
+    """GetNextSubgoal's first half (:522-533) over the frontier's grid
+    indices: distances to the goal, a sort by (distance, frontier position),
+    the nearest max(1, F / 4).  Returns (grid indices, duplicates removed with
+    the first occurrence kept; each one's position in the sorted order)."""
+    frontier = np.asarray(frontier, np.int64)
+    nf = frontier.size
+    if nf == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    dx = np.asarray(Dx, np.float64)[frontier] - float(goal[0])
+    dy = np.asarray(Dy, np.float64)[frontier] - float(goal[1])
+    order = np.lexsort((np.arange(nf), np.sqrt(dx * dx + dy * dy)))   # distance, then frontier position (:526-530)
+    top = frontier[order[:max(1, nf // 4)]]                              # (:533)
+    _, first = np.unique(top, return_index=True)
+    pos = np.sort(first)
+    return top[pos], pos.astype(np.int64)
+
+
+def select_expander(cands, gains, widths) -> int:
+    """The position in ``cands`` (in their sorted order) of the candidate of
+    maximal gain; among equal gains the node's rule (:536-547): the first
+    strict maximum of width.  With every gain zero that is GetNextSubgoal's
+    choice.  -1 without candidates."""
+    gains = np.asarray(gains, np.int64)
+    widths = np.asarray(widths, np.float64)
+    if len(cands) == 0:
+        return -1
+    best, best_w = -1, -1.0
+    for t in np.flatnonzero(gains == gains.max()):
+        if widths[t] > best_w:
+            best, best_w = int(t), widths[t]
+    return best
+
+
 # ---- post-selection geometry (SURVEY.md 8(f)4; csrc/polygeom.cpp) ----------
 def _f64(a):
     return np.ascontiguousarray(a, np.float64)
