@@ -13,49 +13,25 @@
 // the device in f64: the new rows of ctx->Linv (column-major, lda = cap, zero
 // above the diagonal) and the new entries of ctx->zvec.
 //
-// Work layout: one workgroup per 128-position query block (the kept sweep
-// order), eight waves, wave w owns positions 16 w .. 16 w + 15; it walks the
-// 64-column k-tiles in ascending order and skips a tile when the block's kept
-// bounding box and the tile's box put every K* entry below 2^-L.  Kept tiles
-// evaluate K* = sf2 exp2(cexp d^2) in f64 from the f32 coordinates, one entry
-// per lane in the MFMA B-fragment map (k = l >> 4, q = l & 15), and multiply
-// it by the new rows in blocks of 16 on v_mfma_f64_16x16x4_f64: the rows of a
-// column are contiguous in L^-1, so a lane's A operand is one 8-byte load of
-// a 128-byte segment.  NJ row blocks share the K* of a step; more rows than
-// 16 NJ go in further passes over the tiles.  Entries below 2^-150 are exact
-// zeros in every mode, so a cutoff of L >= 150 drops only zeros and is
-// bitwise the dense update.  The epilogue sums v^2 and v z in a fixed order
-// (row block, register, then the four lane groups) and applies them in
-// place: no atomics on the state, and nothing depends on the launch grid.
+// Work layout: the k-tile walk of kstar_walk.hpp, shared with the what-if
+// sweep, over the new rows of L^-1: the rows of a column are contiguous, so a
+// lane's A operand is one 8-byte load of a 128-byte segment.  NJ row blocks
+// share the K* of a step; more rows than 16 NJ go in further passes over the
+// tiles.  A cutoff of L >= 150 drops only exact zeros and is bitwise the dense
+// update.  The epilogue sums v^2 and v z in a fixed order (row block, register,
+// then the four lane groups) and applies them in place: no atomics on the
+// state, and nothing depends on the launch grid.
 #include <cstdint>
 
+#include "kstar_walk.hpp"
 #include "sbo_internal.hpp"
 
 namespace sbo {
 namespace {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kUWaves = kBN / 16;
-constexpr int kUThreads = 64 * kUWaves;
-constexpr double kUZero = -150.0;   // K* exponents below it: the entry is +0.0
-
-__device__ __forceinline__ f64x4 mfma_f64(double a, double b, f64x4 c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
-// squared distance of two boxes (x0, x1, y0, y1); an empty k-tile box
-// (+inf, -inf, ..) is infinitely far
-__device__ __forceinline__ float box_d2(float4 k, float4 q) {
-    const float dx = fmaxf(0.0f, fmaxf(k.x - q.y, q.x - k.y));
-    const float dy = fmaxf(0.0f, fmaxf(k.z - q.w, q.z - k.w));
-    return dx * dx + dy * dy;
-}
-
-// C/D map of v_mfma_f64_16x16x4_f64: register c of lane l is row (l >> 4) + 4 c,
-// column l & 15.
+// Rows are the appended rows n_map .. n of L^-1, columns the wave's positions.
 template <int NJ>
-__global__ __launch_bounds__(kUThreads) void predict_update_kernel(
+__global__ __launch_bounds__(kWalkThreads) void predict_update_kernel(
     const double *__restrict__ Linv, int64_t ld, int64_t n_map, int64_t n, const double *__restrict__ z,
     const float *__restrict__ x, const float *__restrict__ y, const float4 *__restrict__ kbox,
     const float4 *__restrict__ qbox, const float *__restrict__ qx, const float *__restrict__ qy,
@@ -68,38 +44,15 @@ __global__ __launch_bounds__(kUThreads) void predict_update_kernel(
     const bool live = pos < ms;
     const double xq = live ? (double)qx[pos] : 0.0, yq = live ? (double)qy[pos] : 0.0;
     const float4 qb = qbox[blockIdx.x];
-    const float cexp_f = (float)cexp;
-    const int nrb = (int)((n - n_map + 15) / 16);
-    const int ntiles = (int)((n + kBK - 1) / kBK);
+    const WalkRows A{Linv + n_map, ld, n - n_map};
+    const int nrb = (int)((A.rows + 15) / 16);
     double dvar = 0.0, dmu = 0.0;
     int kept = 0;
     for (int rb0 = 0; rb0 < nrb; rb0 += NJ) {
         f64x4 acc[NJ];
 #pragma unroll
         for (int j = 0; j < NJ; ++j) acc[j] = f64x4{0.0, 0.0, 0.0, 0.0};
-        for (int t = 0; t < ntiles; ++t) {
-            // (the same decision in every lane of the workgroup)
-            if (skip_L > 0.0f && cexp_f * box_d2(kbox[t], qb) * 0.999f < -skip_L) continue;
-            if (rb0 == 0) ++kept;
-            for (int s = 0; s < kBK / 4; ++s) {
-                const int64_t k = (int64_t)t * kBK + 4 * s + g;
-                const bool kin = k < n;
-                double e = 0.0;
-                if (kin) {
-                    const double dx = (double)x[k] - xq, dy = (double)y[k] - yq;
-                    const double a = cexp * fma(dy, dy, dx * dx);
-                    e = a < kUZero ? 0.0 : sf2 * exp2(a);
-                }
-                double a[NJ];
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    const int64_t row = n_map + (int64_t)(rb0 + j) * 16 + r;
-                    a[j] = (kin && row < n) ? Linv[row + k * ld] : 0.0;
-                }
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) acc[j] = mfma_f64(a[j], e, acc[j]);
-            }
-        }
+        kstar_walk<NJ>(A, rb0, r, g, xq, yq, x, y, kbox, qb, n, cexp, sf2, skip_L, acc, kept);
         double s2 = 0.0, sz = 0.0;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
@@ -291,16 +244,12 @@ hipError_t launch_predict_update(hipStream_t s, const double *Linv, int64_t ld, 
                                  unsigned long long *tiles_kept) {
     const int64_t R = n - n_map;
     if (R <= 0 || ms <= 0) return hipSuccess;
-    const double cexp = -1.0 / (2.0 * ell * ell * 0.69314718055994530942);
-    const dim3 grid((unsigned)((ms + kBN - 1) / kBN)), block(kUThreads);
-    const int nrb = (int)((R + 15) / 16);
+    const double cexp = exp2_coef64(ell);
+    const dim3 grid((unsigned)((ms + kBN - 1) / kBN)), block(kWalkThreads);
 #define SBO_UPDATE(NJ)                                                                                          \
     hipLaunchKernelGGL(predict_update_kernel<NJ>, grid, block, 0, s, Linv, ld, n_map, n, z, x, y, kbox, qbox, kqx, \
                        kqy, kperm, ms, cexp, sf2, (float)skip_L, mu64, var64, tiles_kept)
-    if (nrb <= 1) SBO_UPDATE(1);
-    else if (nrb <= 2) SBO_UPDATE(2);
-    else if (nrb <= 4) SBO_UPDATE(4);
-    else SBO_UPDATE(8);
+    SBO_WALK_DISPATCH((R + 15) / 16, SBO_UPDATE);
 #undef SBO_UPDATE
     return hipGetLastError();
 }

@@ -28,8 +28,6 @@ namespace {
 
 constexpr const char *kVersion = "sbo-mi355x 0.1.0";
 
-bool dev(uint32_t flags) { return (flags & SBO_DEVICE_PTRS) != 0; }
-
 sbo_status finish(sbo_ctx *ctx, uint32_t flags) {
     if (flags & SBO_ASYNC) return SBO_OK;
     SBO_HIP(hipStreamSynchronize(ctx->stream));
@@ -39,10 +37,6 @@ sbo_status finish(sbo_ctx *ctx, uint32_t flags) {
 #ifndef SBO_FUSED_TN
 #define SBO_FUSED_TN 1
 #endif
-
-// The fit's f64 inverse holds exactly n rows: L^-1 in Linv, computed in f64
-// (SBO_OPT_INVERSE_BITS 64), current for the first n training points.
-bool inverse_current(const sbo_ctx *ctx, int64_t n) { return ctx->inverse_bits == 64 && ctx->linv_n == n; }
 
 // The guard's policy for the f64 inverse (inverse.cpp runs the inverse itself).
 // The digits of the current fit's sliced products (SBO_OPT_INV_OZ_ADAPT:
@@ -296,49 +290,6 @@ sbo_status stage_training(sbo_ctx *ctx, const float *x, const float *y, const fl
     }
     return SBO_OK;
 }
-
-// Sub-allocator over one scratch buffer (16-B aligned pieces).
-struct Carve {
-    char *base;
-    size_t off = 0;
-    explicit Carve(void *b = nullptr) : base(static_cast<char *>(b)) {}
-    template <class T> T *take(size_t count) {
-        T *p = reinterpret_cast<T *>(base + off);
-        off += (count * sizeof(T) + 255) & ~size_t(255);
-        return p;
-    }
-    static size_t need(size_t count, size_t sz) { return (count * sz + 255) & ~size_t(255); }
-};
-
-// Event bracket around one launch when profiling is on.
-hipEvent_t take_event(sbo_ctx *ctx) {
-    if (!ctx->ev_pool.empty()) {
-        hipEvent_t e = ctx->ev_pool.back();
-        ctx->ev_pool.pop_back();
-        return e;
-    }
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    return e;
-}
-
-struct Bracket {
-    sbo_ctx *ctx;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> *list;
-    hipEvent_t a = nullptr, b = nullptr;
-    // (on: a caller's own switch beside sbo_profile's, TickPlan::prof)
-    Bracket(sbo_ctx *c, std::vector<std::pair<hipEvent_t, hipEvent_t>> &l, bool on = true) : ctx(c), list(&l) {
-        if (!ctx->prof || !on) return;
-        a = take_event(ctx);
-        b = take_event(ctx);
-        if (a) (void)hipEventRecord(a, ctx->stream);
-    }
-    ~Bracket() {
-        if (!a || !b) return;
-        (void)hipEventRecord(b, ctx->stream);
-        list->emplace_back(a, b);
-    }
-};
 
 void recycle_events(sbo_ctx *ctx) {
     for (auto *l : {&ctx->ev_predict, &ctx->ev_fill}) {
@@ -2010,13 +1961,15 @@ static_assert(sizeof(sbo_stream_info) == 96, "sbo_stream_info: the bindings mirr
 
 // The skip budget of the sweep in effect (absolute, on any variance / mean):
 // skip_budget_for's tolerance of the fast sweep and of the precise plan
-// (precise_budget).
+// (precise_budget).  (Declared in sbo_host.hpp: sbo_whatif spends it too.)
+}  // namespace
 void stream_budget(const sbo_ctx *ctx, double &var, double &mean) {
     const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
     const double share = std::ldexp(1.0, -ctx->skip_budget);
     var = share * (ctx->precise ? std::min(std::max(ctx->probe_vmin, 1e-12 * sf2), sf2) : sf2);
     mean = share * std::sqrt(sf2);
 }
+namespace {
 
 // Worst-case effect of dropping K* entries below 2^-L on an update over rows
 // whose 1-norms give sum_l1sq and sum_l1z (sbo::StreamHead): with
@@ -2049,74 +2002,79 @@ int stream_cutoff(const sbo_ctx *ctx, const sbo::StreamHead &h, double budget_va
     return 0;
 }
 
-// sbo_tick_stream over queries already on the device: the path decision
-// (include/sbo.h), then either the update of the kept posterior and the
-// acquisition from it, or run_tick with the capture.
-sbo_status run_tick_stream(sbo_ctx *ctx, TickRequest rq) {
-    sbo::StreamKeep &k = ctx->keep;
-    const int64_t n = ctx->n;
-    const int64_t R = k.valid ? n - k.n_map : 0;
+// One sbo_tick_stream call: the report it leaves (info.reason is the verdict so
+// far), and for an update the cutoff and the bounds it spends.
+struct StreamTurn {
     sbo_stream_info info{};
-    info.struct_size = (uint32_t)sizeof(info);
-    info.m = rq.m;
-    info.rows = std::max<int64_t>(R, 0);
-    info.n_map = k.valid ? k.n_map : 0;
-    stream_budget(ctx, info.budget_var, info.budget_mean);
-    int reason = SBO_STREAM_UPDATED;
-    if (!k.valid)
-        reason = k.was_reset ? SBO_STREAM_RESET : SBO_STREAM_FIRST;
-    else if (k.epoch != ctx->fit_epoch || k.precise != ctx->precise)
-        reason = SBO_STREAM_REFIT;
-    else if (k.m != rq.m)
-        reason = SBO_STREAM_QUERIES_CHANGED;
-    else if (!(ctx->has_factor && inverse_current(ctx, n) && ctx->z_n == n && R >= 0))
-        reason = SBO_STREAM_NO_INVERSE;
-    else if (R > ctx->stream_max_rows)
-        reason = SBO_STREAM_ROWS_OVER_CAP;
+    int64_t R = 0;   // rows appended since the kept posterior was computed
+    int L = 0;
+    double spend_var = 0.0, spend_mean = 0.0;
+};
+
+// The part of the path decision that needs no device (include/sbo.h), in its order.
+int stream_decide(const sbo_ctx *ctx, int64_t m, int64_t R) {
+    const sbo::StreamKeep &k = ctx->keep;
+    if (!k.valid) return k.was_reset ? SBO_STREAM_RESET : SBO_STREAM_FIRST;
+    if (k.epoch != ctx->fit_epoch || k.precise != ctx->precise) return SBO_STREAM_REFIT;
+    if (k.m != m) return SBO_STREAM_QUERIES_CHANGED;
+    if (!(fit_state_complete(ctx, ctx->n) && R >= 0)) return SBO_STREAM_NO_INVERSE;
+    if (R > ctx->stream_max_rows) return SBO_STREAM_ROWS_OVER_CAP;
+    return SBO_STREAM_UPDATED;
+}
+
+// The queries against the kept ones and the appended rows' norms (one readback,
+// one sync), then the cutoff and whether the budget still covers its bounds.
+sbo_status stream_read_head(sbo_ctx *ctx, const TickRequest &rq, StreamTurn &t) {
+    sbo::StreamKeep &k = ctx->keep;
     sbo::StreamHead h{};
     sbo::StreamHead *dh = k.head.as<sbo::StreamHead>();
-    double spend_var = 0.0, spend_mean = 0.0;
-    int L = 0;
-    if (reason == SBO_STREAM_UPDATED) {
-        // the queries against the kept ones and the appended rows' norms: one readback, one sync
-        SBO_HIP(hipMemsetAsync(dh, 0, sizeof(sbo::StreamHead) + sizeof(unsigned long long), ctx->stream));
-        SBO_HIP(sbo::launch_stream_compare(ctx->stream, rq.qx, rq.qy, k.qx.as<float>(), k.qy.as<float>(),
-                                           k.perm.as<int32_t>(), k.ms, dh));
-        if (R > 0) {
-            SBO_HIP(k.l1.reserve(sbo::update_l1_bytes(R)));
-            SBO_HIP(sbo::launch_update_bound_sums(ctx->stream, ctx->Linv.as<double>(), ctx->cap, k.n_map, n,
-                                                  ctx->zvec.as<double>(), k.l1.as<double>(), dh));
-        }
-        SBO_HIP(hipMemcpyAsync(&h, dh, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-        SBO_HIP(hipStreamSynchronize(ctx->stream));
-        if (h.mismatch) {
-            reason = SBO_STREAM_QUERIES_CHANGED;
-        } else if (R > 0) {
-            L = stream_cutoff(ctx, h, info.budget_var, info.budget_mean, spend_var, spend_mean);
-            if (k.err_var + spend_var > info.budget_var || k.err_mean + spend_mean > info.budget_mean)
-                reason = SBO_STREAM_BUDGET;
-        }
+    SBO_HIP(hipMemsetAsync(dh, 0, sizeof(sbo::StreamHead) + sizeof(unsigned long long), ctx->stream));
+    SBO_HIP(sbo::launch_stream_compare(ctx->stream, rq.qx, rq.qy, k.qx.as<float>(), k.qy.as<float>(),
+                                       k.perm.as<int32_t>(), k.ms, dh));
+    if (t.R > 0) {
+        SBO_HIP(k.l1.reserve(sbo::update_l1_bytes(t.R)));
+        SBO_HIP(sbo::launch_update_bound_sums(ctx->stream, ctx->Linv.as<double>(), ctx->cap, k.n_map, ctx->n,
+                                              ctx->zvec.as<double>(), k.l1.as<double>(), dh));
     }
-    info.reason = reason;
-    if (reason != SBO_STREAM_UPDATED) {
-        rq.keep = true;
-        if (sbo_status st = run_tick(ctx, rq)) return st;
-        info.path = 0;
-        k.last = info;
-        return SBO_OK;
+    SBO_HIP(hipMemcpyAsync(&h, dh, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    SBO_HIP(hipStreamSynchronize(ctx->stream));
+    if (h.mismatch) {
+        t.info.reason = SBO_STREAM_QUERIES_CHANGED;
+    } else if (t.R > 0) {
+        t.L = stream_cutoff(ctx, h, t.info.budget_var, t.info.budget_mean, t.spend_var, t.spend_mean);
+        if (k.err_var + t.spend_var > t.info.budget_var || k.err_mean + t.spend_mean > t.info.budget_mean)
+            t.info.reason = SBO_STREAM_BUDGET;
     }
+    return SBO_OK;
+}
+
+// Path 0: the full tick, its posterior kept.
+sbo_status stream_fallback(sbo_ctx *ctx, TickRequest rq, StreamTurn &t) {
+    rq.keep = true;
+    if (sbo_status st = run_tick(ctx, rq)) return st;
+    t.info.path = 0;
+    ctx->keep.last = t.info;
+    return SBO_OK;
+}
+
+// Path 1: the rank-R update of the kept posterior, the acquisition from it,
+// and the kept state's bookkeeping.
+sbo_status stream_update(sbo_ctx *ctx, const TickRequest &rq, StreamTurn &t) {
+    sbo::StreamKeep &k = ctx->keep;
+    const int64_t n = ctx->n;
+    sbo::StreamHead *dh = k.head.as<sbo::StreamHead>();
     const int64_t nb = sbo::acq_blocks(k.ms);
     SBO_HIP(ctx->keys.reserve(sizeof(sbo_key) * (size_t)(nb + 1)));
-    if (R > 0) {
+    if (t.R > 0) {
         const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
         Bracket br(ctx, ctx->ev_predict);
         SBO_HIP(sbo::launch_predict_update(ctx->stream, ctx->Linv.as<double>(), ctx->cap, k.n_map, n,
                                            ctx->zvec.as<double>(), ctx->x.as<float>(), ctx->y.as<float>(),
                                            ctx->kbox.as<float4>(), k.qbox.as<float4>(), k.qx.as<float>(),
                                            k.qy.as<float>(), k.perm.as<int32_t>(), k.ms, ctx->hyper.length_scale, sf2,
-                                           L, k.mu64.as<double>(), k.var64.as<double>(),
+                                           t.L, k.mu64.as<double>(), k.var64.as<double>(),
                                            reinterpret_cast<unsigned long long *>(dh + 1)));
-        info.tiles_total = (k.ms + sbo::kBN - 1) / sbo::kBN * ((n + sbo::kBK - 1) / sbo::kBK);
+        t.info.tiles_total = kept_tiles_total(k.ms, n);
     }
     sbo_key *bkeys = ctx->keys.as<sbo_key>();
     SBO_HIP(sbo::launch_acquire_kept(ctx->stream, k.mu64.as<double>(), k.var64.as<double>(), k.ms, rq.beta, rq.f_min,
@@ -2124,13 +2082,31 @@ sbo_status run_tick_stream(sbo_ctx *ctx, TickRequest rq) {
                                      rq.safe, bkeys));
     SBO_HIP(sbo::launch_reduce_keys(ctx->stream, bkeys, nb, rq.key ? rq.key : bkeys + nb));
     k.n_map = n;
-    k.err_var += spend_var;
-    k.err_mean += spend_mean;
+    k.err_var += t.spend_var;
+    k.err_mean += t.spend_mean;
     ++k.updates;
-    info.path = 1;
-    info.cutoff_log2 = L;
-    k.last = info;
+    t.info.path = 1;
+    t.info.cutoff_log2 = t.L;
+    k.last = t.info;
     return SBO_OK;
+}
+
+// sbo_tick_stream over queries already on the device: the path decision
+// (include/sbo.h), then either the update of the kept posterior and the
+// acquisition from it, or run_tick with the capture.
+sbo_status run_tick_stream(sbo_ctx *ctx, TickRequest rq) {
+    const sbo::StreamKeep &k = ctx->keep;
+    StreamTurn t;
+    t.R = k.valid ? ctx->n - k.n_map : 0;
+    t.info.struct_size = (uint32_t)sizeof(t.info);
+    t.info.m = rq.m;
+    t.info.rows = std::max<int64_t>(t.R, 0);
+    t.info.n_map = k.valid ? k.n_map : 0;
+    stream_budget(ctx, t.info.budget_var, t.info.budget_mean);
+    t.info.reason = stream_decide(ctx, rq.m, t.R);
+    if (t.info.reason == SBO_STREAM_UPDATED)
+        if (sbo_status st = stream_read_head(ctx, rq, t)) return st;
+    return t.info.reason == SBO_STREAM_UPDATED ? stream_update(ctx, rq, t) : stream_fallback(ctx, rq, t);
 }
 
 // Host queries staged for a tick: hq sized for them and `rest` more bytes,
@@ -2621,7 +2597,6 @@ SBO_API sbo_status sbo_get_stream(const sbo_ctx *ctx, sbo_stream_info *out) {
     if (!ctx || !out || out->struct_size < sizeof(uint32_t)) return SBO_E_INVAL;
     const sbo::StreamKeep &k = ctx->keep;
     sbo_stream_info info = k.last;
-    info.struct_size = (uint32_t)std::min<size_t>(out->struct_size, sizeof(info));
     info.updates_since_full = k.updates;
     info.err_var = k.err_var;
     info.err_mean = k.err_mean;
@@ -2633,7 +2608,7 @@ SBO_API sbo_status sbo_get_stream(const sbo_ctx *ctx, sbo_stream_info *out) {
             return SBO_E_DEVICE;
         info.tiles_kept = (int64_t)kept;
     }
-    memcpy(out, &info, info.struct_size);
+    copy_info(out, info);
     return SBO_OK;
 }
 
@@ -2664,329 +2639,6 @@ SBO_API sbo_status sbo_debug_stream_state(sbo_ctx *ctx, double *mu64, double *va
     SBO_HIP(hipMemcpyAsync(mu64, dmu, bytes, hipMemcpyDeviceToHost, ctx->stream));
     SBO_HIP(hipMemcpyAsync(var64, dvar, bytes, hipMemcpyDeviceToHost, ctx->stream));
     SBO_HIP(hipStreamSynchronize(ctx->stream));
-    return SBO_OK;
-}
-
-// Model evidence (csrc/evidence.hip): two device phases with one readback
-// between them -- the column norms, per-tile sums and LOO outputs; then, after
-// the host has chosen the kept k-tile pairs from the tiles' norms and boxes,
-// the Gram contraction of grad[0] over (pair, row chunk) items.  Reads the
-// fitted state only; evws / evitems are its own workspaces.
-static sbo_status evidence_run(sbo_ctx *ctx, sbo_evidence_info *out, double *loo_mean, double *loo_var,
-                               uint32_t flags);
-
-SBO_API sbo_status sbo_evidence(sbo_ctx *ctx, sbo_evidence_info *out, double *loo_mean, double *loo_var,
-                                uint32_t flags) {
-    if (!ctx || !out) return SBO_E_INVAL;
-    try {
-        return evidence_run(ctx, out, loo_mean, loo_var, flags);
-    } catch (const std::bad_alloc &) {   // (the host-side tile and item lists)
-        ctx->err = "sbo_evidence: host allocation failed";
-        return SBO_E_OOM;
-    }
-}
-
-static sbo_status evidence_run(sbo_ctx *ctx, sbo_evidence_info *out, double *loo_mean, double *loo_var,
-                               uint32_t flags) {
-    SBO_CHECK(out->struct_size >= sizeof(uint32_t), SBO_E_INVAL, "sbo_evidence: struct_size not set");
-    const int64_t n = ctx->n;
-    SBO_CHECK(ctx->fitted && n > 0, SBO_E_STATE, "sbo_evidence: call sbo_fit first");
-    SBO_CHECK(ctx->has_factor && inverse_current(ctx, n) && ctx->z_n == n, SBO_E_STATE,
-              "sbo_evidence: needs the fit's factor, f64 inverse and z (not an imported state, SBO_OPT_INVERSE_BITS 64)");
-    SBO_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const int64_t T = (n + sbo::kBK - 1) / sbo::kBK;
-    const bool want_loo = loo_mean || loo_var, host_loo = want_loo && !dev(flags);
-    SBO_HIP(ctx->evws.reserve(Carve::need(n, 8) + Carve::need(T * sbo::kEvSums, 8) + Carve::need(1, 8) +
-                              (want_loo ? Carve::need(n, 8) : 0) + (host_loo ? 2 * Carve::need(n, 8) : 0)));
-    Carve cv(ctx->evws.as<void>());
-    double *dc = cv.take<double>(n), *dsums = cv.take<double>(T * sbo::kEvSums), *dres = cv.take<double>(1);
-    const double *X = ctx->Linv.as<double>(), *dalpha = ctx->alpha64.as<double>();
-    hipEvent_t ev[4] = {take_event(ctx), take_event(ctx), take_event(ctx), take_event(ctx)};
-    struct Give {   // the events go back to the pool on every path
-        sbo_ctx *c;
-        hipEvent_t *e;
-        ~Give() {
-            for (int i = 0; i < 4; ++i)
-                if (e[i]) c->ev_pool.push_back(e[i]);
-        }
-    } give{ctx, ev};
-    SBO_CHECK(ev[0] && ev[1] && ev[2] && ev[3], SBO_E_DEVICE, "sbo_evidence: hipEventCreate failed");
-
-    // phase 1: c_i, the per-tile sums, the LOO outputs
-    SBO_HIP(hipEventRecord(ev[0], s));
-    SBO_HIP(sbo::launch_evidence_norms(s, X, ctx->cap, n, dalpha, ctx->zvec.as<double>(), ctx->obs.as<float>(),
-                                       ctx->L.as<float>(), ctx->cap, ctx->hyper.prior_mean, dc, dsums));
-    if (want_loo) {
-        int64_t *dorder = cv.take<int64_t>(n);
-        double *dm = loo_mean, *dv = loo_var;
-        if (host_loo) {
-            dm = cv.take<double>(n);
-            dv = cv.take<double>(n);
-        }
-        SBO_HIP(hipMemcpyAsync(dorder, ctx->order.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, s));
-        SBO_HIP(sbo::launch_evidence_loo(s, dc, dalpha, ctx->obs.as<float>(), dorder, n, loo_mean ? dm : nullptr,
-                                         loo_var ? dv : nullptr));
-        if (host_loo && loo_mean) SBO_HIP(hipMemcpyAsync(loo_mean, dm, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-        if (host_loo && loo_var) SBO_HIP(hipMemcpyAsync(loo_var, dv, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    }
-    SBO_HIP(hipEventRecord(ev[1], s));
-    std::vector<double> sums((size_t)T * sbo::kEvSums), al1(T), sl1(T);
-    std::vector<float> boxes((size_t)4 * T);
-    SBO_HIP(hipMemcpyAsync(sums.data(), dsums, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, s));
-    SBO_HIP(hipMemcpyAsync(boxes.data(), ctx->kbox.as<void>(), sizeof(float) * boxes.size(), hipMemcpyDeviceToHost, s));
-    SBO_HIP(hipStreamSynchronize(s));
-
-    // the totals in tile order
-    double tot[sbo::kEvSums] = {};
-    for (int64_t t = 0; t < T; ++t) {
-        for (int j = 0; j < sbo::kEvSums; ++j) tot[j] += sums[t * sbo::kEvSums + j];
-        al1[t] = sums[t * sbo::kEvSums];
-        sl1[t] = sums[t * sbo::kEvSums + 1];
-    }
-    const double sum_c = tot[2], aa = tot[3], ar = tot[4];
-    const double sn = ctx->hyper.noise_level, noise = sn - ctx->jitter;   // (hyper.noise_level holds the jitter too)
-    const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
-    sbo_evidence_info r{};
-    r.n = n;
-    r.data_fit = -0.5 * tot[7];
-    r.log_det = tot[6];
-    r.lml = r.data_fit - r.log_det - 0.5 * (double)n * sbo::kEvLog2Pi;
-    r.grad[1] = (ar - sn * aa) - ((double)n - sn * sum_c);
-    r.grad[2] = 0.5 * noise * (aa - sum_c);
-    r.grad[3] = tot[5];
-    r.loo_log_pred = tot[8];
-
-    // the cutoff, then the items: kept pair I <= J x chunk of kEvChunk rows from 64 J
-    r.grad_budget = ctx->evidence_budget > 0 ? std::ldexp((double)n, -ctx->evidence_budget) : 0.0;
-    // host cost per call, T = n / 64: the T x T drop map (64 KiB at n = 16384, 1 MiB at 65536), inside
-    // evidence_pairs up to T^2 / 2 candidates of 16 B (0.5 / 8 MiB) and their sort, and 16 B per item below
-    // (about n^2 / 1400 items: 3 MiB at 16384, 47 MiB at 65536)
-    std::vector<uint8_t> drop((size_t)T * T);
-    sbo::evidence_pairs(boxes.data(), al1.data(), sl1.data(), T, ctx->hyper.length_scale, sf2, r.grad_budget,
-                        drop.data(), &r.grad_err_bound);
-    std::vector<int4> items;
-    r.pairs_total = T * (T + 1) / 2;
-    for (int64_t J = 0; J < T; ++J)
-        for (int64_t I = 0; I <= J; ++I) r.pairs_kept += drop[I * T + J] ? 0 : 1;
-    // items grouped by the band of kEvChunk rows their chunk starts in (then J, then I): the
-    // workgroups in flight read one band of X -- kEvChunk x n doubles, which the last-level
-    // cache holds -- and share the J block
-    constexpr int64_t kBand = sbo::kEvChunk / sbo::kBK;   // k-tiles per chunk
-    for (int64_t g = 0; g * sbo::kEvChunk < n; ++g)
-        for (int64_t J = 0; J < T && J / kBand <= g; ++J) {
-            const int64_t k0 = J * sbo::kBK + (g - J / kBand) * sbo::kEvChunk;
-            if (k0 >= n) continue;
-            for (int64_t I = 0; I <= J; ++I)
-                if (!drop[I * T + J]) items.push_back(make_int4((int)I, (int)J, (int)k0, k0 == J * sbo::kBK ? 1 : 0));
-        }
-    r.dropped = r.pairs_kept < r.pairs_total ? 1 : 0;
-    const int64_t ni = (int64_t)items.size();
-    SBO_HIP(ctx->evitems.reserve(Carve::need(ni, sizeof(int4)) + Carve::need(ni, 8)));
-    Carve ci(ctx->evitems.as<void>());
-    int4 *ditems = ci.take<int4>(ni);
-    double *dslots = ci.take<double>(ni);
-    SBO_HIP(hipMemcpyAsync(ditems, items.data(), sizeof(int4) * (size_t)ni, hipMemcpyHostToDevice, s));
-    SBO_HIP(hipEventRecord(ev[2], s));
-    SBO_HIP(sbo::launch_evidence_gram(s, X, ctx->cap, n, ctx->x.as<float>(), ctx->y.as<float>(), dalpha, ditems, ni,
-                                      ctx->hyper.length_scale, sf2, dslots, dres));
-    SBO_HIP(hipEventRecord(ev[3], s));
-    double g0 = 0.0;
-    SBO_HIP(hipMemcpyAsync(&g0, dres, sizeof(double), hipMemcpyDeviceToHost, s));
-    SBO_HIP(hipStreamSynchronize(s));
-    r.grad[0] = g0;   // (the slots carry the 1/2: a diagonal pair halved, an off-diagonal one standing for both orders)
-    float ms1 = 0.0f, ms2 = 0.0f;
-    SBO_HIP(hipEventElapsedTime(&ms1, ev[0], ev[1]));
-    SBO_HIP(hipEventElapsedTime(&ms2, ev[2], ev[3]));
-    r.ms = (double)ms1 + (double)ms2;
-    r.struct_size = (uint32_t)std::min<size_t>(out->struct_size, sizeof(r));
-    memcpy(out, &r, r.struct_size);
-    return SBO_OK;
-}
-
-SBO_API sbo_status sbo_debug_evidence_pairs(const float *boxes, const double *alpha_l1, const double *sqrtc_l1,
-                                            int64_t T, sbo_hyper hyper, double budget, uint8_t *drop, double *bound) {
-    if (T < 0 || !bound || (T > 0 && (!boxes || !alpha_l1 || !sqrtc_l1 || !drop))) return SBO_E_INVAL;
-    if (!(hyper.length_scale > 0.0) || !(hyper.sigma_f > 0.0)) return SBO_E_INVAL;
-    try {
-        sbo::evidence_pairs(boxes, alpha_l1, sqrtc_l1, T, hyper.length_scale, hyper.sigma_f * hyper.sigma_f, budget,
-                            drop, bound);
-    } catch (...) {
-        return SBO_E_OOM;
-    }
-    return SBO_OK;
-}
-
-// What-if posterior (csrc/whatif.hip): the candidate weights W = K^-1 K_c by
-// two triangular products on the f64 inverse, the candidates' sums, one
-// readback (var_c and |w_j|_1: the host chooses the cutoff from them), then the
-// sweep over the kept posterior.  Reads the fitted and the kept state only;
-// wiws is its own workspace.
-static_assert(sizeof(sbo_whatif_info) == 80, "sbo_whatif_info: the bindings mirror this layout");
-
-static sbo_status whatif_run(sbo_ctx *ctx, const float *cx, const float *cy, int64_t p, double beta, double f_min,
-                             int64_t *gain, double *cand_mu, double *cand_var, double *cov, double *lo_new,
-                             sbo_whatif_info *info, uint32_t flags);
-
-SBO_API sbo_status sbo_whatif(sbo_ctx *ctx, const float *cx, const float *cy, int64_t p, double beta, double f_min,
-                              int64_t *gain, double *cand_mu, double *cand_var, double *cov, double *lo_new,
-                              sbo_whatif_info *info, uint32_t flags) {
-    if (!ctx) return SBO_E_INVAL;
-    try {
-        return whatif_run(ctx, cx, cy, p, beta, f_min, gain, cand_mu, cand_var, cov, lo_new, info, flags);
-    } catch (const std::bad_alloc &) {   // (the host copies of the candidates' sums and counts)
-        ctx->err = "sbo_whatif: host allocation failed";
-        return SBO_E_OOM;
-    }
-}
-
-static sbo_status whatif_run(sbo_ctx *ctx, const float *cx, const float *cy, int64_t p, double beta, double f_min,
-                             int64_t *gain, double *cand_mu, double *cand_var, double *cov, double *lo_new,
-                             sbo_whatif_info *info, uint32_t flags) {
-    SBO_CHECK(cx && cy && gain, SBO_E_INVAL, "sbo_whatif: null candidates or gain");
-    SBO_CHECK(p > 0 && p <= 1024, SBO_E_INVAL, "sbo_whatif: p must be in [1, 1024]");
-    SBO_CHECK(std::isfinite(beta) && !std::isnan(f_min), SBO_E_INVAL, "sbo_whatif: beta/f_min must be finite");
-    SBO_CHECK(!info || info->struct_size >= sizeof(uint32_t), SBO_E_INVAL, "sbo_whatif: struct_size not set");
-    const sbo::StreamKeep &k = ctx->keep;
-    const int64_t n = ctx->n;
-    SBO_CHECK(ctx->fitted && n > 0, SBO_E_STATE, "sbo_whatif: call sbo_fit first");
-    SBO_CHECK(k.valid, SBO_E_STATE, "sbo_whatif: no kept posterior (call sbo_tick_stream first)");
-    SBO_CHECK(k.epoch == ctx->fit_epoch && k.n_map == n, SBO_E_STATE,
-              "sbo_whatif: the kept posterior has not seen every fitted row (call sbo_tick_stream again)");
-    SBO_CHECK(ctx->has_factor && inverse_current(ctx, n) && ctx->z_n == n, SBO_E_STATE,
-              "sbo_whatif: needs the fit's f64 inverse and z (not an imported state, SBO_OPT_INVERSE_BITS 64)");
-    SBO_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const int64_t pp = sbo::round_up(p, 16), m = k.m;
-    const bool host = !dev(flags);
-    const size_t mat = (size_t)p * (size_t)m;
-    SBO_HIP(ctx->wiws.reserve(2 * Carve::need((size_t)pp * (size_t)n, 8) + Carve::need(sbo::whatif_part_bytes(pp), 1) +
-                              3 * Carve::need(p, 8) + Carve::need(2 * pp, 8) + Carve::need(p + 1, 8) +
-                              (host ? 2 * Carve::need(p, 4) + (cov ? Carve::need(mat, 8) : 0) +
-                                          (lo_new ? Carve::need(mat, 8) : 0)
-                                    : 0)));
-    Carve cv(ctx->wiws.as<void>());
-    double *Kt = cv.take<double>((size_t)pp * (size_t)n), *Ut = cv.take<double>((size_t)pp * (size_t)n), *Wt = Kt;
-    double *part = cv.take<double>(sbo::whatif_part_bytes(pp) / 8);
-    double *dmu = cv.take<double>(p), *dvar = cv.take<double>(p), *dl1 = cv.take<double>(p);
-    double *dpar = cv.take<double>(2 * pp);
-    unsigned long long *dgain = cv.take<unsigned long long>(p + 1), *dkept = dgain + p;
-    const float *dcx = cx, *dcy = cy;
-    double *dcov = cov, *dlo = lo_new;
-    if (host) {
-        float *sx = cv.take<float>(p), *sy = cv.take<float>(p);
-        SBO_HIP(hipMemcpyAsync(sx, cx, sizeof(float) * p, hipMemcpyHostToDevice, s));
-        SBO_HIP(hipMemcpyAsync(sy, cy, sizeof(float) * p, hipMemcpyHostToDevice, s));
-        dcx = sx;
-        dcy = sy;
-        if (cov) dcov = cv.take<double>(mat);
-        if (lo_new) dlo = cv.take<double>(mat);
-    }
-    hipEvent_t ev[4] = {take_event(ctx), take_event(ctx), take_event(ctx), take_event(ctx)};
-    struct Give {   // the events go back to the pool on every path
-        sbo_ctx *c;
-        hipEvent_t *e;
-        ~Give() {
-            for (int i = 0; i < 4; ++i)
-                if (e[i]) c->ev_pool.push_back(e[i]);
-        }
-    } give{ctx, ev};
-    SBO_CHECK(ev[0] && ev[1] && ev[2] && ev[3], SBO_E_DEVICE, "sbo_whatif: hipEventCreate failed");
-
-    // the weights: K_c^T, U^T = K_c^T X^T, W^T = U^T X (over K_c^T), the candidates' sums
-    const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f, noise = ctx->hyper.noise_level;   // (holds the jitter too)
-    const double *X = ctx->Linv.as<double>();
-    const double one = 1.0, zero = 0.0;
-    SBO_HIP(hipEventRecord(ev[0], s));
-    {
-        Bracket br(ctx, ctx->ev_fill);
-        SBO_HIP(sbo::launch_whatif_fill(s, ctx->x.as<float>(), ctx->y.as<float>(), n, dcx, dcy, p, pp,
-                                        ctx->hyper.length_scale, sf2, Kt));
-        SBO_BLAS(rocblas_set_pointer_mode(ctx->blas, rocblas_pointer_mode_host));
-        if (ctx->whatif_gemm) {   // (the inverse's strict upper half is stored as zeros)
-            SBO_BLAS(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_transpose, (rocblas_int)pp,
-                                   (rocblas_int)n, (rocblas_int)n, &one, Kt, (rocblas_int)pp, X, (rocblas_int)ctx->cap,
-                                   &zero, Ut, (rocblas_int)pp));
-            SBO_BLAS(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_none, (rocblas_int)pp,
-                                   (rocblas_int)n, (rocblas_int)n, &one, Ut, (rocblas_int)pp, X, (rocblas_int)ctx->cap,
-                                   &zero, Wt, (rocblas_int)pp));
-        } else {
-            SBO_BLAS(rocblas_dtrmm(ctx->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_transpose,
-                                   rocblas_diagonal_non_unit, (rocblas_int)pp, (rocblas_int)n, &one, X,
-                                   (rocblas_int)ctx->cap, Kt, (rocblas_int)pp, Ut, (rocblas_int)pp));
-            SBO_BLAS(rocblas_dtrmm(ctx->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_none,
-                                   rocblas_diagonal_non_unit, (rocblas_int)pp, (rocblas_int)n, &one, X,
-                                   (rocblas_int)ctx->cap, Ut, (rocblas_int)pp, Wt, (rocblas_int)pp));
-        }
-        SBO_HIP(sbo::launch_whatif_stats(s, Ut, Wt, p, pp, n, ctx->zvec.as<double>(), ctx->hyper.prior_mean, sf2, noise,
-                                         beta, part, dmu, dvar, dl1, dpar));
-    }
-    SBO_HIP(hipEventRecord(ev[1], s));
-    std::vector<double> hvar((size_t)p), hl1((size_t)p);
-    SBO_HIP(hipMemcpyAsync(hvar.data(), dvar, sizeof(double) * p, hipMemcpyDeviceToHost, s));
-    SBO_HIP(hipMemcpyAsync(hl1.data(), dl1, sizeof(double) * p, hipMemcpyDeviceToHost, s));
-    SBO_HIP(hipStreamSynchronize(s));
-
-    // the cutoff: the context's fixed one, or the smallest L within the sweep's budgets
-    sbo_whatif_info r{};
-    int L = ctx->skip_log2;
-    if (L < 0) {
-        double bvar = 0.0, bmean = 0.0;
-        stream_budget(ctx, bvar, bmean);
-        sbo::whatif_cutoff(p, hl1.data(), hvar.data(), noise, beta, sf2, bvar, bmean, &L, &r.err_cov);
-    } else {
-        r.err_cov = sbo::whatif_err_cov(L, sf2, *std::max_element(hl1.begin(), hl1.end()));
-    }
-
-    // the sweep
-    SBO_HIP(hipMemsetAsync(dgain, 0, sizeof(unsigned long long) * (size_t)(p + 1), s));
-    SBO_HIP(hipEventRecord(ev[2], s));
-    {
-        Bracket br(ctx, ctx->ev_predict);
-        SBO_HIP(sbo::launch_whatif(s, Wt, pp, p, n, ctx->x.as<float>(), ctx->y.as<float>(), ctx->kbox.as<float4>(),
-                                   k.qbox.as<float4>(), k.qx.as<float>(), k.qy.as<float>(), k.perm.as<int32_t>(), k.ms,
-                                   m, ctx->hyper.length_scale, sf2, L, k.mu64.as<double>(), k.var64.as<double>(), dcx,
-                                   dcy, dpar, beta, f_min, dgain, dcov, dlo, dkept));
-    }
-    SBO_HIP(hipEventRecord(ev[3], s));
-    std::vector<unsigned long long> hgain((size_t)p + 1);
-    SBO_HIP(hipMemcpyAsync(hgain.data(), dgain, sizeof(unsigned long long) * (size_t)(p + 1), hipMemcpyDeviceToHost, s));
-    const hipMemcpyKind out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (!host) SBO_HIP(hipMemcpyAsync(gain, dgain, sizeof(int64_t) * p, out, s));
-    if (cand_mu) SBO_HIP(hipMemcpyAsync(cand_mu, dmu, sizeof(double) * p, out, s));
-    if (cand_var) SBO_HIP(hipMemcpyAsync(cand_var, dvar, sizeof(double) * p, out, s));
-    if (host && cov) SBO_HIP(hipMemcpyAsync(cov, dcov, sizeof(double) * mat, out, s));
-    if (host && lo_new) SBO_HIP(hipMemcpyAsync(lo_new, dlo, sizeof(double) * mat, out, s));
-    SBO_HIP(hipStreamSynchronize(s));
-    r.best = 0;
-    for (int64_t j = 0; j < p; ++j) {
-        if (host) gain[j] = (int64_t)hgain[(size_t)j];
-        if (hgain[(size_t)j] > hgain[(size_t)r.best]) r.best = j;   // (the lowest j on ties)
-    }
-    if (!info) return SBO_OK;
-    r.best_gain = (int64_t)hgain[(size_t)r.best];
-    r.cutoff_log2 = L;
-    r.p = p;
-    r.m = m;
-    r.n = n;
-    r.tiles_total = (k.ms + sbo::kBN - 1) / sbo::kBN * ((n + sbo::kBK - 1) / sbo::kBK);
-    r.tiles_kept = (int64_t)hgain[(size_t)p];
-    float ms1 = 0.0f, ms2 = 0.0f;
-    SBO_HIP(hipEventElapsedTime(&ms1, ev[0], ev[1]));
-    SBO_HIP(hipEventElapsedTime(&ms2, ev[2], ev[3]));
-    r.ms = (double)ms1 + (double)ms2;
-    r.struct_size = (uint32_t)std::min<size_t>(info->struct_size, sizeof(r));
-    memcpy(info, &r, r.struct_size);
-    return SBO_OK;
-}
-
-SBO_API sbo_status sbo_debug_whatif_cutoff(int64_t p, const double *w_l1, const double *cand_var, double s,
-                                           double beta, double sf2, double budget_var, double budget_mean,
-                                           int32_t *cutoff_log2, double *err_cov) {
-    if (p <= 0 || !w_l1 || !cand_var || !cutoff_log2 || !err_cov || !(sf2 > 0.0)) return SBO_E_INVAL;
-    int L = 0;
-    sbo::whatif_cutoff(p, w_l1, cand_var, s, beta, sf2, budget_var, budget_mean, &L, err_cov);
-    *cutoff_log2 = L;
     return SBO_OK;
 }
 

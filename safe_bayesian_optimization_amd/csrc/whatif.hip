@@ -29,18 +29,12 @@
 // whatif_cand_kernel reduce u_j . z, |u_j|^2 and |w_j|_1 in a fixed order
 // (column chunks, then the chunks ascending; no floating-point atomics).
 //
-// The sweep (whatif_kernel) has predict_update_kernel's work layout with
-// another left operand and another epilogue: one workgroup per 128-position
-// query block of the kept order, eight waves, wave w owns positions 16 w ..
-// 16 w + 15; it walks the 64-column k-tiles in ascending order and skips a tile
-// when the block's box and the tile's box put every K* entry below 2^-L.  Kept
-// tiles evaluate K* = sf2 exp2(cexp d^2) in f64 in the MFMA B-fragment map
-// (k = l >> 4, q = l & 15) and multiply it by W^T in blocks of 16 candidates on
-// v_mfma_f64_16x16x4_f64: W^T is stored pp x n column-major, so the sixteen
-// candidates of a column are one 128-byte segment and a lane's A operand is
-// one 8-byte load of it.  NJ candidate blocks share the K* of a step; more
-// candidates than 16 NJ go in further passes over the tiles.  Entries below
-// 2^-150 are exact zeros in every mode, so L >= 150 is bitwise the dense call.
+// The sweep (whatif_kernel) is the k-tile walk of kstar_walk.hpp, shared with
+// predict_update_kernel, with another left operand and another epilogue: W^T
+// is stored pp x n column-major, so the sixteen candidates of a column are one
+// 128-byte segment and a lane's A operand is one 8-byte load of it.  NJ
+// candidate blocks share the K* of a step; more candidates than 16 NJ go in
+// further passes over the tiles.  L >= 150 is bitwise the dense call.
 // The epilogue forms, per (candidate, position), the direct term k(q, c_j),
 // cov, mu', var', lo' and the newly-safe predicate; a candidate's count over a
 // wave's sixteen positions comes from one ballot and is added with an integer
@@ -58,36 +52,14 @@
 #include <cmath>
 #include <cstdint>
 
+#include "kstar_walk.hpp"
 #include "sbo_internal.hpp"
 
 namespace sbo {
 namespace {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kWWaves = kBN / 16;
-constexpr int kWThreads = 64 * kWWaves;
-constexpr double kWZero = -150.0;   // K* exponents below it: the entry is +0.0
 constexpr int kWChunks = 32;        // column chunks of the candidate sums
 constexpr int kWSums = 3;           // u . z, |u|^2, |w|_1
-
-__device__ __forceinline__ f64x4 mfma_f64(double a, double b, f64x4 c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
-// squared distance of two boxes (x0, x1, y0, y1); an empty k-tile box
-// (+inf, -inf, ..) is infinitely far
-__device__ __forceinline__ float box_d2(float4 k, float4 q) {
-    const float dx = fmaxf(0.0f, fmaxf(k.x - q.y, q.x - k.y));
-    const float dy = fmaxf(0.0f, fmaxf(k.z - q.w, q.z - k.w));
-    return dx * dx + dy * dy;
-}
-
-__device__ __forceinline__ double rbf64(double ax, double ay, double bx, double by, double cexp, double sf2) {
-    const double dx = ax - bx, dy = ay - by;
-    const double a = cexp * fma(dy, dy, dx * dx);
-    return a < kWZero ? 0.0 : sf2 * exp2(a);
-}
 
 // Kt[j + k pp] = k(train_k, c_j) for j < p, 0 for the padding rows p <= j < pp.
 __global__ __launch_bounds__(256) void whatif_fill_kernel(const float *__restrict__ x, const float *__restrict__ y,
@@ -157,10 +129,9 @@ __global__ __launch_bounds__(256) void whatif_cand_kernel(const double *__restri
     cpar[2 * j + 1] = 1.0 / d;
 }
 
-// C/D map of v_mfma_f64_16x16x4_f64: register c of lane l is row (l >> 4) + 4 c,
-// column l & 15.  Rows are candidates, columns the wave's positions.
+// Rows are candidates, columns the wave's positions.
 template <int NJ>
-__global__ __launch_bounds__(kWThreads) void whatif_kernel(
+__global__ __launch_bounds__(kWalkThreads) void whatif_kernel(
     const double *__restrict__ Wt, int64_t pp, int64_t p, int64_t n, const float *__restrict__ x,
     const float *__restrict__ y, const float4 *__restrict__ kbox, const float4 *__restrict__ qbox,
     const float *__restrict__ qx, const float *__restrict__ qy, const int32_t *__restrict__ perm, int64_t ms, int64_t m,
@@ -186,32 +157,14 @@ __global__ __launch_bounds__(kWThreads) void whatif_kernel(
         safe = __dsub_rn((double)(float)muq, __dmul_rn(beta, (double)sdf)) > f_min;
     }
     const float4 qb = qbox[blockIdx.x];
-    const float cexp_f = (float)cexp;
+    const WalkRows A{Wt, pp, pp};
     const int nrb = (int)(pp / 16);
-    const int ntiles = (int)((n + kBK - 1) / kBK);
     int kept = 0;
     for (int rb0 = 0; rb0 < nrb; rb0 += NJ) {
         f64x4 acc[NJ];
 #pragma unroll
         for (int j = 0; j < NJ; ++j) acc[j] = f64x4{0.0, 0.0, 0.0, 0.0};
-        for (int t = 0; t < ntiles; ++t) {
-            // (the same decision in every lane of the workgroup)
-            if (skip_L > 0.0f && cexp_f * box_d2(kbox[t], qb) * 0.999f < -skip_L) continue;
-            if (rb0 == 0) ++kept;
-            for (int s = 0; s < kBK / 4; ++s) {
-                const int64_t k = (int64_t)t * kBK + 4 * s + g;
-                const bool kin = k < n;
-                const double e = kin ? rbf64((double)x[k], (double)y[k], xq, yq, cexp, sf2) : 0.0;
-                double a[NJ];
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    const int64_t row = (int64_t)(rb0 + j) * 16 + r;
-                    a[j] = (kin && row < pp) ? Wt[row + k * pp] : 0.0;
-                }
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) acc[j] = mfma_f64(a[j], e, acc[j]);
-            }
-        }
+        kstar_walk<NJ>(A, rb0, r, g, xq, yq, x, y, kbox, qb, n, cexp, sf2, skip_L, acc, kept);
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
 #pragma unroll
@@ -245,7 +198,7 @@ size_t whatif_part_bytes(int64_t pp) { return sizeof(double) * (size_t)pp * kWCh
 hipError_t launch_whatif_fill(hipStream_t s, const float *x, const float *y, int64_t n, const float *cx,
                               const float *cy, int64_t p, int64_t pp, double ell, double sf2, double *Kt) {
     if (n <= 0 || pp <= 0) return hipSuccess;
-    const double cexp = -1.0 / (2.0 * ell * ell * 0.69314718055994530942);
+    const double cexp = exp2_coef64(ell);
     hipLaunchKernelGGL(whatif_fill_kernel, dim3((unsigned)((n * pp + 255) / 256)), dim3(256), 0, s, x, y, n, cx, cy, p,
                        pp, cexp, sf2, Kt);
     return hipGetLastError();
@@ -269,16 +222,12 @@ hipError_t launch_whatif(hipStream_t s, const double *Wt, int64_t pp, int64_t p,
                          double beta, double f_min, unsigned long long *gain, double *cov, double *lo_new,
                          unsigned long long *tiles_kept) {
     if (p <= 0 || ms <= 0 || n <= 0) return hipSuccess;
-    const double cexp = -1.0 / (2.0 * ell * ell * 0.69314718055994530942);
-    const dim3 grid((unsigned)((ms + kBN - 1) / kBN)), block(kWThreads);
-    const int nrb = (int)(pp / 16);
+    const double cexp = exp2_coef64(ell);
+    const dim3 grid((unsigned)((ms + kBN - 1) / kBN)), block(kWalkThreads);
 #define SBO_WHATIF(NJ)                                                                                              \
     hipLaunchKernelGGL(whatif_kernel<NJ>, grid, block, 0, s, Wt, pp, p, n, x, y, kbox, qbox, kqx, kqy, kperm, ms, m, \
                        cexp, sf2, (float)skip_L, mu64, var64, cx, cy, cpar, beta, f_min, gain, cov, lo_new, tiles_kept)
-    if (nrb <= 1) SBO_WHATIF(1);
-    else if (nrb <= 2) SBO_WHATIF(2);
-    else if (nrb <= 4) SBO_WHATIF(4);
-    else SBO_WHATIF(8);
+    SBO_WALK_DISPATCH(pp / 16, SBO_WHATIF);
 #undef SBO_WHATIF
     return hipGetLastError();
 }

@@ -4,7 +4,8 @@ workloads, and the outputs are compared element by element.
 
   python tools/compare_libs.py LIB_A LIB_B [--configs C4 C2 box]
   python tools/compare_libs.py LIB_A LIB_B --factor-matrix   (fits under the Cholesky's options, appends)
-  python tools/compare_libs.py LIB_A LIB_B --inverse-matrix  (fits under the f64 inverse's options, appends)"""
+  python tools/compare_libs.py LIB_A LIB_B --inverse-matrix  (fits under the f64 inverse's options, appends)
+  python tools/compare_libs.py LIB_A LIB_B --readers-matrix  (the streaming update, sbo_whatif and sbo_evidence)"""
 import argparse
 import os
 import subprocess
@@ -163,6 +164,86 @@ np.savez({path!r}, **out)
 print("ok", N.LIB_PATH, len(out), "arrays")
 '''
 
+# --readers-matrix: the readers of the fitted state (the streaming update, sbo_whatif, sbo_evidence) at their
+# tests' shapes, one context per shape.  Timings (ms) are left out.
+READERS_CHILD = r'''
+import ctypes, sys, numpy as np, torch
+sys.path.insert(0, {root!r})
+from safe_bayesian_optimization_amd import TerrainMapper
+from safe_bayesian_optimization_amd import _native as N
+from tests import evidence_model as EM
+from tests import test_gpu_evidence as TE
+from tests import test_gpu_whatif as TW
+from tests.test_gpu_stream_tick import WIDE_SHAPES, Rig, wide_options
+out = {{}}
+dev = torch.device("cuda:0")
+def put(name, d, skip=("ms",)):
+    for k, v in d.items():
+        if k in skip:
+            continue
+        out[name + "_" + k] = np.frombuffer(v.encode(), np.uint8) if isinstance(v, str) else np.asarray(v)
+# stream: per skip setting a refit, the full tick that keeps its posterior, the append, the update
+def stream(name, r, n0, b, skips):
+    for skip in skips:
+        r.gm.set_option(N.SBO_OPT_TILE_SKIP, skip)
+        r.fit(n0)
+        r.tick()
+        r.append(b)
+        h, key = r.tick()
+        info = r.gm.stream_info()
+        assert (info["path"], info["rows"]) == (1, b), info
+        mu, var = r.gm.stream_state(r.m)
+        tag = f"stream_{{name}}_skip{{skip}}"
+        put(tag, h)
+        put(tag, dict(key=np.array(key, np.float64), state_mu=mu, state_var=var))
+        put(tag, {{k: info[k] for k in ("cutoff_log2", "tiles_kept", "tiles_total", "reason", "err_var", "err_mean")}})
+for n0, b in [(250, 1), (250, 17), (250, 33)] + WIDE_SHAPES:
+    r = Rig(dev, n0 + b, seed=3 * n0 + b, options=wide_options(b))
+    stream(f"n{{n0}}_b{{b}}", r, n0, b, (-1, 0, 200))
+    r.gm.close()
+r = Rig(dev, 516, seed=17, x_range=(0.0, 1.0), y_range=(0.0, 2.5), options=[(N.SBO_OPT_PRECISION, 1)])
+stream("precise_n500_b16", r, 500, 16, (-1,))
+r.gm.close()
+# what-if
+for shape, kw in TW.SHAPES.items():
+    c = TW.Case(dev, **kw)
+    for gemm in (0, 1):
+        for skip in (-1, 0):
+            c.rig.gm.set_option(N.SBO_OPT_WHATIF_GEMM, gemm)
+            c.rig.gm.set_option(N.SBO_OPT_TILE_SKIP, skip)
+            for p in TW.PS:
+                for device in (False, True):
+                    put(f"whatif_{{shape}}_p{{p}}_gemm{{gemm}}_skip{{skip}}_{{'dev' if device else 'host'}}",
+                        c.call(p, device=device, cov=True, lo_new=True))
+    c.rig.gm.close()
+# evidence
+def evidence(name, gm):
+    for budget in (20, 0):
+        gm.set_option(N.SBO_OPT_EVIDENCE_BUDGET, budget)
+        st, info, mean, var = TE.call(gm)
+        assert st == 0
+        put(f"evidence_{{name}}_budget{{budget}}_host", TE.as_dict(info, mean, var))
+        dm, dv = (torch.full((gm.n,), float("nan"), dtype=torch.float64, device=dev) for _ in range(2))
+        st, info, _, _ = TE.call(gm, flags=N.SBO_DEVICE_PTRS, mean=dm, var=dv)
+        assert st == 0
+        torch.cuda.synchronize()
+        put(f"evidence_{{name}}_budget{{budget}}_dev", TE.as_dict(info, dm.cpu().numpy(), dv.cpu().numpy()))
+for name, (n, xr, yr) in TE.CASES.items():
+    x, y, obs = EM.case_data(n, xr, yr, TE.ELL, TE.HYPER.noise_level)
+    gm = TerrainMapper(0, TE.HYPER)
+    gm.fit(x, y, obs)
+    evidence(name, gm)
+    gm.close()
+x, y, obs = EM.case_data(1027, (0.0, 12 * TE.ELL), (0.0, 12 * TE.ELL), TE.ELL, TE.HYPER.noise_level, seed=5)
+gm = TerrainMapper(0, TE.HYPER)
+gm.fit(x[:1000], y[:1000], obs[:1000])
+gm.append(x[1000:], y[1000:], obs[1000:])      # 1000 -> 1027: across the k-tile boundary at 1024
+evidence("append1027", gm)
+gm.close()
+np.savez({path!r}, **out)
+print("ok", N.LIB_PATH, len(out), "arrays")
+'''
+
 
 def run(lib, configs, path, child=CHILD):
     env = dict(os.environ, SBO_LIB=os.path.abspath(lib))
@@ -183,9 +264,12 @@ def main():
                    help="the factorization's option matrix and the append paths instead of the ticks")
     p.add_argument("--inverse-matrix", action="store_true",
                    help="the f64 inverse's option matrix and the append paths instead of the ticks")
+    p.add_argument("--readers-matrix", action="store_true",
+                   help="the streaming update, sbo_whatif and sbo_evidence at their tests' shapes instead of the ticks")
     a = p.parse_args()
-    child = FACTOR_CHILD if a.factor_matrix else INVERSE_CHILD if a.inverse_matrix else CHILD
-    a.factor_matrix |= a.inverse_matrix      # (reported alike)
+    child = FACTOR_CHILD if a.factor_matrix else INVERSE_CHILD if a.inverse_matrix else \
+        READERS_CHILD if a.readers_matrix else CHILD
+    a.factor_matrix |= a.inverse_matrix | a.readers_matrix      # (reported alike)
     A = run(a.lib_a, a.configs, os.environ.get("CMP_OUT", "/tmp") + "/cmp_a.npz", child)
     B = run(a.lib_b, a.configs, os.environ.get("CMP_OUT", "/tmp") + "/cmp_b.npz", child)
     same = sorted(A) == sorted(B)

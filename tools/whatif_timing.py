@@ -15,8 +15,9 @@ candidates uniform over the data box: the weights' time (fill, the two
 triangular products, the candidate sums; with SBO_OPT_WHATIF_GEMM 0 dtrmm and
 1 dgemm) and the sweep's time (whatif_kernel alone), both from sbo_profile's
 events, the tiles kept and the cutoff L.  Medians over the repetitions after
-one warm-up repetition.  predict_update.hip is the parent commit's file,
-unchanged, so the yardstick is the parent's kernel.  The update and the sweep
+one warm-up repetition.  Both kernels run the one k-tile walk of
+csrc/kstar_walk.hpp, so the yardstick times the same loop over another left
+operand; for a kernel of another build, run this tool under SBO_LIB.  The update and the sweep
 at p = 64 contract the same m x n_kept x 64 products; the update's cutoff
 spends 2^-SBO_OPT_STREAM_SHARE of the skip budget, the what-if's all of it, so
 their kept tiles differ: both are printed, the ratio per kept tile too, and
