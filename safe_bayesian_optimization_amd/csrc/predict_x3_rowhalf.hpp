@@ -7,11 +7,15 @@
 // of 16 KiB, each plane eight row blocks x two k halves of one 1 KiB
 // lane-fragment piece.  A step is (tile, row half): every row block's MFMA
 // chain starts from zero, runs over k half 0 and then k half 1 in the level's
-// product order, and is added into the f32 outer sum a few pieces later --
-// the chains of a step end inside it, so only a short window of them is live
-// and no chain register survives a step.  Per 16 x 16 block this is the
-// sequence of MFMAs of the k-half stages it replaces (chain over k half 0,
-// continued over k half 1), so the results are bitwise the same.
+// product order and ends inside its step.  The eight finished chains of a
+// step stay in registers (fin[R]); the R = 0 step hands its eight across the
+// barrier to the R = 1 step, and one tile end (x3_tile_end) after the R = 1
+// body adds all sixteen into the f32 outer sums, one add per block per tile.
+// (The compiler sank the adds there from wherever the source placed them; the
+// source now says so, and spends 32 packed adds on them instead of 64.)  Per
+// 16 x 16 block this is the sequence of MFMAs of the k-half stages it
+// replaces (chain over k half 0, continued over k half 1) and the same one
+// add, so the results are bitwise the same.
 //
 // K* is built once per tile for all 64 k (kb[2]: one set of pieces per k
 // half) and serves both row-half steps; the next tile's K* and its mean terms
@@ -35,6 +39,18 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+// The translation units of this kernel are built without packed f32 VALU
+// (v_pk_* beside bf16 MFMAs costs more issue cycles than the scalar pair).
+// The kernel turns it on again for itself, for the tile end alone: the step
+// bodies hold no vector-typed f32 arithmetic and the units are built without
+// SLP vectorisation, so nothing between a step's first and last MFMA is
+// packed.  (A device-only attribute: the host pass does not know the feature.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SBO_X3_PACKED_F32 __attribute__((target("packed-fp32-ops")))
+#else
+#define SBO_X3_PACKED_F32
+#endif
 
 constexpr int kXH = 32;                  // k per K* piece set (a k half)
 constexpr int kXPlane = (kBM / 2) * kBK * 2;  // one bf16 plane of a row half: 16 KiB
@@ -118,10 +134,8 @@ __device__ __forceinline__ float kstar1(float xk, float yk, float xq, float yq, 
 // u = 4i, 4i+1, split at 4i+2, mean terms at 4i+3; the next pair's
 // coordinates are read at 4i+1).
 //   A row block's chain starts from zero at h = 0, continues over h = 1 and
-//   is added into outer[8R + rb] at piece 2 rb + D (D = 3 / 5 / 9 at six /
-//   three / one product(s): 6 / 9 / 7 MFMAs after its last one, off the
-//   MFMA's result latency), the last blocks after the loop; the chains
-//   (acc) live only from their first piece to that add.
+//   is left in fin[rb]: the step adds nothing into the outer sums (the tile
+//   end does, x3_tile_end), so all eight chains are live at its end.
 //   LV: 0 all six products, 1 the three largest (a1 kh + a0 km + a0 kh), 2 a0
 //   kh alone; the A planes a level leaves out are not read from LDS, and A
 //   fragments are read AH = 1 / 2 / 4 pieces ahead so the LDS latency stays
@@ -136,7 +150,7 @@ __device__ __forceinline__ float kstar1(float xk, float yk, float xq, float yq, 
 // 2 NS pieces of the planes its level reads and no others.
 template <int R, int LV, int NS, bool MEAN>
 __device__ __forceinline__ void x3_step(const lds_char *pa, const lds_char *pcn, float xq, float yq, int g, float cexp,
-                                        const KPieces (&kb)[2], f32x4 (&outer)[16], KPieces &nx, double &mu,
+                                        const KPieces (&kb)[2], f32x4 (&fin)[8], KPieces &nx, double &mu,
                                         uint32_t voff, const char *asrc, uint32_t adst) {
     // the pieces the next tile's level does not read: no value to keep alive
     if constexpr (NS < 3) nx.l = __builtin_nondeterministic_value(nx.l);
@@ -144,10 +158,8 @@ __device__ __forceinline__ void x3_step(const lds_char *pa, const lds_char *pcn,
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     constexpr bool P1 = LV <= 1, P2 = LV == 0;  // planes a1, a2 in use
     constexpr int NPROD = LV == 0 ? 6 : (LV == 1 ? 3 : 1);
-    constexpr int D = LV == 0 ? 3 : (LV == 1 ? 5 : 9);
     constexpr int AH = LV == 2 ? 4 : (LV == 1 ? 2 : 1);
     u32x4 f0[16], f1[16], f2[16];
-    f32x4 acc[8];
 #pragma unroll
     for (int r = 0; r < AH; ++r) {
         f0[r] = lds_b128(pa + r * 1024);
@@ -207,9 +219,7 @@ __device__ __forceinline__ void x3_step(const lds_char *pa, const lds_char *pcn,
             }
         }
         if (u >= 1 && u <= 2 * NS) dma16(voff, asrc + (u - 1) * kStride, adst + (u - 1) * kStride);
-        // the finished chain of block (u - D) / 2
-        if (u >= D && ((u - D) & 1) == 0) outer[8 * R + (u - D) / 2] += acc[(u - D) / 2];
-        f32x4 v = h == 0 ? zero : acc[rb];
+        f32x4 v = h == 0 ? zero : fin[rb];
         if constexpr (P2) {
             v = mfma(a2, kb[h].h, v);
             v = mfma(a1, kb[h].m, v);
@@ -220,7 +230,7 @@ __device__ __forceinline__ void x3_step(const lds_char *pa, const lds_char *pcn,
             v = mfma(a0, kb[h].m, v);
         }
         v = mfma(a0, kb[h].h, v);
-        acc[rb] = v;
+        fin[rb] = v;
         // interleave: each MFMA followed by two VALU and one LDS read, so the
         // vector work issues in the matrix pipe's shadow (a bf16 MFMA holds
         // the SIMD's issue for 8 of its 16 cycles)
@@ -232,8 +242,21 @@ __device__ __forceinline__ void x3_step(const lds_char *pa, const lds_char *pcn,
         }
         __builtin_amdgcn_sched_barrier(0);
     }
+}
+
+// The tile end, once per tile after the R = 1 body: every block's one f32 add
+// of the tile, outer[8 R + rb] += fin[R][rb], R = 0's blocks first.  Written
+// on the f32x2 halves, so that with packed f32 enabled for the kernel
+// (SBO_X3_PACKED_F32) the 64 adds are 32 v_pk_add_f32: an IEEE add per
+// element, the same bits.  No MFMA of this wave runs beside them.
+__device__ __forceinline__ void x3_tile_end(f32x4 (&outer)[16], const f32x4 (&fin)[2][8]) {
 #pragma unroll
-    for (int rb = (16 - D) / 2 + 1; rb < 8; ++rb) outer[8 * R + rb] += acc[rb];
+    for (int R = 0; R < 2; ++R)
+#pragma unroll
+        for (int rb = 0; rb < 8; ++rb) {
+            outer[8 * R + rb].lo += fin[R][rb].lo;
+            outer[8 * R + rb].hi += fin[R][rb].hi;
+        }
 }
 
 // K* pieces of one k half directly (the prologue's first tile)
@@ -264,7 +287,7 @@ constexpr int kFirst = 2, kLast = 4, kValid = 8;  // first / last tile of its it
 
 // The persistent sweep: eight waves (two per SIMD), wave w owns queries
 // 16w .. 16w+15; every wave loads an eighth of each stage's A planes.
-__global__ __launch_bounds__(512, 1) void predict_x3_kernel(
+__global__ __launch_bounds__(512, 1) SBO_X3_PACKED_F32 void predict_x3_kernel(
     const char *__restrict__ ax3, const float *__restrict__ kc3, const int4 *__restrict__ desc,
     const int4 *__restrict__ rec, const int *__restrict__ seg, int P, int n_items, int nI, uint32_t a_max,
     const float *__restrict__ qx, const float *__restrict__ qy, int64_t m, int64_t ldp, float cexp, float m0,
@@ -382,6 +405,7 @@ __global__ __launch_bounds__(512, 1) void predict_x3_kernel(
     f32x4 outer[16];
 #pragma unroll
     for (int rb = 0; rb < 16; ++rb) outer[rb] = f32x4{};
+    f32x4 fin[2][8];
     double mu = 0.0;
     KPieces kb[2], nx[2];
 #pragma unroll
@@ -461,7 +485,7 @@ __global__ __launch_bounds__(512, 1) void predict_x3_kernel(
         // uniform: one branch here, none inside the body's MFMA region)
         const int ns = nvalid ? 3 - t1.lv : 1;
 #define SBO_X3R_BODY(LV_, NS_, MN_)                                                                              \
-    x3_step<R, LV_, NS_, MN_>(pa, pcn, xq, yq, g, cexp, kb, outer, nx[R], mu, voff, a_src, a_dst)
+    x3_step<R, LV_, NS_, MN_>(pa, pcn, xq, yq, g, cexp, kb, fin[R], nx[R], mu, voff, a_src, a_dst)
 #define SBO_X3R_BY_NEXT(LV_)                                                                                     \
     do {                                                                                                        \
         if (mn) {                                                                                               \
@@ -479,6 +503,7 @@ __global__ __launch_bounds__(512, 1) void predict_x3_kernel(
         else SBO_X3R_BY_NEXT(0);
 #undef SBO_X3R_BY_NEXT
 #undef SBO_X3R_BODY
+        if (R == 1) x3_tile_end(outer, fin);
         if (R == 1 && (t0.flags & kLast)) {
             // item done: column sums of V^2 over its rows (lanes l, l+16, l+32,
             // l+48 hold four row quarters of column l&15 of every block)
@@ -567,6 +592,7 @@ __global__ __launch_bounds__(256) void pack_x3_kernel(const float *__restrict__ 
 }
 
 #undef SBO_X3R_PIN
+#undef SBO_X3_PACKED_F32
 
 }  // namespace
 
