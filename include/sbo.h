@@ -355,6 +355,96 @@ SBO_API sbo_status sbo_debug_whatif_cutoff(int64_t p, const double *w_l1, const 
                                            double beta, double sf2, double budget_var, double budget_mean,
                                            int32_t *cutoff_log2, double *err_cov);
 
+/* Posterior sample paths on the kept grid: `samples` joint draws of the GP
+ * posterior at every kept query, each draw's maximiser over the safe set
+ * (Thompson sampling's key) and the size of its region above f_min.  Nothing
+ * is appended.  The method is pathwise conditioning (Matheron's rule; Wilson
+ * et al., ICML 2020): a prior path from F random Fourier features, and the
+ * data-dependent correction exactly, through the fit's f64 inverse.  With
+ * s = noise_level + jitter, X = L^-1 (f64), the kept f64 mean mu(q):
+ *   g_j(x)  = sf / sqrt(F) sum_{f < F} [ a_fj cos(2 pi t_f(x)) + b_fj sin(2 pi t_f(x)) ]
+ *   t_f(x)  = w_f . (x - c) in turns,  w_f = nu_f / (2 pi l),  nu_f ~ N(0, I2),
+ *             c the centre of the training bounding box (sbo_get_bounds)
+ *   t_j     = g_j(train) + sqrt(s) eps_j          (n)        a, b, eps ~ N(0, 1)
+ *   u_j     = X t_j,  w_j = X^T u_j  (= K^-1 t_j)
+ *   path_j(q) = mu(q) + g_j(q) - k*(q) . w_j      for every kept query q
+ * E[path] = mu exactly; the covariance is the posterior's up to the feature
+ * approximation of the prior kernel (pointwise standard error about
+ * 1 / sqrt(2 F) of sf2), which is measured, not bounded: kernel_err is the
+ * maximum over d = (a, +-b) 4 l / 32, a, b = 0 .. 32, of
+ * |k^(d) / sf2 - exp(-|d|^2 / 2 l^2)|, k^(d) / sf2 = (1 / F) sum_f cos(2 pi w_f . d).
+ *
+ * The random numbers are part of the interface.  With normal(seed_t, e) =
+ * element e of the counter-based SplitMix64 / Box-Muller stream started at
+ * seed_t (uniform u_i = (output i + 1 of SplitMix64(seed_t) >> 11) 2^-53;
+ * normal e = sqrt(-2 log max(u_2e, 1e-300)) cos(2 pi u_2e+1)), sample
+ * J = first + j uses
+ *   nu_f       = (normal(seed, 2 f), normal(seed, 2 f + 1))
+ *   a_fJ, b_fJ = normal(seed + 1, J 2 F + f), normal(seed + 1, J 2 F + F + f)
+ *   eps_J at the training point with caller index i = normal(seed + 2, J 2^24 + i)
+ * (seeds mod 2^64).  So a path depends on (seed, J, F, the fit) only: not on
+ * `samples` or how a range of J is cut into calls, not on
+ * SBO_OPT_SPATIAL_ORDER, and not on the rank -- every rank of a sharded grid
+ * draws the same global path on its rows, and the per-sample keys combine with
+ * sbo_keys_reduce.
+ *
+ * keys: `samples` keys; keys[j].score = path_j at its maximiser over the safe
+ * queries, idx = index_offset + the caller's index of it (the lowest index on
+ * ties; a NaN never wins; idx -1 and score 0 when nothing is safe).  safe(q)
+ * is recomputed from the kept state exactly as sbo_tick_stream forms its
+ * `safe` output (for the same beta and f_min); f_min = -inf gives the
+ * unconstrained maximiser.  count_above: samples counts #{q : path_j(q) >
+ * f_min}, or NULL.  paths: samples x m row-major in the caller's query order
+ * (m = the kept posterior's), or NULL.  Host pointers; device pointers (every
+ * array) with SBO_DEVICE_PTRS.  Synchronous (|w_j|_1 is read back for the
+ * cutoff; SBO_ASYNC is ignored).  info may be NULL; the caller sets
+ * info->struct_size to sizeof(sbo_sample_info) and the library writes no more
+ * than that many bytes.
+ *
+ * The sweep's K* cutoff is sbo_whatif's: dropping entries below 2^-L moves
+ * path_j(q) by at most e_j = sf2 2^-L |w_j|_1 (rigorous).  SBO_OPT_TILE_SKIP 0:
+ * dense; a fixed L spends its own bound; L >= 150 drops only exact zeros
+ * (bitwise the dense result); -1 (auto): the smallest L in [16, 149] with
+ * max_j e_j <= budget_mean (sbo_get_stream's; nothing accumulates), else 150.
+ * All floating-point sums run in a fixed order, the counts are integer sums
+ * and the keys' order is total: two calls agree bitwise.
+ *
+ * SBO_E_STATE exactly as sbo_whatif.  SBO_E_INVAL for samples outside
+ * [1, 1024], first < 0, first + samples > 2^20, features outside [1, 4096],
+ * NULL keys, or a fit of more than 2^24 points (eps's counter).  Alters no fitted or kept state; its workspace is freed by
+ * sbo_trim. */
+typedef struct sbo_sample_info {
+    uint32_t struct_size;            /* caller sets; no more than this many bytes are written */
+    int32_t  cutoff_log2;            /* L (0: dense) */
+    int64_t  samples, first, m, n, features;
+    int64_t  tiles_total, tiles_kept;   /* (query block, k-tile) pairs */
+    double   err_path;               /* rigorous bound on |path error| from the cutoff: max_j sf2 2^-L |w_j|_1 */
+    double   kernel_err;             /* measured: max |k^(d)/sf2 - exp(-|d|^2 / 2 l^2)| on the lattice above */
+    double   w_l1_max;               /* max_j |w_j|_1 */
+    double   ms;                     /* device time of the call's kernels */
+} sbo_sample_info;
+SBO_API sbo_status sbo_sample(sbo_ctx *ctx, uint64_t seed, int64_t first, int64_t samples, int64_t features,
+                              double beta, double f_min, int64_t index_offset,
+                              sbo_key *keys,          /* samples: argmax of path_j over the safe set */
+                              int64_t *count_above,   /* samples: #{q : path_j(q) > f_min}; may be NULL */
+                              double *paths,          /* samples x m row-major, caller's query order; may be NULL */
+                              sbo_sample_info *info, uint32_t flags);
+
+/* Test accessor: sbo_sample's auto cutoff alone, on the host (no context, no
+ * device).  w_l1: per sample |w_j|_1.  *cutoff_log2 = the smallest L in
+ * [16, 149] with sf2 2^-L max_j |w_j|_1 <= budget_mean, 150 if none is, 0
+ * (dense) when budget_mean <= 0; *err_path = sf2 2^-L max_j |w_j|_1 (0 when
+ * dense). */
+SBO_API sbo_status sbo_debug_sample_cutoff(int64_t samples, const double *w_l1, double sf2, double budget_mean,
+                                           int32_t *cutoff_log2, double *err_path);
+
+/* Test accessor: the standard normals the device generates for sbo_sample, to
+ * host buffers: nu (2 features), ab (samples x 2 features row-major: a then b
+ * of each sample) and eps (samples x n row-major, the caller's training
+ * order).  Needs a fitted context. */
+SBO_API sbo_status sbo_debug_sample_draws(sbo_ctx *ctx, uint64_t seed, int64_t first, int64_t samples,
+                                          int64_t features, double *nu, double *ab, double *eps);
+
 /* Sweep work of each query under the current fit: builds the tick's tile
  * plan for these queries (no sweep) and writes cost[i] = the k-tiles its
  * 128-query block multiplies, summed over row blocks and weighted by their
@@ -791,7 +881,8 @@ SBO_API sbo_status sbo_get_inverse_check(const sbo_ctx *ctx, sbo_inv_check *out)
  * calls for speed (the recursive inverse's scratch and the int8-sliced GEMM's
  * packed operands -- about 2.1 GB at N = 16384, 8.5 GB at 32768 -- the inverse
  * check's, the append re-sort's staging copy, sbo_evidence's column norms and
- * work items, sbo_whatif's candidate weights and the precise sweep's K* table, up to SBO_OPT_TABLE_MB); they
+ * work items, sbo_whatif's candidate weights, sbo_sample's weights and keys
+ * and the precise sweep's K* table, up to SBO_OPT_TABLE_MB); they
  * are allocated again on the next call that needs them.  The fitted state
  * (factor, inverse, operands) stays, and so does sbo_tick_stream's kept
  * posterior (sbo_stream_reset frees that).  Waits for the context's streams. */

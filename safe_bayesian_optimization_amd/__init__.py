@@ -4,7 +4,8 @@ Layout:
   csrc/       HIP kernels for gfx950, host orchestration (rocSOLVER) and the
               C ABI of libsbo.so (declared in include/sbo.h)
   _native.py  ctypes binding (no fallback: missing library -> error)
-  gp.py       TerrainMapper -- the GP mapper behind get_terrain_map_with_uncertainty
+  gp.py       TerrainMapper -- the GP mapper behind get_terrain_map_with_uncertainty,
+              its readers of the kept posterior (whatif, sample, thompson_subgoal)
   node.py     OptimizerCore -- mirror of OptimizerNode's ComputeSets /
               FindSafetyContourIndices / GetNextSubgoal
   dist.py     M-row sharding + the cross-rank argmax key reduction

@@ -38,6 +38,7 @@ EXPORTS = (
     "sbo_tick_stream", "sbo_get_stream", "sbo_stream_reset", "sbo_debug_stream_state",
     "sbo_evidence", "sbo_debug_evidence_pairs", "sbo_debug_inverse_plan",
     "sbo_whatif", "sbo_debug_whatif_cutoff",
+    "sbo_sample", "sbo_debug_sample_cutoff", "sbo_debug_sample_draws",
 )
 # sbo_stream_reason (include/sbo.h, sbo_get_stream)
 STREAM_REASONS = ("FIRST", "UPDATED", "QUERIES_CHANGED", "REFIT", "NO_INVERSE", "ROWS_OVER_CAP", "BUDGET", "RESET")
@@ -142,6 +143,13 @@ class sbo_whatif_info(ctypes.Structure):
                 ("best_gain", ctypes.c_int64), ("ms", ctypes.c_double)]
 
 
+class sbo_sample_info(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("cutoff_log2", ctypes.c_int32), ("samples", ctypes.c_int64),
+                ("first", ctypes.c_int64), ("m", ctypes.c_int64), ("n", ctypes.c_int64), ("features", ctypes.c_int64),
+                ("tiles_total", ctypes.c_int64), ("tiles_kept", ctypes.c_int64), ("err_path", ctypes.c_double),
+                ("kernel_err", ctypes.c_double), ("w_l1_max", ctypes.c_double), ("ms", ctypes.c_double)]
+
+
 _lib = None
 
 
@@ -208,6 +216,13 @@ def lib():
     L.sbo_debug_whatif_cutoff.argtypes = [i64, vp, vp, dbl, dbl, dbl, dbl, dbl, ctypes.POINTER(ctypes.c_int32),
                                           ctypes.POINTER(dbl)]
     L.sbo_debug_whatif_cutoff.restype = st
+    u64 = ctypes.c_uint64
+    L.sbo_sample.argtypes = [vp, u64, i64, i64, i64, dbl, dbl, i64, vp, vp, vp, ctypes.POINTER(sbo_sample_info), u32]
+    L.sbo_sample.restype = st
+    L.sbo_debug_sample_cutoff.argtypes = [i64, vp, dbl, dbl, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(dbl)]
+    L.sbo_debug_sample_cutoff.restype = st
+    L.sbo_debug_sample_draws.argtypes = [vp, u64, i64, i64, i64, vp, vp, vp]
+    L.sbo_debug_sample_draws.restype = st
     L.sbo_query_cost.argtypes = [vp, vp, vp, i64, vp, u32]
     L.sbo_query_cost.restype = st
     L.sbo_key_combine.argtypes = [sbo_key, sbo_key]

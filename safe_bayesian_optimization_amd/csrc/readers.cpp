@@ -1,6 +1,7 @@
-// readers.cpp -- sbo_evidence (csrc/evidence.hip) and sbo_whatif (csrc/whatif.hip) with their debug entry points:
-// the readers of the fitted and the kept state.  Each call is a sequence of stages over a plan (readers.hpp): checks
-// and reservation, a device phase with one readback, the host's choice from it, a second device phase, the copy-out.
+// readers.cpp -- sbo_evidence (csrc/evidence.hip), sbo_whatif (csrc/whatif.hip) and sbo_sample (csrc/sample.hip) with
+// their debug entry points: the readers of the fitted and the kept state.  Each call is a sequence of stages over a
+// plan (readers.hpp): checks and reservation, a device phase with one readback, the host's choice from it, a second
+// device phase, the copy-out.
 #include "readers.hpp"
 
 #include <algorithm>
@@ -186,6 +187,42 @@ static_assert(sizeof(sbo_whatif_info) == 80, "sbo_whatif_info: the bindings mirr
 
 namespace {
 
+// What sbo_whatif and sbo_sample (`who`) read: a kept posterior of the current epoch that has seen every fitted row,
+// and the fit's f64 inverse and z.
+sbo_status kept_reader_state(sbo_ctx *ctx, const std::string &who) {
+    const int64_t n = ctx->n;
+    const sbo::StreamKeep &k = ctx->keep;
+    SBO_CHECK(ctx->fitted && n > 0, SBO_E_STATE, who + ": call sbo_fit first");
+    SBO_CHECK(k.valid, SBO_E_STATE, who + ": no kept posterior (call sbo_tick_stream first)");
+    SBO_CHECK(k.epoch == ctx->fit_epoch && k.n_map == n, SBO_E_STATE,
+              who + ": the kept posterior has not seen every fitted row (call sbo_tick_stream again)");
+    SBO_CHECK(fit_state_complete(ctx, n), SBO_E_STATE,
+              who + ": needs the fit's f64 inverse and z (not an imported state, SBO_OPT_INVERSE_BITS 64)");
+    return SBO_OK;
+}
+
+// U^T = B^T X^T and W^T = U^T X for `rows` right-hand sides stored as rows (rows x n column-major each at leading
+// dimension ldb; Wt may be Bt): W = K^-1 B by two triangular products on the f64 inverse X.
+sbo_status inverse_products(sbo_ctx *ctx, const double *Bt, double *Ut, double *Wt, int64_t rows, int64_t ldb,
+                            int64_t n_) {
+    const double *X = ctx->Linv.as<double>();
+    const double one = 1.0, zero = 0.0;
+    const rocblas_int pp = (rocblas_int)rows, lb = (rocblas_int)ldb, n = (rocblas_int)n_, ld = (rocblas_int)ctx->cap;
+    SBO_BLAS(rocblas_set_pointer_mode(ctx->blas, rocblas_pointer_mode_host));
+    if (ctx->whatif_gemm) {   // (the inverse's strict upper half is stored as zeros)
+        SBO_BLAS(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_transpose, pp, n, n, &one, Bt, lb, X,
+                               ld, &zero, Ut, lb));
+        SBO_BLAS(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_none, pp, n, n, &one, Ut, lb, X, ld,
+                               &zero, Wt, lb));
+    } else {
+        SBO_BLAS(rocblas_dtrmm(ctx->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_transpose,
+                               rocblas_diagonal_non_unit, pp, n, &one, X, ld, Bt, lb, Ut, lb));
+        SBO_BLAS(rocblas_dtrmm(ctx->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_none,
+                               rocblas_diagonal_non_unit, pp, n, &one, X, ld, Ut, lb, Wt, lb));
+    }
+    return SBO_OK;
+}
+
 // Stage 1: the checks, wiws reserved and carved, a host caller's candidates staged.
 sbo_status whatif_plan(sbo_ctx *ctx, const float *cx, const float *cy, const sbo_whatif_info *info, uint32_t flags,
                        WhatifPlan &w) {
@@ -194,13 +231,8 @@ sbo_status whatif_plan(sbo_ctx *ctx, const float *cx, const float *cy, const sbo
     SBO_CHECK(p > 0 && p <= 1024, SBO_E_INVAL, "sbo_whatif: p must be in [1, 1024]");
     SBO_CHECK(std::isfinite(w.beta) && !std::isnan(w.f_min), SBO_E_INVAL, "sbo_whatif: beta/f_min must be finite");
     SBO_CHECK(!info || info->struct_size >= sizeof(uint32_t), SBO_E_INVAL, "sbo_whatif: struct_size not set");
+    if (sbo_status st = kept_reader_state(ctx, "sbo_whatif")) return st;
     const sbo::StreamKeep &k = ctx->keep;
-    SBO_CHECK(ctx->fitted && n > 0, SBO_E_STATE, "sbo_whatif: call sbo_fit first");
-    SBO_CHECK(k.valid, SBO_E_STATE, "sbo_whatif: no kept posterior (call sbo_tick_stream first)");
-    SBO_CHECK(k.epoch == ctx->fit_epoch && k.n_map == n, SBO_E_STATE,
-              "sbo_whatif: the kept posterior has not seen every fitted row (call sbo_tick_stream again)");
-    SBO_CHECK(fit_state_complete(ctx, n), SBO_E_STATE,
-              "sbo_whatif: needs the fit's f64 inverse and z (not an imported state, SBO_OPT_INVERSE_BITS 64)");
     SBO_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const int64_t pp = w.pp = sbo::round_up(p, 16);
@@ -234,26 +266,12 @@ sbo_status whatif_weights(sbo_ctx *ctx, const WhatifPlan &w, PhaseEvents &pe, st
                           std::vector<double> &hl1) {
     hipStream_t s = ctx->stream;
     const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f, noise = ctx->hyper.noise_level;   // (holds the jitter too)
-    const double *X = ctx->Linv.as<double>();
-    const double one = 1.0, zero = 0.0;
-    const rocblas_int pp = (rocblas_int)w.pp, n = (rocblas_int)w.n, ld = (rocblas_int)ctx->cap;
     SBO_HIP(pe.record(0));
     {
         Bracket br(ctx, ctx->ev_fill);
         SBO_HIP(sbo::launch_whatif_fill(s, ctx->x.as<float>(), ctx->y.as<float>(), w.n, w.cx, w.cy, w.p, w.pp,
                                         ctx->hyper.length_scale, sf2, w.Kt));
-        SBO_BLAS(rocblas_set_pointer_mode(ctx->blas, rocblas_pointer_mode_host));
-        if (ctx->whatif_gemm) {   // (the inverse's strict upper half is stored as zeros)
-            SBO_BLAS(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_transpose, pp, n, n, &one, w.Kt,
-                                   pp, X, ld, &zero, w.Ut, pp));
-            SBO_BLAS(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_none, pp, n, n, &one, w.Ut, pp,
-                                   X, ld, &zero, w.Wt, pp));
-        } else {
-            SBO_BLAS(rocblas_dtrmm(ctx->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_transpose,
-                                   rocblas_diagonal_non_unit, pp, n, &one, X, ld, w.Kt, pp, w.Ut, pp));
-            SBO_BLAS(rocblas_dtrmm(ctx->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_none,
-                                   rocblas_diagonal_non_unit, pp, n, &one, X, ld, w.Ut, pp, w.Wt, pp));
-        }
+        if (sbo_status st = inverse_products(ctx, w.Kt, w.Ut, w.Wt, w.pp, w.pp, w.n)) return st;
         SBO_HIP(sbo::launch_whatif_stats(s, w.Ut, w.Wt, w.p, w.pp, w.n, ctx->zvec.as<double>(), ctx->hyper.prior_mean,
                                          sf2, noise, w.beta, w.part, w.mu, w.var, w.l1, w.par));
     }
@@ -367,5 +385,223 @@ SBO_API sbo_status sbo_debug_whatif_cutoff(int64_t p, const double *w_l1, const 
     int L = 0;
     sbo::whatif_cutoff(p, w_l1, cand_var, s, beta, sf2, budget_var, budget_mean, &L, err_cov);
     *cutoff_log2 = L;
+    return SBO_OK;
+}
+
+// ------------------------------------------------------------ posterior sample paths
+// The draws (frequencies, feature weights, sqrt(s) eps), T^T += the prior paths at the training points, the weights
+// W = K^-1 T by the what-if's two triangular products, |w_j|_1 and the feature kernel's error, one readback (the host
+// chooses the cutoff from |w_j|_1), then the sweep over the kept posterior and the key reduction.  Reads the fitted
+// and the kept state only; smws is its own workspace.
+//
+// rocBLAS chooses a product's blocking, and with it the order of a row's sums, from the number of rows (measured at
+// n = 700: 17 + 133 rows in two calls against 150 in one differ in the last place).  A path must not depend on how a
+// range of samples is cut into calls, so T^T, U^T and W^T have kSampleChunk-row chunks (leading dimension pw, the
+// rows past the samples zero) and every product runs on one chunk: rocBLAS sees one shape, whatever `samples` is.
+constexpr int64_t kSampleChunk = 128;
+static_assert(sizeof(sbo_sample_info) == 96, "sbo_sample_info: the bindings mirror this layout");
+
+using sbo::SamplePlan;
+
+namespace {
+
+// The sizes every entry point of the sampler takes.
+sbo_status sample_sizes(sbo_ctx *ctx, int64_t first, int64_t samples, int64_t features, const std::string &who) {
+    SBO_CHECK(samples >= 1 && samples <= 1024, SBO_E_INVAL, who + ": samples must be in [1, 1024]");
+    SBO_CHECK(first >= 0 && first + samples <= ((int64_t)1 << 20), SBO_E_INVAL,
+              who + ": first must be >= 0 and first + samples <= 2^20");
+    SBO_CHECK(features >= 1 && features <= 4096, SBO_E_INVAL, who + ": features must be in [1, 4096]");
+    return SBO_OK;
+}
+
+// Stage 1: the checks, smws reserved and carved.
+sbo_status sample_plan(sbo_ctx *ctx, const sbo_sample_info *info, uint32_t flags, SamplePlan &p) {
+    SBO_CHECK(p.out_keys, SBO_E_INVAL, "sbo_sample: null keys");
+    if (sbo_status st = sample_sizes(ctx, p.first, p.S, p.F, "sbo_sample")) return st;
+    SBO_CHECK(std::isfinite(p.beta) && !std::isnan(p.f_min), SBO_E_INVAL, "sbo_sample: beta/f_min must be finite");
+    SBO_CHECK(!info || info->struct_size >= sizeof(uint32_t), SBO_E_INVAL, "sbo_sample: struct_size not set");
+    if (sbo_status st = kept_reader_state(ctx, "sbo_sample")) return st;
+    const int64_t n = p.n = ctx->n, S = p.S;
+    SBO_CHECK(n <= ((int64_t)1 << 24), SBO_E_INVAL, "sbo_sample: more than 2^24 training points");
+    SBO_HIP(hipSetDevice(ctx->device));
+    const sbo::StreamKeep &k = ctx->keep;
+    const int64_t pp = p.pp = sbo::round_up(S, 16), Fp = p.Fp = sbo::round_up(p.F, 4);
+    const int64_t pw = p.pw = sbo::round_up(S, kSampleChunk);
+    p.m = k.m;
+    p.nb = sbo::sample_blocks(k.ms);
+    p.host = !dev(flags);
+    p.mat = (size_t)S * (size_t)p.m;
+    p.cx0 = 0.5 * ((double)ctx->bbox[0] + (double)ctx->bbox[1]);
+    p.cy0 = 0.5 * ((double)ctx->bbox[2] + (double)ctx->bbox[3]);
+    const size_t pn = (size_t)pw * (size_t)n, pf = (size_t)pp * (size_t)(2 * Fp), pk = (size_t)S * (size_t)p.nb;
+    SBO_HIP(ctx->smws.reserve(2 * Carve::need(pn, 8) + Carve::need(pf, 8) + 2 * Carve::need(Fp, 8) + Carve::need(n, 8) +
+                              Carve::need(sbo::whatif_part_bytes(pw), 1) + Carve::need(S, 8) +
+                              Carve::need(2 * S + 2 * pw, 8) + Carve::need(S + 2, 8) + Carve::need(pk, sizeof(sbo_key)) +
+                              Carve::need(S, sizeof(sbo_key)) + (p.host && p.out_paths ? Carve::need(p.mat, 8) : 0)));
+    Carve cv(ctx->smws.as<void>());
+    p.Wt = p.Tt = cv.take<double>(pn), p.Ut = cv.take<double>(pn), p.Theta = cv.take<double>(pf);
+    p.wx = cv.take<double>(Fp), p.wy = cv.take<double>(Fp);
+    p.order = cv.take<int64_t>(n);
+    p.part = cv.take<double>(sbo::whatif_part_bytes(pw) / 8);
+    p.l1 = cv.take<double>(S), p.junk = cv.take<double>(2 * S + 2 * pw);
+    p.count = cv.take<unsigned long long>(S + 2), p.kept = p.count + S, p.kerr = p.kept + 1;
+    p.pkeys = cv.take<sbo_key>(pk), p.keys = cv.take<sbo_key>(S);
+    p.paths = p.out_paths;
+    if (p.host && p.out_paths) p.paths = cv.take<double>(p.mat);
+    return SBO_OK;
+}
+
+// Stage 2 (phase 1): the draws, T^T += g(train), U^T = T^T X^T, W^T = U^T X (over T^T), |w_j|_1 by the what-if's
+// chunked sums, the feature kernel's error; |w_j|_1 and the error read back.
+sbo_status sample_weights(sbo_ctx *ctx, const SamplePlan &p, PhaseEvents &pe, std::vector<double> &hl1,
+                          double &kernel_err) {
+    hipStream_t s = ctx->stream;
+    const sbo_hyper &h = ctx->hyper;   // (noise_level holds the jitter too)
+    SBO_HIP(hipMemcpyAsync(p.order, ctx->order.data(), sizeof(int64_t) * p.n, hipMemcpyHostToDevice, s));
+    SBO_HIP(hipMemsetAsync(p.kerr, 0, sizeof(unsigned long long), s));
+    SBO_HIP(pe.record(0));
+    {
+        Bracket br(ctx, ctx->ev_fill);
+        SBO_HIP(sbo::launch_sample_draw(s, p.seed, p.first, p.S, p.pp, p.pw, p.F, p.Fp, p.n, p.order, h.length_scale,
+                                        h.sigma_f, h.noise_level, p.wx, p.wy, p.Theta, p.Tt, nullptr, nullptr, nullptr));
+        SBO_HIP(sbo::launch_sample_train(s, p.Theta, p.pp, p.n, ctx->x.as<float>(), ctx->y.as<float>(), p.wx, p.wy,
+                                         p.Fp, p.cx0, p.cy0, p.Tt, p.pw));
+        for (int64_t r0 = 0; r0 < p.pw; r0 += kSampleChunk)
+            if (sbo_status st = inverse_products(ctx, p.Tt + r0, p.Ut + r0, p.Wt + r0, kSampleChunk, p.pw, p.n))
+                return st;
+        // (the candidates' u . z and |u|^2 of the what-if mean nothing here: junk)
+        double *jmu = p.junk, *jvar = jmu + p.S, *jpar = jvar + p.S;
+        SBO_HIP(sbo::launch_whatif_stats(s, p.Ut, p.Wt, p.S, p.pw, p.n, ctx->zvec.as<double>(), h.prior_mean,
+                                         h.sigma_f * h.sigma_f, h.noise_level, p.beta, p.part, jmu, jvar, p.l1, jpar));
+        SBO_HIP(sbo::launch_sample_kernel_err(s, p.wx, p.wy, p.F, h.length_scale, p.kerr));
+    }
+    SBO_HIP(pe.record(1));
+    unsigned long long bits = 0;
+    SBO_HIP(hipMemcpyAsync(hl1.data(), p.l1, sizeof(double) * p.S, hipMemcpyDeviceToHost, s));
+    SBO_HIP(hipMemcpyAsync(&bits, p.kerr, sizeof(bits), hipMemcpyDeviceToHost, s));
+    SBO_HIP(hipStreamSynchronize(s));
+    memcpy(&kernel_err, &bits, sizeof(double));
+    return SBO_OK;
+}
+
+// Stage 3: the cutoff -- the context's fixed one, or the smallest L within the sweep's mean budget -- and its bound
+// on |path error|.
+int sample_choose_cutoff(const sbo_ctx *ctx, const std::vector<double> &hl1, double &err_path) {
+    const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
+    int L = ctx->skip_log2;
+    if (L < 0) {
+        double bvar = 0.0, bmean = 0.0;
+        stream_budget(ctx, bvar, bmean);
+        sbo::sample_cutoff((int64_t)hl1.size(), hl1.data(), sf2, bmean, &L, &err_path);
+    } else {
+        err_path = sbo::whatif_err_cov(L, sf2, *std::max_element(hl1.begin(), hl1.end()));
+    }
+    return L;
+}
+
+// Stage 4 (phase 2): the sweep over the kept posterior at cutoff L, then the samples' keys.
+sbo_status sample_sweep(sbo_ctx *ctx, const SamplePlan &p, PhaseEvents &pe, int L) {
+    hipStream_t s = ctx->stream;
+    const sbo::StreamKeep &k = ctx->keep;
+    SBO_HIP(hipMemsetAsync(p.count, 0, sizeof(unsigned long long) * (size_t)(p.S + 1), s));
+    SBO_HIP(pe.record(2));
+    {
+        Bracket br(ctx, ctx->ev_predict);
+        SBO_HIP(sbo::launch_sample(s, p.Wt, p.pw, p.Theta, p.pp, p.S, p.n, ctx->x.as<float>(), ctx->y.as<float>(),
+                                   ctx->kbox.as<float4>(), k.qbox.as<float4>(), k.qx.as<float>(), k.qy.as<float>(),
+                                   k.perm.as<int32_t>(), k.ms, p.m, ctx->hyper.length_scale,
+                                   ctx->hyper.sigma_f * ctx->hyper.sigma_f, L, k.mu64.as<double>(),
+                                   k.var64.as<double>(), p.wx, p.wy, p.Fp, p.cx0, p.cy0, p.beta, p.f_min,
+                                   p.index_offset, p.count, p.paths, p.pkeys, p.keys, p.kept));
+    }
+    SBO_HIP(pe.record(3));
+    return SBO_OK;
+}
+
+// Stage 5: the outputs to the caller; with `info` wanted the sizes, the tile counts and the phases' time into r.
+sbo_status sample_read_out(sbo_ctx *ctx, const SamplePlan &p, PhaseEvents &pe, bool info, sbo_sample_info &r) {
+    hipStream_t s = ctx->stream;
+    const hipMemcpyKind out = p.host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    unsigned long long kept = 0;
+    SBO_HIP(hipMemcpyAsync(&kept, p.kept, sizeof(kept), hipMemcpyDeviceToHost, s));
+    SBO_HIP(hipMemcpyAsync(p.out_keys, p.keys, sizeof(sbo_key) * (size_t)p.S, out, s));
+    if (p.out_count) SBO_HIP(hipMemcpyAsync(p.out_count, p.count, sizeof(int64_t) * (size_t)p.S, out, s));
+    if (p.host && p.out_paths) SBO_HIP(hipMemcpyAsync(p.out_paths, p.paths, sizeof(double) * p.mat, out, s));
+    SBO_HIP(hipStreamSynchronize(s));
+    if (!info) return SBO_OK;
+    r.samples = p.S, r.first = p.first, r.m = p.m, r.n = p.n, r.features = p.F;
+    r.tiles_total = kept_tiles_total(ctx->keep.ms, p.n);
+    r.tiles_kept = (int64_t)kept;
+    SBO_HIP(pe.elapsed());
+    r.ms = pe.ms;
+    return SBO_OK;
+}
+
+sbo_status sample_run(sbo_ctx *ctx, SamplePlan &p, sbo_sample_info *info, uint32_t flags) {
+    if (sbo_status st = sample_plan(ctx, info, flags, p)) return st;
+    PhaseEvents pe(ctx);
+    SBO_CHECK(pe.ok(), SBO_E_DEVICE, "sbo_sample: hipEventCreate failed");
+    std::vector<double> hl1((size_t)p.S);
+    sbo_sample_info r{};
+    if (sbo_status st = sample_weights(ctx, p, pe, hl1, r.kernel_err)) return st;
+    r.w_l1_max = *std::max_element(hl1.begin(), hl1.end());
+    r.cutoff_log2 = sample_choose_cutoff(ctx, hl1, r.err_path);
+    if (sbo_status st = sample_sweep(ctx, p, pe, r.cutoff_log2)) return st;
+    if (sbo_status st = sample_read_out(ctx, p, pe, info != nullptr, r)) return st;
+    if (info) copy_info(info, r);
+    return SBO_OK;
+}
+
+}  // namespace
+
+SBO_API sbo_status sbo_sample(sbo_ctx *ctx, uint64_t seed, int64_t first, int64_t samples, int64_t features,
+                              double beta, double f_min, int64_t index_offset, sbo_key *keys, int64_t *count_above,
+                              double *paths, sbo_sample_info *info, uint32_t flags) {
+    if (!ctx) return SBO_E_INVAL;
+    try {
+        SamplePlan p;
+        p.seed = seed, p.first = first, p.S = samples, p.F = features, p.beta = beta, p.f_min = f_min;
+        p.index_offset = index_offset;
+        p.out_keys = keys, p.out_count = count_above, p.out_paths = paths;
+        return sample_run(ctx, p, info, flags);
+    } catch (const std::bad_alloc &) {   // (the host copy of the samples' sums)
+        ctx->err = "sbo_sample: host allocation failed";
+        return SBO_E_OOM;
+    }
+}
+
+SBO_API sbo_status sbo_debug_sample_cutoff(int64_t samples, const double *w_l1, double sf2, double budget_mean,
+                                           int32_t *cutoff_log2, double *err_path) {
+    if (samples <= 0 || !w_l1 || !cutoff_log2 || !err_path || !(sf2 > 0.0)) return SBO_E_INVAL;
+    int L = 0;
+    sbo::sample_cutoff(samples, w_l1, sf2, budget_mean, &L, err_path);
+    *cutoff_log2 = L;
+    return SBO_OK;
+}
+
+SBO_API sbo_status sbo_debug_sample_draws(sbo_ctx *ctx, uint64_t seed, int64_t first, int64_t samples,
+                                          int64_t features, double *nu, double *ab, double *eps) {
+    if (!ctx) return SBO_E_INVAL;
+    SBO_CHECK(nu && ab && eps, SBO_E_INVAL, "sbo_debug_sample_draws: null output");
+    if (sbo_status st = sample_sizes(ctx, first, samples, features, "sbo_debug_sample_draws")) return st;
+    const int64_t n = ctx->n, S = samples, F = features;
+    SBO_CHECK(ctx->fitted && n > 0, SBO_E_STATE, "sbo_debug_sample_draws: call sbo_fit first");
+    SBO_CHECK(n <= ((int64_t)1 << 24), SBO_E_INVAL, "sbo_debug_sample_draws: more than 2^24 training points");
+    SBO_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const int64_t pp = sbo::round_up(S, 16), Fp = sbo::round_up(F, 4);
+    SBO_HIP(ctx->smws.reserve(2 * Carve::need(Fp, 8) + Carve::need(n, 8) + Carve::need(2 * F, 8) +
+                              Carve::need(S * 2 * F, 8) + Carve::need(S * n, 8)));
+    Carve cv(ctx->smws.as<void>());
+    double *wx = cv.take<double>(Fp), *wy = cv.take<double>(Fp);
+    int64_t *order = cv.take<int64_t>(n);
+    double *dnu = cv.take<double>(2 * F), *dab = cv.take<double>(S * 2 * F), *deps = cv.take<double>(S * n);
+    SBO_HIP(hipMemcpyAsync(order, ctx->order.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, s));
+    SBO_HIP(sbo::launch_sample_draw(s, seed, first, S, pp, pp, F, Fp, n, order, ctx->hyper.length_scale, ctx->hyper.sigma_f,
+                                    ctx->hyper.noise_level, wx, wy, nullptr, nullptr, dnu, dab, deps));
+    SBO_HIP(hipMemcpyAsync(nu, dnu, sizeof(double) * 2 * F, hipMemcpyDeviceToHost, s));
+    SBO_HIP(hipMemcpyAsync(ab, dab, sizeof(double) * S * 2 * F, hipMemcpyDeviceToHost, s));
+    SBO_HIP(hipMemcpyAsync(eps, deps, sizeof(double) * S * n, hipMemcpyDeviceToHost, s));
+    SBO_HIP(hipStreamSynchronize(s));
     return SBO_OK;
 }

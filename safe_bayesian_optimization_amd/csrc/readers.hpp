@@ -1,4 +1,4 @@
-// readers.hpp -- sbo_evidence and sbo_whatif (readers.cpp) as stages over a
+// readers.hpp -- sbo_evidence, sbo_whatif and sbo_sample (readers.cpp) as stages over a
 // plan: the call's sizes, the caller's pointers and the device pointers carved
 // for it.  The stages between the device phases are pure.  Host only.
 #pragma once
@@ -39,6 +39,26 @@ struct WhatifPlan {
     unsigned long long *gain = nullptr, *kept = nullptr;                   // p counts, then the sweep's tiles
     const float *cx = nullptr, *cy = nullptr;    // the candidates on the device
     double *cov = nullptr, *lo = nullptr;        // where the sweep writes them (null: not wanted)
+};
+
+struct SamplePlan {
+    int64_t n = 0, S = 0, pp = 0, F = 0, Fp = 0, m = 0;   // rows, samples (rounded up to 16), features (to 4), kept queries
+    int64_t pw = 0;                              // samples rounded up to the products' row chunk: T^T, U^T, W^T's leading dimension
+    int64_t first = 0, index_offset = 0, nb = 0;          // the first sample's number; the sweep's query blocks
+    uint64_t seed = 0;
+    bool host = false;                           // the caller's pointers are host memory
+    size_t mat = 0;                              // S m: the entries of paths
+    double beta = 0.0, f_min = 0.0, cx0 = 0.0, cy0 = 0.0;   // (cx0, cy0): the centre of the training bounding box
+    sbo_key *out_keys = nullptr;                 // the caller's
+    int64_t *out_count = nullptr;
+    double *out_paths = nullptr;
+    double *Tt = nullptr, *Ut = nullptr, *Wt = nullptr, *Theta = nullptr;   // T^T, U^T, W^T (over T^T), Theta^T
+    double *wx = nullptr, *wy = nullptr;         // the frequencies in turns
+    int64_t *order = nullptr;                    // the rows' caller indices
+    double *part = nullptr, *l1 = nullptr, *junk = nullptr;   // the sums' chunks, |w_j|_1, the sums sbo_sample does not use
+    unsigned long long *count = nullptr, *kept = nullptr, *kerr = nullptr;   // S counts, the sweep's tiles, kernel_err's bits
+    sbo_key *pkeys = nullptr, *keys = nullptr;   // S x nb partial keys, S keys
+    double *paths = nullptr;                     // where the sweep writes them (null: not wanted)
 };
 
 }  // namespace sbo

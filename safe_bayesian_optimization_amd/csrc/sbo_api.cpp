@@ -3205,7 +3205,7 @@ SBO_API sbo_status sbo_trim(sbo_ctx *ctx) {
     if (ctx->inv_stream) SBO_HIP(hipStreamSynchronize(ctx->inv_stream));
     if (ctx->chk_stream) SBO_HIP(hipStreamSynchronize(ctx->chk_stream));
     for (sbo::DevBuf *b : {&ctx->scratch, &ctx->gzws, &ctx->gzws_aux, &ctx->chk, &ctx->restage, &ctx->kzt, &ctx->qcost,
-                           &ctx->awork, &ctx->evws, &ctx->evitems, &ctx->wiws,
+                           &ctx->awork, &ctx->evws, &ctx->evitems, &ctx->wiws, &ctx->smws,
                            &ctx->cholx3[0], &ctx->cholx3[1]})
         b->release();
     return SBO_OK;

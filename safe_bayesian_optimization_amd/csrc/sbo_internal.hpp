@@ -280,6 +280,9 @@ struct sbo_ctx {
     int whatif_gemm = 0;         // SBO_OPT_WHATIF_GEMM: the candidate weights' two products by 0 dtrmm, 1 dgemm over the zero half
     sbo::DevBuf wiws;            // K_c^T / W^T, U^T, the candidates' sums and factors, counts, host staging
 
+    // posterior sample paths (sbo_sample, sample.hip): workspace only (sbo_trim frees it)
+    sbo::DevBuf smws;            // T^T / W^T, U^T, Theta^T, the frequencies, the sums, counts, keys, host staging
+
     // kernel timing (sbo_profile)
     bool prof = false;
     std::vector<hipEvent_t> ev_pool;               // free events
@@ -559,6 +562,40 @@ hipError_t launch_whatif(hipStream_t s, const double *Wt, int64_t pp, int64_t p,
 void whatif_cutoff(int64_t p, const double *w_l1, const double *cand_var, double s, double beta, double sf2,
                    double budget_var, double budget_mean, int *L_out, double *err_cov);
 double whatif_err_cov(int L, double sf2, double l1max);
+// Posterior sample paths (sample.hip, sbo_sample), pp = samples rounded up to
+// 16, Fp = features rounded up to 4.  launch_sample_draw: the frequencies
+// (wx, wy: Fp each, in turns), Theta^T (pp x 2 Fp column-major, times
+// -sf / sqrt(F)) and T^T = sqrt(noise) eps (ldw x n column-major, ldw >= pp,
+// the rows from S on zero; order: the rows' caller indices on the device) of samples first .. first + S - 1 from
+// the streams seed, seed + 1, seed + 2; Theta / Tt may be null, and raw_nu
+// (2 F), raw_ab (S x 2 F), raw_eps (S x n, the caller's training order) take
+// the standard normals themselves when not null.  launch_sample_train:
+// T^T += g(train).  launch_sample_kernel_err: *out (zeroed by the caller) =
+// the bits of the feature kernel's largest error on the lattice.
+// launch_sample: the sweep over the kept posterior -- count[j] += the positions
+// with path_j > f_min (zeroed by the caller), paths (S x m row-major, the
+// caller's query order; may be null), pkeys: S x sample_blocks(ms) partial keys,
+// keys[j] = the argmax of path_j over the safe positions with index_offset
+// added; skip_L and tiles_kept as launch_whatif's.  sample_cutoff (host): the
+// auto cutoff L and its bound on |path error| (whatif_err_cov of the largest
+// |w_j|_1).
+hipError_t launch_sample_draw(hipStream_t s, uint64_t seed, int64_t first, int64_t S, int64_t pp, int64_t ldw, int64_t F,
+                              int64_t Fp, int64_t n, const int64_t *order, double ell, double sf, double noise, double *wx,
+                              double *wy, double *Theta, double *Tt, double *raw_nu, double *raw_ab, double *raw_eps);
+hipError_t launch_sample_train(hipStream_t s, const double *Theta, int64_t pp, int64_t n, const float *x,
+                               const float *y, const double *wx, const double *wy, int64_t Fp, double cx0, double cy0,
+                               double *Tt, int64_t ldw);
+hipError_t launch_sample_kernel_err(hipStream_t s, const double *wx, const double *wy, int64_t F, double ell,
+                                    unsigned long long *out);
+int64_t sample_blocks(int64_t ms);
+hipError_t launch_sample(hipStream_t s, const double *Wt, int64_t ldw, const double *Theta, int64_t pp, int64_t S, int64_t n,
+                         const float *x, const float *y, const float4 *kbox, const float4 *qbox, const float *kqx,
+                         const float *kqy, const int32_t *kperm, int64_t ms, int64_t m, double ell, double sf2,
+                         int skip_L, const double *mu64, const double *var64, const double *wx, const double *wy,
+                         int64_t Fp, double cx0, double cy0, double beta, double f_min, int64_t index_offset,
+                         unsigned long long *count, double *paths, sbo_key *pkeys, sbo_key *keys,
+                         unsigned long long *tiles_kept);
+void sample_cutoff(int64_t S, const double *w_l1, double sf2, double budget_mean, int *L_out, double *err_path);
 // Precise sweep (predict_f64.hip, SBO_OPT_PRECISION): A = sf2 L^-1 packed in
 // f64 from the fit's f64 inverse for row blocks >= I0 (tile (I, t) at
 // tile_start(I) + t, two 64 KiB stages in MFMA fragment order), and per k-tile

@@ -392,6 +392,63 @@ class TerrainMapper:
         widths = np.asarray(hi, np.float64)[cands] - np.asarray(lo, np.float64)[cands]
         return int(cands[node.select_expander(cands, gains, widths)])
 
+    # --------------------------------------------------------- sample paths
+    def sample(self, samples: int, seed: int, beta: float, f_min: float, *, features: int = 1024, first: int = 0,
+               index_offset: int = 0, paths: bool = False, device=None) -> dict:
+        """``samples`` joint draws of the posterior on the kept grid of the last
+        ``tick_stream`` (sbo_sample; pathwise conditioning on ``features``
+        random Fourier features), numbered ``first`` .. ``first + samples - 1``
+        under ``seed``: ``scores`` / ``idx`` (f64 / int64, samples) = each
+        draw's maximum over the safe queries and where it is (``index_offset``
+        added; -1 when nothing is safe), ``count_above`` (int64) = the queries
+        with the draw above ``f_min``, and with ``paths`` the samples x m draws
+        in the caller's query order (else None); ``keys`` holds the raw
+        (samples, 2) int64 keys, as ``Context.reduce_keys`` combines them across
+        shards; plus the fields of ``sbo_sample_info``.  Host arrays by
+        default; with ``device`` (a torch device) the outputs are torch tensors
+        written on the device."""
+        S = int(samples)
+        r = N.sbo_sample_info()
+        r.struct_size = ctypes.sizeof(r)
+        m = self.stream_info()["m"] if paths else 0
+        if device is not None:
+            import torch
+            fl = N.SBO_DEVICE_PTRS
+            keys = torch.empty((max(S, 0), 2), dtype=torch.int64, device=device)
+            count = torch.empty(max(S, 0), dtype=torch.int64, device=device)
+            pm = torch.empty((S, m), dtype=torch.float64, device=device) if paths else None
+        else:
+            fl = 0
+            keys = np.empty((max(S, 0), 2), np.int64)
+            count = np.empty(max(S, 0), np.int64)
+            pm = np.empty((S, m), np.float64) if paths else None
+        self.ctx.check(self._lib.sbo_sample(self.ctx.handle, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), S,
+                                            int(features), float(beta), float(f_min), int(index_offset), _ptr(keys),
+                                            _ptr(count), _ptr(pm), ctypes.byref(r), fl))
+        if device is not None:
+            scores, idx = keys[:, 0].contiguous().view(torch.float64), keys[:, 1].contiguous()
+        else:
+            scores, idx = keys[:, 0].copy().view(np.float64), keys[:, 1].copy()
+        out = {"scores": scores, "idx": idx, "count_above": count, "paths": pm, "keys": keys}
+        out.update({f: getattr(r, f) for f, _ in N.sbo_sample_info._fields_ if f != "struct_size"})
+        return out
+
+    def sample_draws(self, samples: int, seed: int, *, features: int = 1024, first: int = 0):
+        """Test access: the standard normals the device generates for
+        ``sample`` (sbo_debug_sample_draws): nu (features, 2), ab (samples,
+        2 features: a then b) and eps (samples, n; the caller's training order)."""
+        S, F = int(samples), int(features)
+        nu, ab, eps = np.empty((F, 2), np.float64), np.empty((S, 2 * F), np.float64), np.empty((S, self.n), np.float64)
+        self.ctx.check(self._lib.sbo_debug_sample_draws(self.ctx.handle, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), S,
+                                                        F, _ptr(nu), _ptr(ab), _ptr(eps)))
+        return nu, ab, eps
+
+    def thompson_subgoal(self, beta: float, f_min: float, seed: int, features: int = 1024) -> int:
+        """The next subgoal by Thompson sampling: the maximiser of one
+        posterior draw (sample 0 of ``seed``) over the safe set of the last
+        ``tick_stream``'s grid; -1 when nothing is safe."""
+        return int(self.sample(1, seed, beta, f_min, features=features)["idx"][0])
+
     def query_cost(self, qx, qy):
         """Sweep work of each query under the current fit (sbo_query_cost):
         the k-tiles its 128-query block multiplies, per query.  Deterministic,

@@ -5,7 +5,7 @@ workloads, and the outputs are compared element by element.
   python tools/compare_libs.py LIB_A LIB_B [--configs C4 C2 box]
   python tools/compare_libs.py LIB_A LIB_B --factor-matrix   (fits under the Cholesky's options, appends)
   python tools/compare_libs.py LIB_A LIB_B --inverse-matrix  (fits under the f64 inverse's options, appends)
-  python tools/compare_libs.py LIB_A LIB_B --readers-matrix  (the streaming update, sbo_whatif and sbo_evidence)"""
+  python tools/compare_libs.py LIB_A LIB_B --readers-matrix  (the streaming update, sbo_whatif, sbo_sample and sbo_evidence)"""
 import argparse
 import os
 import subprocess
@@ -164,7 +164,7 @@ np.savez({path!r}, **out)
 print("ok", N.LIB_PATH, len(out), "arrays")
 '''
 
-# --readers-matrix: the readers of the fitted state (the streaming update, sbo_whatif, sbo_evidence) at their
+# --readers-matrix: the readers of the fitted state (the streaming update, sbo_whatif, sbo_sample, sbo_evidence) at their
 # tests' shapes, one context per shape.  Timings (ms) are left out.
 READERS_CHILD = r'''
 import ctypes, sys, numpy as np, torch
@@ -173,6 +173,7 @@ from safe_bayesian_optimization_amd import TerrainMapper
 from safe_bayesian_optimization_amd import _native as N
 from tests import evidence_model as EM
 from tests import test_gpu_evidence as TE
+from tests import test_gpu_sample as TS
 from tests import test_gpu_whatif as TW
 from tests.test_gpu_stream_tick import WIDE_SHAPES, Rig, wide_options
 out = {{}}
@@ -215,6 +216,17 @@ for shape, kw in TW.SHAPES.items():
                 for device in (False, True):
                     put(f"whatif_{{shape}}_p{{p}}_gemm{{gemm}}_skip{{skip}}_{{'dev' if device else 'host'}}",
                         c.call(p, device=device, cov=True, lo_new=True))
+    c.rig.gm.close()
+# sample paths
+for shape, kw in TW.SHAPES.items():
+    c = TS.SampleCase(dev, **kw)
+    for skip in (-1, 0):
+        c.rig.gm.set_option(N.SBO_OPT_TILE_SKIP, skip)
+        for S in TS.SS:
+            for F in TS.FS:
+                for device in (False, True):
+                    put(f"sample_{{shape}}_S{{S}}_F{{F}}_skip{{skip}}_{{'dev' if device else 'host'}}",
+                        c.call(S, F, device=device))
     c.rig.gm.close()
 # evidence
 def evidence(name, gm):
@@ -265,7 +277,8 @@ def main():
     p.add_argument("--inverse-matrix", action="store_true",
                    help="the f64 inverse's option matrix and the append paths instead of the ticks")
     p.add_argument("--readers-matrix", action="store_true",
-                   help="the streaming update, sbo_whatif and sbo_evidence at their tests' shapes instead of the ticks")
+                   help="the streaming update, sbo_whatif, sbo_sample and sbo_evidence at their tests' shapes instead of "
+                        "the ticks")
     a = p.parse_args()
     child = FACTOR_CHILD if a.factor_matrix else INVERSE_CHILD if a.inverse_matrix else \
         READERS_CHILD if a.readers_matrix else CHILD

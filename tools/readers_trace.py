@@ -1,10 +1,11 @@
-"""The launches of the three readers of the fitted state under a kernel trace, at
+"""The launches of the four readers of the fitted state under a kernel trace, at
 the shapes of their tests: a stream sequence (fit 250, tick, appends of 1, 17
 and 33 with a tick each; fit 300 + 65 and fit 650 + 150 under
 SBO_OPT_STREAM_MAX_ROWS 256), sbo_evidence on the three cases of
-tests/test_gpu_evidence.py (default budget and dense, LOO to the host), and
+tests/test_gpu_evidence.py (default budget and dense, LOO to the host),
 sbo_whatif on the three shapes of tests/test_gpu_whatif.py at p = 1, 17, 150
-(dtrmm and dgemm weights).  Run once per build (SBO_LIB) and compare the lists:
+(dtrmm and dgemm weights), and sbo_sample on the same shapes at S = 1, 17, 150
+and F = 1, 37, 256 (tests/test_gpu_sample.py).  Run once per build (SBO_LIB) and compare the lists:
     rocprofv3 --kernel-trace -d D -o run --output-format csv -- python3 tools/readers_trace.py
     python tools/readers_trace.py --list D profiles/<name>.txt"""
 import os
@@ -19,7 +20,7 @@ HEADER = """\
 # Kernel launches of one traced run of the readers of the fitted state at their tests' shapes.  Stream: fit 250, tick, appends
 # of 1, 17, 33 with a tick each; fit 300 + append 65 and fit 650 + append 150 under STREAM_MAX_ROWS 256.  Evidence: one_tile_row,
 # wide, lpsc_box at EVIDENCE_BUDGET 20 and 0 with LOO.  What-if: appended333, box24l, lpsc700precise at p = 1, 17, 150, cov and
-# lo_new, WHATIF_GEMM 0 then 1.
+# lo_new, WHATIF_GEMM 0 then 1.  Sample: the same shapes at S = 1, 17, 150 x F = 1, 37, 256 with paths.
 # Per queue (numbered by first launch), the kernels in start order as ids of the legend below (ids by first appearance, queue by queue);
 # names longer than 120 characters are cut, with 8 hex digits of the full name's SHA-1.
 """
@@ -31,6 +32,7 @@ def main():
     import torch
     from safe_bayesian_optimization_amd import _native as N
     from tests import test_gpu_evidence as TE
+    from tests import test_gpu_sample as TS
     from tests import test_gpu_whatif as TW
     from tests.test_gpu_stream_tick import WIDE_SHAPES, Rig, wide_options
     dev = torch.device("cuda:0")
@@ -59,6 +61,13 @@ def main():
             c.rig.gm.set_option(N.SBO_OPT_WHATIF_GEMM, gemm)
             for p in TW.PS:
                 c.call(p, cov=True, lo_new=True)
+        torch.cuda.synchronize()
+        c.rig.gm.close()
+    for shape, kw in TW.SHAPES.items():
+        c = TS.SampleCase(dev, **kw)
+        for S in TS.SS:
+            for F in TS.FS:
+                c.call(S, F)
         torch.cuda.synchronize()
         c.rig.gm.close()
 
