@@ -973,6 +973,16 @@ SBO_API sbo_status sbo_debug_x3_stamps(sbo_ctx *ctx, double *cycles, int n);
  * the operand's size; host_buf may be null to ask for it alone. */
 SBO_API sbo_status sbo_debug_x3_operand(sbo_ctx *ctx, void *host_buf, int64_t cap, int64_t *bytes);
 
+/* Test accessor: which parts of the context's model are valid, as the first
+ * min(cap, 13) of: [0] n, [1] npad, [2] fitted, [3] has_factor, [4] rows of the
+ * f64 inverse, [5] rows of z, [6] N at the last probe, [7] the first row block
+ * the split operand must be derived from for the kernel variant in effect (-1:
+ * current), [8] the layout it was last derived in (-1: never), [9] / [10] the
+ * same for the precise operand and SBO_OPT_PRECISE_KERNEL, [11] a precise pack
+ * is in flight that the host has not waited for, [12] fit_epoch.  Nothing is
+ * launched or waited for; valid on an unfitted context. */
+SBO_API sbo_status sbo_debug_state(const sbo_ctx *ctx, int64_t *out, int cap);
+
 /* Test accessor: the plan a tick of these m queries (host pointers) would
  * sweep under the context's options -- the plan sbo_query_cost builds; no
  * sweep runs -- as int32 in host_buf: [0] nI row blocks, [1] nQ query blocks

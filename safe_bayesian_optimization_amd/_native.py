@@ -34,7 +34,7 @@ EXPORTS = (
     "sbo_get_bounds", "sbo_get_jitter", "sbo_get_tile_bounds", "sbo_state_bytes", "sbo_export_state", "sbo_import_state", "sbo_query_cost",
     "sbo_polygon_correct", "sbo_polydist", "sbo_point_within", "sbo_project_subgoal", "sbo_get_precision",
     "sbo_kd_order", "sbo_get_probe", "sbo_keys_reduce", "sbo_get_inverse_check", "sbo_trim", "sbo_warmup",
-    "sbo_debug_gz_gemm", "sbo_debug_gz_gemm_packed", "sbo_debug_x3_operand", "sbo_debug_plan",
+    "sbo_debug_gz_gemm", "sbo_debug_gz_gemm_packed", "sbo_debug_x3_operand", "sbo_debug_plan", "sbo_debug_state",
     "sbo_tick_stream", "sbo_get_stream", "sbo_stream_reset", "sbo_debug_stream_state",
     "sbo_evidence", "sbo_debug_evidence_pairs", "sbo_debug_inverse_plan",
     "sbo_whatif", "sbo_debug_whatif_cutoff",
@@ -291,6 +291,8 @@ def lib():
     L.sbo_debug_x3_stamps.restype = st
     L.sbo_debug_x3_operand.argtypes = [vp, vp, i64, ctypes.POINTER(i64)]
     L.sbo_debug_x3_operand.restype = st
+    L.sbo_debug_state.argtypes = [vp, ctypes.POINTER(i64), ctypes.c_int]
+    L.sbo_debug_state.restype = st
     L.sbo_debug_plan.argtypes = [vp, vp, vp, i64, vp, i64, ctypes.POINTER(i64)]
     L.sbo_debug_plan.restype = st
     L.sbo_debug_gz_gemm.argtypes = [vp, i32, i32, vp, i64, i64, vp, i64, i64, i64, i64, i64, dbl, vp, i64, i64, u32]

@@ -128,13 +128,13 @@ InvPlan plan_inverse(const InvConfig &cfg, int64_t n, int64_t ld) {
 
 InvConfig inv_config(const sbo_ctx *ctx, int digits) {
     InvConfig c;
-    c.base = ctx->inv_base;
-    c.panels = ctx->inv_panels;
-    c.leaves = !ctx->inv_batched      ? InvLeaves::kOneByOne
-               : ctx->inv_leaves_own ? InvLeaves::kDoubling
+    c.base = ctx->opt.inv_base;
+    c.panels = ctx->opt.inv_panels;
+    c.leaves = !ctx->opt.inv_batched      ? InvLeaves::kOneByOne
+               : ctx->opt.inv_leaves_own ? InvLeaves::kDoubling
                                      : InvLeaves::kBatched;
     c.digits = digits;
-    c.oz_min = ctx->inv_oz_min > 0 ? ctx->inv_oz_min : (ctx->n >= 12288 ? 2048 : 4096);
+    c.oz_min = ctx->opt.inv_oz_min > 0 ? ctx->opt.inv_oz_min : (ctx->n >= 12288 ? 2048 : 4096);
     c.two_lanes = aux_ready(ctx);
     return c;
 }
@@ -148,19 +148,19 @@ InvConfig inv_config_early(const sbo_ctx *ctx) {
 
 sbo_status inverse_reserve(sbo_ctx *ctx, const InvPlan &plan) {
     SBO_HIP(ctx->Linv.reserve(sizeof(double) * (size_t)plan.ld * (size_t)plan.ld));
-    SBO_HIP(ctx->scratch.reserve(sizeof(double) * (size_t)std::max<int64_t>(plan.scratch_doubles(), 1)));
+    SBO_HIP(ctx->ws.scratch.reserve(sizeof(double) * (size_t)std::max<int64_t>(plan.scratch_doubles(), 1)));
     SBO_HIP(ctx->info.reserve(sizeof(rocblas_int) * (size_t)plan.info_total));
     // one workspace per lane (SBO_OPT_INV_OZ: the sliced products on the int8
     // matrix cores)
-    SBO_HIP(ctx->gzws.reserve(plan.ws_bytes[0]));
-    SBO_HIP(ctx->gzws_aux.reserve(plan.ws_bytes[1]));
+    SBO_HIP(ctx->ws.gzws.reserve(plan.ws_bytes[0]));
+    SBO_HIP(ctx->ws.gzws_aux.reserve(plan.ws_bytes[1]));
     return SBO_OK;
 }
 
 namespace {
 
-InvLane lane_main(sbo_ctx *ctx) { return {ctx->stream, ctx->blas, &ctx->gzws}; }
-InvLane lane_aux(sbo_ctx *ctx) { return {ctx->aux_stream, ctx->blas_aux, &ctx->gzws_aux}; }
+InvLane lane_main(sbo_ctx *ctx) { return {ctx->stream, ctx->blas, &ctx->ws.gzws}; }
+InvLane lane_aux(sbo_ctx *ctx) { return {ctx->aux_stream, ctx->blas_aux, &ctx->ws.gzws_aux}; }
 InvLane lane_inv(sbo_ctx *ctx) { return {ctx->inv_stream, ctx->blas_inv, nullptr}; }
 
 // ---- the pieces: one node on one lane ----
@@ -186,7 +186,7 @@ struct NodeView {
 };
 NodeView view(const sbo_ctx *ctx, const InvPlan &plan, const InvNode &nd) {
     double *A = ctx->Linv.as<double>() + nd.off * (plan.ld + 1);
-    return {nd.h, nd.m(), plan.ld, A, A + nd.h, A + nd.h * (plan.ld + 1), ctx->scratch.as<double>() + nd.s_off};
+    return {nd.h, nd.m(), plan.ld, A, A + nd.h, A + nd.h * (plan.ld + 1), ctx->ws.scratch.as<double>() + nd.s_off};
 }
 
 // S = B A^-1 of a node whose A^-1 is done
@@ -318,7 +318,7 @@ sbo_status inverse_leaves(sbo_ctx *ctx, const InvPlan &plan, rocblas_handle hb) 
     double *Li = ctx->Linv.as<double>();
     rocblas_int *info = ctx->info.as<rocblas_int>() + 1;
     if (plan.doubling) {
-        if (sbo_status st = leaves_doubling(ctx, plan, hb, Li, ctx->scratch.as<double>()); st != SBO_OK) return st;
+        if (sbo_status st = leaves_doubling(ctx, plan, hb, Li, ctx->ws.scratch.as<double>()); st != SBO_OK) return st;
     } else if (nf > 0)
         SBO_BLAS(rocsolver_dtrtri_strided_batched(hb, rocblas_fill_lower, rocblas_diagonal_non_unit, (rocblas_int)b,
                                                   Li, (rocblas_int)ld, (rocblas_stride)(b * (ld + 1)), info,
@@ -431,8 +431,8 @@ sbo_status inverse_incremental(sbo_ctx *ctx, int64_t n, int64_t ld, int64_t n_ol
     SBO_HIP(hipMemset2DAsync(Li + n_old * ld, sizeof(double) * (size_t)ld, 0, sizeof(double) * (size_t)n_old,
                              (size_t)b, ctx->stream));
     // (sized by the capacity, so that the appends of a streaming loop do not regrow it)
-    SBO_HIP(ctx->scratch.reserve(sizeof(double) * (size_t)sbo::round_up(b, 256) * (size_t)ld));
-    double *S = ctx->scratch.as<double>();
+    SBO_HIP(ctx->ws.scratch.reserve(sizeof(double) * (size_t)sbo::round_up(b, 256) * (size_t)ld));
+    double *S = ctx->ws.scratch.as<double>();
     const double zero = 0.0;
     if (b <= sbo::kAppendInvRows) {
         // row by row: S[r,:]^T = Li^T T[r,:]^T, one dtrmv over the

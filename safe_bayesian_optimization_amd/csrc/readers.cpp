@@ -68,9 +68,9 @@ sbo_status evidence_plan(sbo_ctx *ctx, const sbo_evidence_info *out, uint32_t fl
     p.T = (n + sbo::kBK - 1) / sbo::kBK;
     p.want_loo = p.out_mean || p.out_var;
     p.host_loo = p.want_loo && !dev(flags);
-    SBO_HIP(ctx->evws.reserve(Carve::need(n, 8) + Carve::need(p.T * sbo::kEvSums, 8) + Carve::need(1, 8) +
+    SBO_HIP(ctx->ws.evws.reserve(Carve::need(n, 8) + Carve::need(p.T * sbo::kEvSums, 8) + Carve::need(1, 8) +
                               (p.want_loo ? Carve::need(n, 8) : 0) + (p.host_loo ? 2 * Carve::need(n, 8) : 0)));
-    Carve cv(ctx->evws.as<void>());
+    Carve cv(ctx->ws.evws.as<void>());
     p.c = cv.take<double>(n), p.sums = cv.take<double>(p.T * sbo::kEvSums), p.res = cv.take<double>(1);
     if (!p.want_loo) return SBO_OK;
     p.order = cv.take<int64_t>(n);
@@ -111,8 +111,8 @@ sbo_status evidence_gram(sbo_ctx *ctx, const EvidencePlan &p, PhaseEvents &pe, c
                          sbo_evidence_info &r) {
     hipStream_t s = ctx->stream;
     const int64_t ni = (int64_t)items.size();
-    SBO_HIP(ctx->evitems.reserve(Carve::need(ni, sizeof(int4)) + Carve::need(ni, 8)));
-    Carve ci(ctx->evitems.as<void>());
+    SBO_HIP(ctx->ws.evitems.reserve(Carve::need(ni, sizeof(int4)) + Carve::need(ni, 8)));
+    Carve ci(ctx->ws.evitems.as<void>());
     int4 *ditems = ci.take<int4>(ni);
     double *dslots = ci.take<double>(ni);
     SBO_HIP(hipMemcpyAsync(ditems, items.data(), sizeof(int4) * (size_t)ni, hipMemcpyHostToDevice, s));
@@ -144,7 +144,7 @@ sbo_status evidence_run(sbo_ctx *ctx, sbo_evidence_info *out, double *loo_mean, 
     // the cutoff, then the items.  Host cost per call, T = n / 64: the T x T drop map (64 KiB at n = 16384, 1 MiB at
     // 65536), inside evidence_pairs up to T^2 / 2 candidates of 16 B (0.5 / 8 MiB) and their sort, and 16 B per item
     // (about n^2 / 1400 items: 3 MiB at 16384, 47 MiB at 65536)
-    r.grad_budget = ctx->evidence_budget > 0 ? std::ldexp((double)p.n, -ctx->evidence_budget) : 0.0;
+    r.grad_budget = ctx->opt.evidence_budget > 0 ? std::ldexp((double)p.n, -ctx->opt.evidence_budget) : 0.0;
     std::vector<uint8_t> drop((size_t)T * T);
     sbo::evidence_pairs(boxes.data(), al1.data(), sl1.data(), T, ctx->hyper.length_scale,
                         ctx->hyper.sigma_f * ctx->hyper.sigma_f, r.grad_budget, drop.data(), &r.grad_err_bound);
@@ -209,7 +209,7 @@ sbo_status inverse_products(sbo_ctx *ctx, const double *Bt, double *Ut, double *
     const double one = 1.0, zero = 0.0;
     const rocblas_int pp = (rocblas_int)rows, lb = (rocblas_int)ldb, n = (rocblas_int)n_, ld = (rocblas_int)ctx->cap;
     SBO_BLAS(rocblas_set_pointer_mode(ctx->blas, rocblas_pointer_mode_host));
-    if (ctx->whatif_gemm) {   // (the inverse's strict upper half is stored as zeros)
+    if (ctx->opt.whatif_gemm) {   // (the inverse's strict upper half is stored as zeros)
         SBO_BLAS(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_transpose, pp, n, n, &one, Bt, lb, X,
                                ld, &zero, Ut, lb));
         SBO_BLAS(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_none, pp, n, n, &one, Ut, lb, X, ld,
@@ -239,12 +239,12 @@ sbo_status whatif_plan(sbo_ctx *ctx, const float *cx, const float *cy, const sbo
     w.m = k.m;
     w.host = !dev(flags);
     w.mat = (size_t)p * (size_t)w.m;
-    SBO_HIP(ctx->wiws.reserve(2 * Carve::need((size_t)pp * (size_t)n, 8) + Carve::need(sbo::whatif_part_bytes(pp), 1) +
+    SBO_HIP(ctx->ws.wiws.reserve(2 * Carve::need((size_t)pp * (size_t)n, 8) + Carve::need(sbo::whatif_part_bytes(pp), 1) +
                               3 * Carve::need(p, 8) + Carve::need(2 * pp, 8) + Carve::need(p + 1, 8) +
                               (w.host ? 2 * Carve::need(p, 4) + (w.out_cov ? Carve::need(w.mat, 8) : 0) +
                                             (w.out_lo ? Carve::need(w.mat, 8) : 0)
                                       : 0)));
-    Carve cv(ctx->wiws.as<void>());
+    Carve cv(ctx->ws.wiws.as<void>());
     w.Wt = w.Kt = cv.take<double>((size_t)pp * (size_t)n), w.Ut = cv.take<double>((size_t)pp * (size_t)n);
     w.part = cv.take<double>(sbo::whatif_part_bytes(pp) / 8);
     w.mu = cv.take<double>(p), w.var = cv.take<double>(p), w.l1 = cv.take<double>(p);
@@ -287,7 +287,7 @@ sbo_status whatif_weights(sbo_ctx *ctx, const WhatifPlan &w, PhaseEvents &pe, st
 int whatif_choose_cutoff(const sbo_ctx *ctx, const WhatifPlan &w, const std::vector<double> &hvar,
                          const std::vector<double> &hl1, double &err_cov) {
     const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
-    int L = ctx->skip_log2;
+    int L = ctx->opt.skip_log2;
     if (L < 0) {
         double bvar = 0.0, bmean = 0.0;
         stream_budget(ctx, bvar, bmean);
@@ -434,11 +434,11 @@ sbo_status sample_plan(sbo_ctx *ctx, const sbo_sample_info *info, uint32_t flags
     p.cx0 = 0.5 * ((double)ctx->bbox[0] + (double)ctx->bbox[1]);
     p.cy0 = 0.5 * ((double)ctx->bbox[2] + (double)ctx->bbox[3]);
     const size_t pn = (size_t)pw * (size_t)n, pf = (size_t)pp * (size_t)(2 * Fp), pk = (size_t)S * (size_t)p.nb;
-    SBO_HIP(ctx->smws.reserve(2 * Carve::need(pn, 8) + Carve::need(pf, 8) + 2 * Carve::need(Fp, 8) + Carve::need(n, 8) +
+    SBO_HIP(ctx->ws.smws.reserve(2 * Carve::need(pn, 8) + Carve::need(pf, 8) + 2 * Carve::need(Fp, 8) + Carve::need(n, 8) +
                               Carve::need(sbo::whatif_part_bytes(pw), 1) + Carve::need(S, 8) +
                               Carve::need(2 * S + 2 * pw, 8) + Carve::need(S + 2, 8) + Carve::need(pk, sizeof(sbo_key)) +
                               Carve::need(S, sizeof(sbo_key)) + (p.host && p.out_paths ? Carve::need(p.mat, 8) : 0)));
-    Carve cv(ctx->smws.as<void>());
+    Carve cv(ctx->ws.smws.as<void>());
     p.Wt = p.Tt = cv.take<double>(pn), p.Ut = cv.take<double>(pn), p.Theta = cv.take<double>(pf);
     p.wx = cv.take<double>(Fp), p.wy = cv.take<double>(Fp);
     p.order = cv.take<int64_t>(n);
@@ -488,7 +488,7 @@ sbo_status sample_weights(sbo_ctx *ctx, const SamplePlan &p, PhaseEvents &pe, st
 // on |path error|.
 int sample_choose_cutoff(const sbo_ctx *ctx, const std::vector<double> &hl1, double &err_path) {
     const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
-    int L = ctx->skip_log2;
+    int L = ctx->opt.skip_log2;
     if (L < 0) {
         double bvar = 0.0, bmean = 0.0;
         stream_budget(ctx, bvar, bmean);
@@ -590,9 +590,9 @@ SBO_API sbo_status sbo_debug_sample_draws(sbo_ctx *ctx, uint64_t seed, int64_t f
     SBO_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const int64_t pp = sbo::round_up(S, 16), Fp = sbo::round_up(F, 4);
-    SBO_HIP(ctx->smws.reserve(2 * Carve::need(Fp, 8) + Carve::need(n, 8) + Carve::need(2 * F, 8) +
+    SBO_HIP(ctx->ws.smws.reserve(2 * Carve::need(Fp, 8) + Carve::need(n, 8) + Carve::need(2 * F, 8) +
                               Carve::need(S * 2 * F, 8) + Carve::need(S * n, 8)));
-    Carve cv(ctx->smws.as<void>());
+    Carve cv(ctx->ws.smws.as<void>());
     double *wx = cv.take<double>(Fp), *wy = cv.take<double>(Fp);
     int64_t *order = cv.take<int64_t>(n);
     double *dnu = cv.take<double>(2 * F), *dab = cv.take<double>(S * 2 * F), *deps = cv.take<double>(S * n);

@@ -18,7 +18,6 @@
 
 #include "inverse.hpp"
 #include "sbo_host.hpp"
-#include "sbo_internal.hpp"
 
 using sbo::DevBuf;
 using sbo::kAppendInvGemm;
@@ -42,7 +41,7 @@ sbo_status finish(sbo_ctx *ctx, uint32_t flags) {
 // The digits of the current fit's sliced products (SBO_OPT_INV_OZ_ADAPT:
 // chosen per fit by choose_inv_digits; 0 with SBO_OPT_INV_OZ 0)
 int inv_digits(const sbo_ctx *ctx) {
-    return ctx->inv_oz == 0 ? 0 : ctx->inv_oz_cur > 0 ? ctx->inv_oz_cur : ctx->inv_oz;
+    return ctx->opt.inv_oz == 0 ? 0 : ctx->inv_oz_cur > 0 ? ctx->inv_oz_cur : ctx->opt.inv_oz;
 }
 // SBO_OPT_INV_OZ_ADAPT: the guard's readings of a sliced inverse (its
 // effect on the variance and on the mean at 31 queries) grow ~256x per digit
@@ -89,18 +88,18 @@ int choose_inv_digits(const sbo_ctx *ctx) {
     // (diagnostic build: SBO_INV_OZ_FORCE = d takes d digits for every fit
     // the pinning allows -- the pinning's test, test_diagnostic_only_variants)
     if (const char *e = getenv("SBO_INV_OZ_FORCE");
-        e && ctx->inv_oz_adapt && ctx->inv_check != 0 && ctx->inv_oz != 0 && !(ctx->inv_oz_pinned && inv_same_data(ctx)))
-        return std::clamp(atoi(e), 4, ctx->inv_oz);
+        e && ctx->opt.inv_oz_adapt && ctx->opt.inv_check != 0 && ctx->opt.inv_oz != 0 && !(ctx->inv_oz_pinned && inv_same_data(ctx)))
+        return std::clamp(atoi(e), 4, ctx->opt.inv_oz);
 #endif
-    if (!ctx->inv_oz_adapt || ctx->inv_check == 0 || ctx->inv_oz == 0 || ctx->inv_oz_next <= 0 ||
+    if (!ctx->opt.inv_oz_adapt || ctx->opt.inv_check == 0 || ctx->opt.inv_oz == 0 || ctx->inv_oz_next <= 0 ||
         !inv_same_data(ctx))
-        return ctx->inv_oz;
-    return std::min(ctx->inv_oz, ctx->inv_oz_next);
+        return ctx->opt.inv_oz;
+    return std::min(ctx->opt.inv_oz, ctx->inv_oz_next);
 }
 // the bound a checked inverse must meet on both readings: tol, and tol /
 // kInvOzReduced for fewer than SBO_OPT_INV_OZ digits
 double inv_check_bar(const sbo_ctx *ctx, const sbo_inv_check &r) {
-    return (r.digits > 0 && r.digits < ctx->inv_oz) ? r.tol / kInvOzReduced : r.tol;
+    return (r.digits > 0 && r.digits < ctx->opt.inv_oz) ? r.tol / kInvOzReduced : r.tol;
 }
 bool inv_check_passed(const sbo_ctx *ctx, const sbo_inv_check &r) {
     const double bar = inv_check_bar(ctx, r);
@@ -113,17 +112,17 @@ void record_inv_digits(sbo_ctx *ctx, const sbo_inv_check &r) {
     ctx->inv_oz_hist_area = bbox_area(ctx);
     ctx->inv_oz_hist_hyper = ctx->hyper;
     ctx->inv_oz_next = 0;
-    if (!ctx->inv_oz_adapt || !r.ran || r.digits <= 0) return;
+    if (!ctx->opt.inv_oz_adapt || !r.ran || r.digits <= 0) return;
     if (!inv_check_passed(ctx, r)) {
         // fired at reduced digits: this data keeps SBO_OPT_INV_OZ digits from
         // now on (no reduced fit that fires every other time)
-        if (r.digits < ctx->inv_oz) ctx->inv_oz_pinned = true;
+        if (r.digits < ctx->opt.inv_oz) ctx->inv_oz_pinned = true;
         return;
     }
     if (ctx->inv_oz_pinned) return;
     const double e = std::max(r.err, r.err_mean);
-    int nd = ctx->inv_oz;
-    for (int d = kInvOzAdaptMin; d < ctx->inv_oz; ++d)
+    int nd = ctx->opt.inv_oz;
+    for (int d = kInvOzAdaptMin; d < ctx->opt.inv_oz; ++d)
         if (e * std::ldexp(1.0, 8 * (r.digits - d)) <= r.tol / kInvOzPredict) {
             nd = d;
             break;
@@ -235,7 +234,7 @@ void kd_order(const std::vector<float> &hx, const std::vector<float> &hy, int64_
 }
 
 // Copy `count` measurements into the context's training buffers at `dst`,
-// in Hilbert (ctx->spatial_order == 1) or Morton (2) order so that every
+// in Hilbert (ctx->opt.spatial_order == 1) or Morton (2) order so that every
 // 64-point k-tile is spatially compact and far tiles can be skipped, and
 // record the caller's index of each internal row in ctx->order.
 sbo_status stage_training(sbo_ctx *ctx, const float *x, const float *y, const float *obs, int64_t count,
@@ -248,9 +247,9 @@ sbo_status stage_training(sbo_ctx *ctx, const float *x, const float *y, const fl
     SBO_HIP(hipStreamSynchronize(ctx->stream));
     std::vector<int64_t> perm(count);
     for (int64_t i = 0; i < count; ++i) perm[i] = i;
-    if (ctx->spatial_order == 3 && count > 1) {
+    if (ctx->opt.spatial_order == 3 && count > 1) {
         kd_order(hx, hy, perm.data(), count, dst % sbo::kBK);
-    } else if (ctx->spatial_order && count > 1) {
+    } else if (ctx->opt.spatial_order && count > 1) {
         const auto mx = std::minmax_element(hx.begin(), hx.end());
         const auto my = std::minmax_element(hy.begin(), hy.end());
         const double x0 = *mx.first, sx = std::max(1e-30, (double)*mx.second - x0);
@@ -261,7 +260,7 @@ sbo_status stage_training(sbo_ctx *ctx, const float *x, const float *y, const fl
             const double v = std::min(1.0, std::max(0.0, (hy[i] - y0) / sy));
             const uint32_t qu = (uint32_t)(u * 65535.0), qv = (uint32_t)(v * 65535.0);
             code[i] = !(std::isfinite(u) && std::isfinite(v)) ? 0
-                      : ctx->spatial_order == 2                ? morton2(qu, qv)
+                      : ctx->opt.spatial_order == 2                ? morton2(qu, qv)
                                                                : hilbert2(qu, qv);
         }
         std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) { return code[a] < code[b]; });
@@ -380,59 +379,78 @@ struct TickPlan {
     const int32_t *perm = nullptr;
     const float *qx = nullptr, *qy = nullptr;
 };
-// The split operand of the current kernel variant's layout, brought up to
-// date on ctx->stream: the bf16 planes of any row block repacked since it was
-// last derived (all of them after a change of layout) and the coordinates.
-sbo_status derive_x3(sbo_ctx *ctx) {
-    const int64_t nIc = ctx->npad / sbo::kBM;
-    const int layout = sbo::x3_layout(ctx->kernel_variant);
-    if (layout != ctx->x3_layout) ctx->x3_I0 = 0;  // another layout: derive all of it
-    if (ctx->x3_I0 < nIc) {
-        const int64_t I0 = std::max<int64_t>(ctx->x3_I0, 0);
-        SBO_HIP(grow_keep(ctx, ctx->ax3, sbo::x3_operand_bytes(ctx->npad), sbo::x3_operand_bytes(I0 * sbo::kBM)));
-        SBO_HIP(ctx->kc3.reserve(sbo::x3_coord_bytes(ctx->npad)));
-        SBO_HIP(sbo::launch_pack_x3(ctx->stream, ctx->aug.as<float>(), ctx->kcoord.as<float>(), ctx->npad, I0, layout,
-                                    ctx->ax3.as<char>(), ctx->kc3.as<float>()));
-        ctx->x3_I0 = INT64_MAX;
-        ctx->x3_layout = layout;
-    }
+}  // namespace
+
+// ---- the split operand (SplitOperand, sbo_ctx.hpp)
+sbo_status SplitOperand::reserve(sbo_ctx *ctx, int64_t npad, int layout) {
+    const int64_t I0 = std::min(st_.start(layout), npad / sbo::kBM);
+    SBO_HIP(grow_keep(ctx, ax3, sbo::x3_operand_bytes(npad), sbo::x3_operand_bytes(I0 * sbo::kBM)));
+    SBO_HIP(kc3.reserve(sbo::x3_coord_bytes(npad)));
     return SBO_OK;
+}
+sbo_status SplitOperand::update(sbo_ctx *ctx, int64_t npad, int layout, hipStream_t planes, bool coords) {
+    if (st_.current(npad / sbo::kBM, layout)) return SBO_OK;
+    if (sbo_status st = reserve(ctx, npad, layout)) return st;
+    SBO_HIP(sbo::launch_pack_x3(planes, ctx->aug.as<float>(), coords ? ctx->kcoord.as<float>() : nullptr, npad,
+                                st_.start(layout), layout, ax3.as<char>(), coords ? kc3.as<float>() : nullptr));
+    st_.mark(layout);
+    return SBO_OK;
+}
+sbo_status SplitOperand::pack_coords(sbo_ctx *ctx, int64_t npad, hipStream_t s) {
+    SBO_HIP(sbo::launch_pack_x3(s, nullptr, ctx->kcoord.as<float>(), npad, 0, 0, nullptr, kc3.as<float>()));
+    return SBO_OK;
+}
+namespace {
+// The split operand of the current kernel variant's layout, up to date on
+// ctx->stream (the tick's lazy derivation, sbo_debug_x3_operand).
+sbo_status derive_x3(sbo_ctx *ctx) {
+    return ctx->split.update(ctx, ctx->npad, sbo::x3_layout(ctx->opt.kernel_variant), ctx->stream, true);
 }
 
 sbo_status run_tick(sbo_ctx *ctx, const TickRequest &rq, TickPlan *plan_out = nullptr);
-sbo_status probe_precision(sbo_ctx *ctx);
+sbo_status probe_precision(sbo_ctx *ctx, int precision);
 // the precision probe runs on this refresh (probe_precision): on a fresh fit,
 // and on appends once N has grown by SBO_OPT_REPROBE % (default a quarter)
 // since the last probe
 bool probe_due(const sbo_ctx *ctx) {
     return ctx->probe_n == 0 || ctx->n < ctx->probe_n ||
-           (ctx->n - ctx->probe_n) * 100 >= ctx->probe_n * (int64_t)ctx->reprobe_pct;
-}
-
-// Wait (host) for a precise-operand pack still running on aux_stream
-// (refresh_operand leaves it in flight past the fit's own host sync).
-sbo_status drain_poz(sbo_ctx *ctx) {
-    if (ctx->poz_pending) {
-        SBO_HIP(hipEventSynchronize(ctx->ev_poz));
-        ctx->poz_pending = false;
-    }
-    return SBO_OK;
+           (ctx->n - ctx->probe_n) * 100 >= ctx->probe_n * (int64_t)ctx->opt.reprobe_pct;
 }
 
 // Wait (host) for an accuracy guard still running on chk_stream: it reads L,
-// L^-1, x/y/obs and ctx->chk, so whoever abandons a refresh waits for it
+// L^-1, x/y/obs and ctx->ws.chk, so whoever abandons a refresh waits for it
 // before those buffers are regrown, freed or rewritten.
 void drain_guard(sbo_ctx *ctx) {
     if (ctx->chk_stream) (void)hipStreamSynchronize(ctx->chk_stream);
 }
 
+// The context out of the fitted state, every buffer keeping its capacity: no
+// model, nothing derived from one, no guard in flight.  The one list of what
+// "fitted" stands on; the digit adaptation's history across fits
+// (inv_oz_next, inv_oz_hist_*, inv_oz_pinned) is not part of it.
+void unfit(sbo_ctx *ctx) {
+    ++ctx->fit_epoch;   // (whatever follows is another model: a kept posterior is not updated into it)
+    ctx->fitted = false;
+    ctx->has_factor = false;
+    ctx->n = 0;
+    ctx->linv_n = 0;
+    ctx->z_n = 0;
+    ctx->probe_n = 0;
+    ctx->precise = false;
+    ctx->n_sorted = 0;
+    ctx->order.clear();
+    ctx->chk_res = sbo_inv_check{};
+    ctx->split.all_changed();
+    ctx->pop.all_changed();
+    drain_guard(ctx);
+}
+
 // The one commit point of the calls that rebuild the model (sbo_fit,
 // sbo_append, sbo_import_state), armed once their arguments are accepted and
-// drain_poz has run.  From then on the context counts as fitted only through
-// commit(): every other way out -- an error return of any stage, the probe
-// and the guard's reading included -- leaves it unfitted with no inverse to
-// extend and no guard in flight, so that it accepts a new sbo_fit, an import
-// or option calls and nothing else.
+// the precise operand's pack is drained.  From then on the context counts as
+// fitted only through commit(): every other way out -- an error return of any
+// stage, the probe and the guard's reading included -- is unfit(), so that it
+// accepts a new sbo_fit, an import or option calls and nothing else.
 struct FitCommit {
     sbo_ctx *ctx;
     bool committed = false;
@@ -444,49 +462,69 @@ struct FitCommit {
         return SBO_OK;
     }
     ~FitCommit() {
-        if (committed) return;
-        ++ctx->fit_epoch;   // (whatever follows is another model: a kept posterior is not updated into it)
-        ctx->fitted = false;
-        ctx->linv_n = 0;
-        drain_guard(ctx);
+        if (!committed) unfit(ctx);
     }
 };
 
-// The precise operand's buffers for npad rows, keeping the row blocks below
-// I0 (grow_keep copies on `stream` and waits for it: the fit reserves them
-// before it forks work onto aux_stream, so that the fork is not serialised).
-sbo_status reserve_precise(sbo_ctx *ctx, int64_t npad, int64_t I0) {
-    if (sbo_status st = drain_poz(ctx)) return st;
-    if (precise_kernel_traits(ctx->precise_kernel).int8) {
-        SBO_HIP(grow_keep(ctx, ctx->aoz, sbo::oz_operand_bytes(npad), sbo::oz_operand_bytes(I0 * sbo::kBM)));
-        SBO_HIP(grow_keep(ctx, ctx->eoz, sbo::oz_exp_bytes(npad), sbo::oz_exp_bytes(I0 * sbo::kBM)));
-        SBO_HIP(ctx->koz.reserve(sbo::oz_coord_bytes(npad)));
-    } else {
-        SBO_HIP(grow_keep(ctx, ctx->a64, sbo::f64_operand_bytes(npad), sbo::f64_operand_bytes(I0 * sbo::kBM)));
-        SBO_HIP(ctx->kc64.reserve(sbo::f64_coord_bytes(npad)));
+}  // namespace
+
+// ---- the precise operand (PreciseOperand, sbo_ctx.hpp)
+sbo_status PreciseOperand::drain(sbo_ctx *ctx) {
+    if (pending_) {
+        SBO_HIP(hipEventSynchronize(ev));
+        pending_ = false;
     }
     return SBO_OK;
 }
-
-// The precise sweep's operand (SBO_OPT_PRECISE_KERNEL: f64 tiles or int8
-// digit tiles) for row blocks >= I0 of npad rows, from the f64 inverse and
-// alpha64, on stream s (the buffers grow as in reserve_precise).
-sbo_status pack_precise(sbo_ctx *ctx, hipStream_t s, int64_t npad, int64_t I0) {
-    if (sbo_status st = reserve_precise(ctx, npad, I0)) return st;
+sbo_status PreciseOperand::wait_on(sbo_ctx *ctx, hipStream_t s) const {
+    if (pending_) SBO_HIP(hipStreamWaitEvent(s, ev, 0));
+    return SBO_OK;
+}
+// The buffers for npad rows, keeping the row blocks below the first stale one
+// (grow_keep copies on `stream` and waits for it: the fit reserves them
+// before it forks work onto aux_stream, so that the fork is not serialised).
+sbo_status PreciseOperand::reserve(sbo_ctx *ctx, int64_t npad) {
+    if (sbo_status st = drain(ctx)) return st;
+    const PreciseKernel pk = precise_kernel_traits(ctx->opt.precise_kernel);
+    const int64_t I0 = std::min(st_.start(pk.layout), npad / sbo::kBM);
+    if (pk.int8) {
+        SBO_HIP(grow_keep(ctx, aoz, sbo::oz_operand_bytes(npad), sbo::oz_operand_bytes(I0 * sbo::kBM)));
+        SBO_HIP(grow_keep(ctx, eoz, sbo::oz_exp_bytes(npad), sbo::oz_exp_bytes(I0 * sbo::kBM)));
+        SBO_HIP(koz.reserve(sbo::oz_coord_bytes(npad)));
+    } else {
+        SBO_HIP(grow_keep(ctx, a64, sbo::f64_operand_bytes(npad), sbo::f64_operand_bytes(I0 * sbo::kBM)));
+        SBO_HIP(kc64.reserve(sbo::f64_coord_bytes(npad)));
+    }
+    return SBO_OK;
+}
+// The operand of SBO_OPT_PRECISE_KERNEL's layout (f64 tiles or int8 digit
+// tiles) for npad rows from the first stale row block on, from the f64
+// inverse and alpha64, on stream s; a pack on another stream than `stream`
+// stays in flight (wait_on, drain).
+sbo_status PreciseOperand::update(sbo_ctx *ctx, int64_t npad, hipStream_t s) {
+    const PreciseKernel pk = precise_kernel_traits(ctx->opt.precise_kernel);
+    if (st_.current(npad / sbo::kBM, pk.layout)) return SBO_OK;
+    if (sbo_status st = reserve(ctx, npad)) return st;
+    const int64_t I0 = st_.start(pk.layout);
     const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
-    const PreciseKernel pk = precise_kernel_traits(ctx->precise_kernel);
     if (pk.int8) {
         SBO_HIP(sbo::launch_pack_oz(s, ctx->Linv.as<double>(), ctx->cap, ctx->n, npad, I0, sf2, ctx->x.as<float>(),
-                                    ctx->y.as<float>(), ctx->alpha64.as<double>(), ctx->aoz.as<char>(),
-                                    ctx->eoz.as<int>(), ctx->koz.as<char>(), pk.pairs));
+                                    ctx->y.as<float>(), ctx->alpha64.as<double>(), aoz.as<char>(), eoz.as<int>(),
+                                    koz.as<char>(), pk.pairs));
     } else {
         SBO_HIP(sbo::launch_pack_f64(s, ctx->Linv.as<double>(), ctx->cap, ctx->n, npad, I0, sf2, ctx->x.as<float>(),
-                                     ctx->y.as<float>(), ctx->alpha64.as<double>(), ctx->a64.as<double>(),
-                                     ctx->kc64.as<double>()));
+                                     ctx->y.as<float>(), ctx->alpha64.as<double>(), a64.as<double>(),
+                                     kc64.as<double>()));
+    }
+    st_.mark(pk.layout);
+    if (s != ctx->stream) {
+        SBO_HIP(hipEventRecord(ev, s));
+        pending_ = true;
     }
     return SBO_OK;
 }
 
+namespace {
 // The inverse's accuracy guard (SBO_OPT_INV_CHECK; inv_check.hip).  Launch:
 // on chk_stream once `stream` has finished the inverse, beside the operand
 // packs that follow it (it only reads L, L^-1 and the observations).  The
@@ -527,11 +565,11 @@ sbo_status inverse_check_launch(sbo_ctx *ctx) {
         SBO_HIP(hipEventCreate(&ctx->ev_chk0));
         SBO_HIP(hipEventCreate(&ctx->ev_chk1));
     }
-    SBO_HIP(ctx->chk.reserve(sbo::inv_check_bytes(n)));
+    SBO_HIP(ctx->ws.chk.reserve(sbo::inv_check_bytes(n)));
     float *q = nullptr;
     double *cs = nullptr;
     SBO_HIP(sbo::launch_inv_check(ctx->chk_stream, nullptr, nullptr, 0, n, nullptr, nullptr, nullptr, 0.0, 0.0,
-                                  0.0, ctx->chk.as<void>(), &q, &cs));
+                                  0.0, ctx->ws.chk.as<void>(), &q, &cs));
     static thread_local std::vector<float> hq;   // (lives until the copy below has run)
     hq.assign(2 * kChkGrid * kChkGrid, 0.0f);
     bbox_lattice(ctx->bbox, kChkGrid, hq.data(), hq.data() + kChkGrid * kChkGrid);
@@ -554,7 +592,7 @@ sbo_status inverse_check_launch(sbo_ctx *ctx) {
     const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
     SBO_HIP(sbo::launch_inv_check(ctx->chk_stream, ctx->Linv.as<double>(), ctx->L.as<float>(), ctx->cap, n,
                                   ctx->x.as<float>(), ctx->y.as<float>(), ctx->obs.as<float>(),
-                                  ctx->hyper.prior_mean, sf2, ctx->hyper.length_scale, ctx->chk.as<void>(), nullptr,
+                                  ctx->hyper.prior_mean, sf2, ctx->hyper.length_scale, ctx->ws.chk.as<void>(), nullptr,
                                   nullptr));
     SBO_HIP(hipEventRecord(ctx->ev_chk1, ctx->chk_stream));
     return SBO_OK;
@@ -565,7 +603,7 @@ sbo_status inverse_check_read(sbo_ctx *ctx, sbo_inv_check &r) {
     float *q = nullptr;
     double *cs = nullptr;
     SBO_HIP(sbo::launch_inv_check(ctx->chk_stream, nullptr, nullptr, 0, ctx->n, nullptr, nullptr, nullptr, 0.0, 0.0,
-                                  0.0, ctx->chk.as<void>(), &q, &cs));
+                                  0.0, ctx->ws.chk.as<void>(), &q, &cs));
     constexpr int G = kChkGrid * kChkGrid, Q = kChkQueries;
     double h[4 * Q];
     SBO_HIP(hipMemcpyAsync(h, cs, sizeof(h), hipMemcpyDeviceToHost, ctx->chk_stream));
@@ -628,41 +666,42 @@ struct RefreshPlan {
     bool guard;          // the accuracy guard runs on this inverse
     bool inc_alpha;      // alpha updated from the kept z instead of solved in full
     bool aux;            // alpha and the derived operands go to aux_stream
-    bool eager_x3, eager_f64;
+    bool eager_x3, eager_f64;   // the derived operands brought up to date on aux_stream beside the packs
     int x3_layout;
     bool fused_norms;    // the tile norms ran with the pack (SBO_FUSED_TN)
 };
 RefreshPlan plan_refresh(const sbo_ctx *ctx, int64_t n_old, const FactorHandover &ho, InvAttempt attempt) {
+    const sbo_options &o = ctx->opt;
     RefreshPlan p{};
     p.n = ctx->n;
     p.ld = ctx->cap;
     p.npad = sbo::round_up(p.n, sbo::kBM);
     p.nI = p.npad / sbo::kBM;
     p.sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
-    p.f64 = ctx->inverse_bits == 64;
+    p.f64 = o.inverse_bits == 64;
     p.incr = n_old > 0 && inverse_current(ctx, n_old) && ctx->npad > 0;
     p.n_old = p.incr ? n_old : 0;
     p.I0 = p.n_old / sbo::kBM;
     p.old_tiles = (size_t)sbo::total_tiles(p.I0);
-    p.half_done = p.f64 && ctx->inverse_rec && !p.incr && ho.half_n == p.n;
+    p.half_done = p.f64 && o.inverse_rec && !p.incr && ho.half_n == p.n;
     p.widened = ho.widened_n == p.n;
-    const int want = attempt == kInvDgemm ? 0 : attempt == kInvFullDigits ? ctx->inv_oz : inv_digits(ctx);
+    const int want = attempt == kInvDgemm ? 0 : attempt == kInvFullDigits ? o.inv_oz : inv_digits(ctx);
     if (p.half_done)
         p.inv = ho.half;
-    else if (p.f64 && !p.incr && ctx->inverse_rec)
+    else if (p.f64 && !p.incr && o.inverse_rec)
         p.inv = sbo::plan_inverse(inv_config(ctx, want), p.n, p.ld);
     p.half_slots = p.half_done ? p.inv.half_slots() : 0;
     p.info_slots = sbo::inv_info(p.n).total;
     const bool sliced = p.inv.sliced();
     p.digits = sliced ? want : 0;
     p.guard = p.f64 && !p.incr &&
-              (ctx->inv_check == 2 || attempt == kInvDgemm || (ctx->inv_check == 1 && sliced));
+              (o.inv_check == 2 || attempt == kInvDgemm || (o.inv_check == 1 && sliced));
     p.inc_alpha = p.incr && ctx->z_n == n_old && p.n - n_old <= kAppendInvGemm;
     p.aux = p.f64 && aux_ready(ctx);
-    p.eager_x3 = p.aux && ctx->kernel_variant >= 2;
+    p.eager_x3 = p.aux && o.kernel_variant >= 2;
     p.eager_f64 =
-        p.aux && ctx->precision_opt != 0 && (probe_due(ctx) || ctx->precise || ctx->precision_opt == 1);
-    p.x3_layout = sbo::x3_layout(ctx->kernel_variant);
+        p.aux && o.precision_opt != 0 && (probe_due(ctx) || ctx->precise || o.precision_opt == 1);
+    p.x3_layout = sbo::x3_layout(o.kernel_variant);
     p.fused_norms = p.f64 && SBO_FUSED_TN;
     return p;
 }
@@ -755,9 +794,9 @@ sbo_status refresh_alpha(sbo_ctx *ctx, const RefreshPlan &p) {
     } else {
         // z = L^-1 r and alpha = L^-T z by the own two-pass kernels (one
         // read of the triangle each; rocBLAS dtrmv took 1.4 ms at C4)
-        SBO_HIP(ctx->awork.reserve(sbo::alpha_work_bytes(n)));
+        SBO_HIP(ctx->ws.awork.reserve(sbo::alpha_work_bytes(n)));
         SBO_HIP(sbo::launch_alpha_f64(sa, Li, ld, n, ctx->obs.as<float>(), ctx->hyper.prior_mean, zv, d,
-                                      ctx->awork.as<double>()));
+                                      ctx->ws.awork.as<double>()));
     }
     ctx->z_n = n;
     SBO_HIP(sbo::launch_narrow(sa, d, n, ctx->alpha.as<float>()));
@@ -774,17 +813,11 @@ sbo_status refresh_alpha(sbo_ctx *ctx, const RefreshPlan &p) {
 sbo_status refresh_packs(sbo_ctx *ctx, const RefreshPlan &p) {
     const int64_t n = p.n, ld = p.ld, npad = p.npad, I0 = p.I0;
     double *Li = ctx->Linv.as<double>();
-    ctx->a64_I0 = std::min(ctx->a64_I0, I0);
-    if (!p.incr) ctx->a64_I0 = 0;
-    if (p.eager_x3) {
-        if (p.x3_layout != ctx->x3_layout) ctx->x3_I0 = 0;
-        const int64_t xI0 = std::max<int64_t>(std::min(ctx->x3_I0, I0), 0);
-        SBO_HIP(grow_keep(ctx, ctx->ax3, sbo::x3_operand_bytes(npad), sbo::x3_operand_bytes(xI0 * sbo::kBM)));
-        SBO_HIP(ctx->kc3.reserve(sbo::x3_coord_bytes(npad)));
-        ctx->x3_I0 = xI0;
-    }
-    if (p.eager_f64)   // (before the fork: a growing operand copies and waits on `stream`)
-        if (sbo_status st = reserve_precise(ctx, npad, std::max<int64_t>(ctx->a64_I0, 0))) return st;
+    // (before the fork: a growing operand copies and waits on `stream`)
+    if (p.eager_x3)
+        if (sbo_status st = ctx->split.reserve(ctx, npad, p.x3_layout)) return st;
+    if (p.eager_f64)
+        if (sbo_status st = ctx->pop.reserve(ctx, npad)) return st;
 #if SBO_FUSED_TN
     // the pack and the tile norms in one pass over L^-1 (tile_norm_kernel<true>)
     SBO_HIP(grow_keep(ctx, ctx->tile_lgn, 2 * sizeof(float4) * (size_t)sbo::total_tiles(p.nI),
@@ -797,23 +830,18 @@ sbo_status refresh_packs(sbo_ctx *ctx, const RefreshPlan &p) {
     if (!p.eager_x3 && !p.eager_f64) return SBO_OK;
     SBO_HIP(hipEventRecord(ctx->ev_panel, ctx->stream));
     SBO_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_panel, 0));
-    if (p.eager_x3)
-        SBO_HIP(sbo::launch_pack_x3(ctx->aux_stream, ctx->aug.as<float>(), nullptr, npad, ctx->x3_I0, p.x3_layout,
-                                    ctx->ax3.as<char>(), nullptr));
+    if (p.eager_x3)   // (its coordinates: refresh_join)
+        if (sbo_status st = ctx->split.update(ctx, npad, p.x3_layout, ctx->aux_stream, false)) return st;
     // the row sums too (the skip budget's, read by the host after the
     // tile norms): the tile norms start right after the pack
-    SBO_HIP(ctx->scratch.reserve(sizeof(double) * (size_t)npad));
-    SBO_HIP(sbo::launch_row_l1(ctx->aux_stream, ctx->aug.as<float>(), npad, I0, ctx->scratch.as<double>()));
+    SBO_HIP(ctx->ws.scratch.reserve(sizeof(double) * (size_t)npad));
+    SBO_HIP(sbo::launch_row_l1(ctx->aux_stream, ctx->aug.as<float>(), npad, I0, ctx->ws.scratch.as<double>()));
     SBO_HIP(hipEventRecord(ctx->ev_pack, ctx->aux_stream));   // what the host reads in refresh_skip_budget
     // the precise operand after it, left running past this fit's host
     // sync: only the probe's precise sweep reads it, on the device,
-    // after ev_poz (round 6: 1.7 ms at C4 off the fit's critical path)
-    if (p.eager_f64) {
-        if (sbo_status st = pack_precise(ctx, ctx->aux_stream, npad, std::max<int64_t>(ctx->a64_I0, 0))) return st;
-        ctx->a64_I0 = INT64_MAX;
-        SBO_HIP(hipEventRecord(ctx->ev_poz, ctx->aux_stream));
-        ctx->poz_pending = true;
-    }
+    // after its event (round 6: 1.7 ms at C4 off the fit's critical path)
+    if (p.eager_f64)
+        if (sbo_status st = ctx->pop.update(ctx, npad, ctx->aux_stream)) return st;
     return SBO_OK;
 }
 
@@ -851,8 +879,8 @@ sbo_status refresh_join(sbo_ctx *ctx, const RefreshPlan &p) {
     const int64_t npad = p.npad;
     const bool packs_aux = p.eager_x3 || p.eager_f64;
     if (!packs_aux) {
-        SBO_HIP(ctx->scratch.reserve(sizeof(double) * (size_t)npad));
-        SBO_HIP(sbo::launch_row_l1(ctx->stream, ctx->aug.as<float>(), npad, p.I0, ctx->scratch.as<double>()));
+        SBO_HIP(ctx->ws.scratch.reserve(sizeof(double) * (size_t)npad));
+        SBO_HIP(sbo::launch_row_l1(ctx->stream, ctx->aug.as<float>(), npad, p.I0, ctx->ws.scratch.as<double>()));
     }
     if (!p.fused_norms) {
         SBO_HIP(grow_keep(ctx, ctx->tile_lgn, 2 * sizeof(float4) * (size_t)sbo::total_tiles(p.nI),
@@ -865,8 +893,7 @@ sbo_status refresh_join(sbo_ctx *ctx, const RefreshPlan &p) {
         SBO_HIP(sbo::launch_pack_kcoord(ctx->stream, ctx->x.as<float>(), ctx->y.as<float>(), ctx->alpha.as<float>(),
                                         p.n, npad, p.sf2, ctx->kcoord.as<float>()));
         if (p.eager_x3)  // the split sweep's coordinates (its planes are on aux_stream)
-            SBO_HIP(sbo::launch_pack_x3(ctx->stream, nullptr, ctx->kcoord.as<float>(), npad, 0, 0, nullptr,
-                                        ctx->kc3.as<float>()));
+            if (sbo_status st = ctx->split.pack_coords(ctx, npad, ctx->stream)) return st;
     }
     if (packs_aux) SBO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_pack, 0));  // row sums and packs
     return SBO_OK;
@@ -904,7 +931,7 @@ sbo_status refresh_skip_budget(sbo_ctx *ctx, const RefreshPlan &p) {
     const int64_t n = p.n, r0 = p.I0 * sbo::kBM;
     std::vector<double> rl1((size_t)(p.npad - r0));
     std::vector<float> ha((size_t)n);
-    SBO_HIP(hipMemcpyAsync(rl1.data(), ctx->scratch.as<double>() + r0, sizeof(double) * (p.npad - r0),
+    SBO_HIP(hipMemcpyAsync(rl1.data(), ctx->ws.scratch.as<double>() + r0, sizeof(double) * (p.npad - r0),
                            hipMemcpyDeviceToHost, ctx->stream));
     SBO_HIP(hipMemcpyAsync(ha.data(), ctx->alpha.as<float>(), sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
     SBO_HIP(hipStreamSynchronize(ctx->stream));
@@ -914,7 +941,7 @@ sbo_status refresh_skip_budget(sbo_ctx *ctx, const RefreshPlan &p) {
     double al1 = 0.0;
     for (float v : ha) al1 += std::fabs((double)v);
     ctx->alpha_l1 = al1 * p.sf2;
-    const double tol = std::ldexp(1.0, -ctx->skip_budget), sf = std::sqrt(p.sf2);
+    const double tol = std::ldexp(1.0, -ctx->opt.skip_budget), sf = std::sqrt(p.sf2);
     const double tau2 = tol * sf / 2.0 * 0.99;  // 1 % for the dV^2 term
     skip_cutoffs(ctx->max_row_l1, n, p.nI, tau2, ctx->auto_skip_log2, ctx->lg_tau_v);
     ctx->auto_skip_mean_log2 = skip_cut(ctx->alpha_l1 / (tol * sf));
@@ -923,7 +950,7 @@ sbo_status refresh_skip_budget(sbo_ctx *ctx, const RefreshPlan &p) {
 
 // The tile boxes, then every rocSOLVER info slot read in one sync: a singular
 // block anywhere (the first non-zero slot) is NOT_SPD.  Past that check the
-// packed operand is the context's: npad, and which derived operands are stale.
+// packed operand is the context's: npad.
 sbo_status refresh_read_info(sbo_ctx *ctx, const RefreshPlan &p) {
     SBO_HIP(ctx->kbox.reserve(sizeof(float4) * (size_t)(p.npad / sbo::kBK)));
     SBO_HIP(sbo::launch_tile_boxes(ctx->stream, ctx->x.as<float>(), ctx->y.as<float>(), p.n, p.npad,
@@ -939,13 +966,6 @@ sbo_status refresh_read_info(sbo_ctx *ctx, const RefreshPlan &p) {
     if (hinfo != 0) ctx->linv_n = 0;
     SBO_CHECK(hinfo == 0, SBO_E_NOT_SPD, "trtri: singular factor (info=" + std::to_string(hinfo) + ")");
     ctx->npad = p.npad;
-    if (p.eager_x3) {
-        ctx->x3_I0 = INT64_MAX;
-        ctx->x3_layout = p.x3_layout;
-    } else {
-        ctx->x3_I0 = std::min(ctx->x3_I0, p.I0);  // the split operand is derived lazily (run_tick)
-        if (!p.incr && ctx->a64_I0 != INT64_MAX) ctx->a64_I0 = 0;
-    }
     return SBO_OK;
 }
 
@@ -978,8 +998,12 @@ sbo_status refresh_operand(sbo_ctx *ctx, int64_t n_old = 0, FactorHandover ho = 
     bool fired = false;
     float ms_rejected = 0.0f;
     for (InvAttempt attempt = kInvChosen;;) {
-        if (sbo_status st = drain_poz(ctx)) return st;
+        if (sbo_status st = ctx->pop.drain(ctx)) return st;
         const RefreshPlan p = plan_refresh(ctx, n_old, ho, attempt);
+        // what this refresh rewrites, for the derived operands: the row blocks from
+        // I0 on (a full refresh: I0 = 0, everything); refresh_packs or the tick derives them
+        ctx->split.rows_changed(p.I0);
+        ctx->pop.rows_changed(p.I0);
         if (sbo_status st = refresh_begin(ctx, p)) return st;
         if (p.f64) {
             if (sbo_status st = refresh_inverse(ctx, p)) return st;
@@ -999,7 +1023,7 @@ sbo_status refresh_operand(sbo_ctx *ctx, int64_t n_old = 0, FactorHandover ho = 
         // probe with it only because probe_n is reset first (as fill_and_factor
         // does for new data): probe_precision has just set it to n, and
         // probe_due() would keep the rejected inverse's readings.
-        if (sbo_status st = probe_precision(ctx)) return st;
+        if (sbo_status st = probe_precision(ctx, ctx->opt.precision_opt)) return st;
         if (!p.guard) break;
         bool redo = false;
         if (sbo_status st = refresh_guard_verdict(ctx, attempt, redo)) return st;
@@ -1007,9 +1031,9 @@ sbo_status refresh_operand(sbo_ctx *ctx, int64_t n_old = 0, FactorHandover ho = 
         if (!fired) first = ctx->chk_res;
         fired = true;
         ms_rejected += ctx->chk_res.ms;
-        if (ctx->chk_res.digits < ctx->inv_oz) {
+        if (ctx->chk_res.digits < ctx->opt.inv_oz) {
             attempt = kInvFullDigits;
-            ctx->inv_oz_cur = ctx->inv_oz;   // (the digits this fit's inverse ends up with)
+            ctx->inv_oz_cur = ctx->opt.inv_oz;   // (the digits this fit's inverse ends up with)
         } else {
             attempt = kInvDgemm;
         }
@@ -1043,7 +1067,7 @@ void skip_budget_for(const sbo_ctx *ctx, double tol, int &L, float &lg_tau) {
 void precise_budget(sbo_ctx *ctx) {
     const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
     const double floor_v = std::max(ctx->probe_vmin, 1e-12 * sf2);
-    skip_budget_for(ctx, std::ldexp(1.0, -ctx->skip_budget) * std::min(floor_v, sf2), ctx->p_skip_log2,
+    skip_budget_for(ctx, std::ldexp(1.0, -ctx->opt.skip_budget) * std::min(floor_v, sf2), ctx->p_skip_log2,
                     ctx->p_lg_tau_v);
 }
 
@@ -1075,18 +1099,18 @@ void precise_budget(sbo_ctx *ctx) {
 // inverse (SBO_OPT_INVERSE_BITS 64) and a factor (not an imported state).
 constexpr double kPreciseTol = 5e-6;
 constexpr int kProbeRefBits = 24;
-sbo_status probe_precision(sbo_ctx *ctx) {
+sbo_status probe_precision(sbo_ctx *ctx, int precision) {
     const bool avail = ctx->has_factor && inverse_current(ctx, ctx->n);
-    if (!avail || ctx->precision_opt == 0) {
+    if (!avail || precision == 0) {
         ctx->precise = false;
         if (!avail) ctx->probe_n = 0;
         return SBO_OK;
     }
     const bool fresh = probe_due(ctx);
     if (fresh) {
-        const int G = ctx->probe_grid, MG = G * G;
+        const int G = ctx->opt.probe_grid, MG = G * G;
         const int64_t n = ctx->n;
-        const int MT = (int)std::min<int64_t>(n, ctx->probe_train), M = MG + MT;
+        const int MT = (int)std::min<int64_t>(n, ctx->opt.probe_train), M = MG + MT;
         const int64_t stride = n / MT;     // >= 1
         std::vector<float> h(2 * (size_t)M);
         bbox_lattice(ctx->bbox, G, h.data(), h.data() + M);
@@ -1161,8 +1185,8 @@ sbo_status probe_precision(sbo_ctx *ctx) {
     precise_budget(ctx);
     // a looser skip budget than the default (B < 20: the caller trades
     // accuracy for speed) loosens the threshold by the same factor
-    const double tol = kPreciseTol * std::ldexp(1.0, std::max(0, 20 - ctx->skip_budget));
-    ctx->precise = ctx->precision_opt == 1 || ctx->probe_err > tol;
+    const double tol = kPreciseTol * std::ldexp(1.0, std::max(0, 20 - ctx->opt.skip_budget));
+    ctx->precise = precision == 1 || ctx->probe_err > tol;
     return SBO_OK;
 }
 
@@ -1210,7 +1234,7 @@ constexpr int64_t kSmallTrail = 6144;
 // one until the next look-ahead has waited for it.
 struct PanelPack {
     bool oz = false, x3 = false;
-    int buffer = 0;                // which of ctx->cholx3
+    int buffer = 0;                // which of ctx->ws.cholx3
     const char *planes = nullptr;
 };
 
@@ -1229,23 +1253,24 @@ struct PanelPack {
 // The plan, and the info slots it points at (sized here, so that the pointer
 // is final before the first launch).
 sbo_status chol_plan(sbo_ctx *ctx, int64_t n, int64_t ld, bool early_inv, CholPlan &p) {
+    const sbo_options &o = ctx->opt;
     p.n = n;
     p.ld = ld;
     p.NB = sbo::kCholNB;
-    p.NB2 = std::max<int64_t>(p.NB, (int64_t)ctx->chol_outer / p.NB * p.NB);
-    const int g = ctx->chol_gemm_own;
+    p.NB2 = std::max<int64_t>(p.NB, (int64_t)o.chol_outer / p.NB * p.NB);
+    const int g = o.chol_gemm_own;
     p.update = g == 1   ? CholPlan::kOwnSmall
                : g == 2 ? CholPlan::kOwn
                : g == 3 ? CholPlan::kX3
                : g >= 4 ? CholPlan::kOz
                         : CholPlan::kRocblas;
     p.oz_digits = p.update == CholPlan::kOz ? g : 0;
-    p.chain = ctx->chol_diag;
-    p.own_trsm = ctx->chol_trsm_own;
+    p.chain = o.chol_diag;
+    p.own_trsm = o.chol_trsm_own;
     // early_inv: a fit with the recursive f64 inverse.  Its first half beside
     // the Cholesky with SBO_OPT_INV_OVERLAP = R > 0; otherwise the factor is
     // widened for it on the way.
-    p.early = early_inv && ctx->inv_overlap > 0 && n > ctx->inv_base;
+    p.early = early_inv && o.inv_overlap > 0 && n > o.inv_base;
     if (p.early) p.inv = sbo::plan_inverse(inv_config_early(ctx), n, ld);
     p.h_inv = p.early ? p.inv.nodes[0].h : -1;
     p.widen = early_inv && !p.early;
@@ -1288,20 +1313,20 @@ sbo_status forked_stream(sbo_ctx *ctx, hipStream_t *s, rocblas_handle *hb, int *
 // here on.
 sbo_status chol_streams(sbo_ctx *ctx, const CholPlan &p) {
     if (p.early) {
-        if (sbo_status st = forked_stream(ctx, &ctx->inv_stream, &ctx->blas_inv, &ctx->inv_reserved, ctx->inv_overlap))
-            return st;
+        sbo_status st = forked_stream(ctx, &ctx->inv_stream, &ctx->blas_inv, &ctx->inv_reserved, ctx->opt.inv_overlap);
+        if (st != SBO_OK) return st;
         if (!ctx->ev_half) {
             SBO_HIP(hipEventCreateWithFlags(&ctx->ev_half, hipEventDisableTiming));
             SBO_HIP(hipEventCreateWithFlags(&ctx->ev_inv, hipEventDisableTiming));
         }
     }
-    if (sbo_status st = forked_stream(ctx, &ctx->aux_stream, &ctx->blas_aux, &ctx->aux_reserved, ctx->chol_reserve))
+    if (sbo_status st = forked_stream(ctx, &ctx->aux_stream, &ctx->blas_aux, &ctx->aux_reserved, ctx->opt.chol_reserve))
         return st;
     if (!ctx->ev_panel) {   // (all four together: aux_ready tests the first)
         SBO_HIP(hipEventCreateWithFlags(&ctx->ev_panel, hipEventDisableTiming));
         SBO_HIP(hipEventCreateWithFlags(&ctx->ev_trail, hipEventDisableTiming));
         SBO_HIP(hipEventCreateWithFlags(&ctx->ev_pack, hipEventDisableTiming));
-        SBO_HIP(hipEventCreateWithFlags(&ctx->ev_poz, hipEventDisableTiming));
+        SBO_HIP(hipEventCreateWithFlags(&ctx->pop.ev, hipEventDisableTiming));
     }
     SBO_BLAS(rocblas_set_pointer_mode(ctx->blas, rocblas_pointer_mode_host));
     SBO_BLAS(rocblas_set_pointer_mode(ctx->blas_aux, rocblas_pointer_mode_host));
@@ -1321,7 +1346,7 @@ sbo_status chol_reserve_early(sbo_ctx *ctx, const CholPlan &p) {
 sbo_status chol_reserve_panels(sbo_ctx *ctx, const CholPlan &p) {
     if (p.widen) SBO_HIP(ctx->Linv.reserve(sizeof(double) * (size_t)p.ld * (size_t)p.ld));
     if (p.n <= p.NB2) return SBO_OK;
-    for (sbo::DevBuf &pb : ctx->cholx3) {
+    for (sbo::DevBuf &pb : ctx->ws.cholx3) {
         if (p.update == CholPlan::kX3) SBO_HIP(pb.reserve(sbo::chol_x3_bytes(p.n - p.NB2, p.NB2)));
         if (p.update == CholPlan::kOz) SBO_HIP(pb.reserve(sbo::gz_pack_bytes(p.n - p.NB2, p.NB2, p.oz_digits)));
     }
@@ -1410,7 +1435,7 @@ sbo_status chol_pack_panel(sbo_ctx *ctx, const CholPlan &p, const float *P, int6
     pk.oz = p.update == CholPlan::kOz && W % 64 == 0 && W2 % 128 == 0;
     pk.x3 = p.update == CholPlan::kX3 && W % 32 == 0;
     if (!pk.oz && !pk.x3) return SBO_OK;
-    sbo::DevBuf &pb = ctx->cholx3[buffer];
+    sbo::DevBuf &pb = ctx->ws.cholx3[buffer];
     if (pk.oz) {
         CHOL_HIP(sbo::launch_gz_pack_f32(ctx->stream, p.oz_digits, P, p.ld, m3, W, pb.as<char>()));
     } else {
@@ -1572,7 +1597,7 @@ sbo_status factor_block(sbo_ctx *ctx, float *L, int64_t n, int64_t ld, bool earl
                         FactorHandover &ho) {
     ho = FactorHandover{};
     ho.info = ctx->info.as<rocblas_int>();
-    if (ctx->chol_blocked) {
+    if (ctx->opt.chol_blocked) {
         if (sbo_status st = blocked_potrf(ctx, L, n, ld, early_inv, ho)) return st;
     } else {
         SBO_BLAS(rocsolver_spotrf(ctx->blas, rocblas_fill_lower, (rocblas_int)n, L, (rocblas_int)ld, ho.info));
@@ -1584,7 +1609,7 @@ sbo_status factor_block(sbo_ctx *ctx, float *L, int64_t n, int64_t ld, bool earl
 sbo_status factor_and_refresh(sbo_ctx *ctx) {
     ctx->inv_oz_cur = choose_inv_digits(ctx);
     FactorHandover ho;
-    if (sbo_status st = factor_block(ctx, ctx->L.as<float>(), ctx->n, ctx->cap, ctx->inverse_bits == 64 && ctx->inverse_rec,
+    if (sbo_status st = factor_block(ctx, ctx->L.as<float>(), ctx->n, ctx->cap, ctx->opt.inverse_bits == 64 && ctx->opt.inverse_rec,
                                      FactorOf::kFit, ho))
         return st;
     ctx->has_factor = true;
@@ -1596,7 +1621,7 @@ sbo_status factor_and_refresh(sbo_ctx *ctx) {
 // the fast and of the precise sweep (SBO_OPT_TILE_SKIP -1), the fixed cutoff.
 sbo::SkipPlan skip_rule(const sbo_ctx *ctx, Sweep sweep) {
     const bool precise = sweep != Sweep::kFast;
-    const bool split = !precise && ctx->kernel_variant >= 2;
+    const bool split = !precise && ctx->opt.kernel_variant >= 2;
     sbo::SkipPlan s;
     s.prod_full = split ? 6 : 1;
     s.records = split;
@@ -1613,13 +1638,13 @@ sbo::SkipPlan skip_rule(const sbo_ctx *ctx, Sweep sweep) {
         skip_budget_for(ctx, ctx->probe_ref_tol, s.L, s.lg_tau_v);
         s.L_mean = ctx->auto_skip_mean_log2;
         tile_norms();
-    } else if (ctx->skip_log2 < 0 && !precise) {
+    } else if (ctx->opt.skip_log2 < 0 && !precise) {
         s.L = ctx->auto_skip_log2;
         s.L_mean = ctx->auto_skip_mean_log2;
         s.lg_tau_v = ctx->lg_tau_v;
-        s.levels = sbo::x3_levels(ctx->kernel_variant) ? 1 : 0;
+        s.levels = sbo::x3_levels(ctx->opt.kernel_variant) ? 1 : 0;
         tile_norms();
-    } else if (ctx->skip_log2 < 0) {
+    } else if (ctx->opt.skip_log2 < 0) {
         s.L = ctx->p_skip_log2;
         // the precise sweep's mean 2^8 tighter than the budget's 2^-B sf
         // (absolute): its tiles are the last row block's only, and the mean
@@ -1629,7 +1654,7 @@ sbo::SkipPlan skip_rule(const sbo_ctx *ctx, Sweep sweep) {
         s.lg_tau_v = ctx->p_lg_tau_v;
         tile_norms();
     } else {
-        s.L = ctx->skip_log2;
+        s.L = ctx->opt.skip_log2;
     }
     return s;
 }
@@ -1656,19 +1681,20 @@ void diag_skip_overrides(sbo::SkipPlan &s) {
 // The plan's first half: what the request and the context's options decide
 // before the queries are looked at.
 sbo_status tick_plan(sbo_ctx *ctx, const TickRequest &rq, TickPlan &p) {
+    const sbo_options &o = ctx->opt;
     const Sweep sweep = rq.sweep != Sweep::kCtx ? rq.sweep : ctx->precise ? Sweep::kPrecise : Sweep::kFast;
     SBO_CHECK(sweep == Sweep::kFast || (ctx->has_factor && inverse_current(ctx, ctx->n)),
               SBO_E_STATE, "precise sweep: needs the fit's f64 inverse (not an imported state, INVERSE_BITS 64)");
     const bool full = rq.want == TickWant::kTick;
     p.nI = ctx->npad / sbo::kBM;
-    p.P = ctx->sweep_groups > 0 ? ctx->sweep_groups : std::max(1, ctx->num_cu);
+    p.P = o.sweep_groups > 0 ? o.sweep_groups : std::max(1, ctx->num_cu);
     p.precise = sweep != Sweep::kFast;
-    p.pk = precise_kernel_traits(ctx->precise_kernel);
+    p.pk = precise_kernel_traits(o.precise_kernel);
     // plan only => row-block-major item order, unchunked, no counters
     p.chunked = full && p.precise && p.pk.table;
     p.prof = full && ctx->prof && !rq.quiet;
     p.skip = skip_rule(ctx, sweep);
-    p.skip.order_blk = full && p.precise ? ctx->plan_block : 0;
+    p.skip.order_blk = full && p.precise ? o.plan_block : 0;
     // (a chunk's plan is gone by the acquisition: its empty items' partials are written)
     p.skip.zero_empty = p.chunked;
 #ifdef SBO_DIAG
@@ -1684,10 +1710,10 @@ sbo_status tick_order_queries(sbo_ctx *ctx, const TickRequest &rq, TickPlan &p) 
     const int64_t m = rq.m;
     QueryOrder o{nullptr, qx, qy};
     int64_t ms = m;
-    if (ctx->query_order && p.skip.L > 0 && m > sbo::kBN) {
+    if (ctx->opt.query_order && p.skip.L > 0 && m > sbo::kBN) {
         int32_t *perm = nullptr;
         float *sx = nullptr, *sy = nullptr;
-        if (ctx->query_order == 1) {
+        if (ctx->opt.query_order == 1) {
             // a raster grid's shape, read once per query buffer (one stream
             // sync); the patch layout is valid for any data, so a reused
             // buffer holding other points still gets correct outputs
@@ -1701,7 +1727,7 @@ sbo_status tick_order_queries(sbo_ctx *ctx, const TickRequest &rq, TickPlan &p) 
                 ctx->qgrid_m = m;
             }
         }
-        if (ctx->query_order == 1 && ctx->qgrid.ok) {
+        if (ctx->opt.query_order == 1 && ctx->qgrid.ok) {
             SBO_HIP(sbo::launch_query_grid(ctx->stream, qx, qy, m, ctx->qgrid, ctx->qgwork.as<void>(), &perm, &sx,
                                            &sy));
             o = QueryOrder{perm, sx, sy};
@@ -1756,9 +1782,9 @@ sbo_status tick_build_plan(sbo_ctx *ctx, const TickPlan &p, int64_t c0, int64_t 
 
 // sbo_query_cost: the plan's work per query, no sweep.
 sbo_status tick_cost(sbo_ctx *ctx, const TickPlan &p, float *cost) {
-    SBO_HIP(ctx->qcost.reserve(sizeof(float) * (size_t)p.nQ));
+    SBO_HIP(ctx->ws.qcost.reserve(sizeof(float) * (size_t)p.nQ));
     SBO_HIP(sbo::launch_plan_cost(ctx->stream, ctx->npad, p.ms, p.P, ctx->plan_work.as<void>(), p.perm,
-                                  ctx->qcost.as<float>(), cost));
+                                  ctx->ws.qcost.as<float>(), cost));
     return SBO_OK;
 }
 
@@ -1766,12 +1792,8 @@ sbo_status tick_cost(sbo_ctx *ctx, const TickPlan &p, float *cost) {
 // running on aux_stream, and row blocks repacked since (or all of them, after
 // a change of SBO_OPT_PRECISE_KERNEL's layout) are derived from the f64 inverse.
 sbo_status precise_operand(sbo_ctx *ctx, const TickPlan &p) {
-    if (ctx->poz_pending) SBO_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_poz, 0));
-    if (ctx->a64_I0 < p.nI) {
-        if (sbo_status st = pack_precise(ctx, ctx->stream, ctx->npad, std::max<int64_t>(ctx->a64_I0, 0))) return st;
-        ctx->a64_I0 = INT64_MAX;
-    }
-    return SBO_OK;
+    if (sbo_status st = ctx->pop.wait_on(ctx, ctx->stream)) return st;
+    return ctx->pop.update(ctx, p.nI * sbo::kBM, ctx->stream);
 }
 
 // The int8 sweep over mc positions (nq query blocks) from c0 on under the plan
@@ -1781,11 +1803,11 @@ sbo_status launch_oz(sbo_ctx *ctx, const TickPlan &p, int64_t c0, int64_t mc, in
     const unsigned short *tl = nullptr;
     const int *seg = nullptr;
     sbo::plan_views(ctx->npad, mc, p.P, ctx->plan_work.as<void>(), &desc, &tl, &seg);
-    SBO_HIP(sbo::launch_predict_oz(ctx->stream, ctx->aoz.as<char>(), ctx->eoz.as<int>(), ctx->koz.as<char>(), desc,
-                                   tl, seg, p.P, (int)(p.nI * nq), (int)p.nI, p.qx + c0, p.qy + c0, mc, p.ldp,
-                                   ctx->hyper.length_scale, ctx->hyper.prior_mean, ctx->part.as<double>() + c0,
-                                   ctx->mean.as<double>() + c0, ctx->precise_kernel,
-                                   p.chunked ? ctx->kzt.as<char>() : nullptr));
+    SBO_HIP(sbo::launch_predict_oz(ctx->stream, ctx->pop.aoz.as<char>(), ctx->pop.eoz.as<int>(),
+                                   ctx->pop.koz.as<char>(), desc, tl, seg, p.P, (int)(p.nI * nq), (int)p.nI, p.qx + c0,
+                                   p.qy + c0, mc, p.ldp, ctx->hyper.length_scale, ctx->hyper.prior_mean,
+                                   ctx->part.as<double>() + c0, ctx->mean.as<double>() + c0, ctx->opt.precise_kernel,
+                                   p.chunked ? ctx->ws.kzt.as<char>() : nullptr));
     return SBO_OK;
 }
 
@@ -1796,23 +1818,23 @@ sbo_status launch_oz(sbo_ctx *ctx, const TickPlan &p, int64_t c0, int64_t mc, in
 // item's result does not depend on the chunking (plans are per query block).
 sbo_status sweep_precise_chunked(sbo_ctx *ctx, const TickPlan &p) {
     const size_t per_qb = sbo::oz_table_bytes(ctx->npad, p.pk.pairs);
-    size_t budget = (size_t)ctx->table_mb << 20;
+    size_t budget = (size_t)ctx->opt.table_mb << 20;
     if (budget == 0) {
         // auto: 1/32 of the free device memory, within [256 MiB, 8 GiB]
         // (8 GiB: 9 chunks on the lpsc grid, 1.4 % faster than 2 GiB's 33)
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = size_t(64) << 30;
-        budget = std::clamp(fr / 32 + ctx->kzt.capacity() / 32, size_t(256) << 20, size_t(8) << 30);
+        budget = std::clamp(fr / 32 + ctx->ws.kzt.capacity() / 32, size_t(256) << 20, size_t(8) << 30);
     }
     const int64_t Qc = std::clamp<int64_t>((int64_t)(budget / per_qb), 1, p.nQ);
-    SBO_HIP(ctx->kzt.reserve(per_qb * (size_t)Qc));
+    SBO_HIP(ctx->ws.kzt.reserve(per_qb * (size_t)Qc));
     Bracket br(ctx, ctx->ev_predict, p.prof);
     for (int64_t qb0 = 0; qb0 < p.nQ; qb0 += Qc) {
         const int64_t c0 = qb0 * sbo::kBN, mc = std::min<int64_t>(Qc * sbo::kBN, p.ms - c0);
         const int64_t nq = std::min(Qc, p.nQ - qb0);
         if (sbo_status st = tick_build_plan(ctx, p, c0, mc)) return st;
-        SBO_HIP(sbo::launch_kstar_table(ctx->stream, ctx->koz.as<char>(), p.qx + c0, p.qy + c0, mc, ctx->npad,
-                                        ctx->hyper.length_scale, nq, ctx->kzt.as<char>(), p.pk.pairs));
+        SBO_HIP(sbo::launch_kstar_table(ctx->stream, ctx->pop.koz.as<char>(), p.qx + c0, p.qy + c0, mc, ctx->npad,
+                                        ctx->hyper.length_scale, nq, ctx->ws.kzt.as<char>(), p.pk.pairs));
         if (sbo_status st = launch_oz(ctx, p, c0, mc, nq)) return st;
     }
     return SBO_OK;
@@ -1826,8 +1848,8 @@ sbo_status sweep_precise(sbo_ctx *ctx, const TickPlan &p) {
     const unsigned short *tl = nullptr;
     const int *seg = nullptr;
     sbo::plan_views(ctx->npad, p.ms, p.P, ctx->plan_work.as<void>(), &desc, &tl, &seg);
-    SBO_HIP(sbo::launch_predict_f64(ctx->stream, ctx->a64.as<double>(), ctx->kc64.as<double>(), desc, tl, seg, p.P,
-                                    (int)(p.nI * p.nQ), (int)p.nI, p.qx, p.qy, p.ms, p.ldp, ctx->hyper.length_scale,
+    SBO_HIP(sbo::launch_predict_f64(ctx->stream, ctx->pop.a64.as<double>(), ctx->pop.kc64.as<double>(), desc, tl, seg,
+                                    p.P, (int)(p.nI * p.nQ), (int)p.nI, p.qx, p.qy, p.ms, p.ldp, ctx->hyper.length_scale,
                                     ctx->hyper.prior_mean, ctx->part.as<double>(), ctx->mean.as<double>()));
     return SBO_OK;
 }
@@ -1852,10 +1874,10 @@ sbo_status sweep_fast_x3(sbo_ctx *ctx, const TickPlan &p, int64_t m) {
     const int4 *rec = nullptr;
     sbo::plan_views(ctx->npad, p.ms, p.P, ctx->plan_work.as<void>(), &desc, &tl, &seg, &rec);
     Bracket br(ctx, ctx->ev_predict, p.prof);
-    SBO_HIP(sbo::launch_predict_x3(ctx->stream, ctx->ax3.as<char>(), ctx->kc3.as<float>(), desc, rec, seg, p.P,
-                                   (int)(p.nI * p.nQ), (int)p.nI, qx, qy, p.ms, p.ldp,
+    SBO_HIP(sbo::launch_predict_x3(ctx->stream, ctx->split.ax3.as<char>(), ctx->split.kc3.as<float>(), desc, rec, seg,
+                                   p.P, (int)(p.nI * p.nQ), (int)p.nI, qx, qy, p.ms, p.ldp,
                                    sbo::exp2_coef_f((float)ctx->hyper.length_scale), (float)ctx->hyper.prior_mean,
-                                   ctx->part.as<float>(), ctx->mean.as<float>(), ctx->kernel_variant));
+                                   ctx->part.as<float>(), ctx->mean.as<float>(), ctx->opt.kernel_variant));
     return SBO_OK;
 }
 
@@ -1863,7 +1885,7 @@ sbo_status sweep_fast_f32(sbo_ctx *ctx, const TickPlan &p) {
     Bracket br(ctx, ctx->ev_predict, p.prof);
     SBO_HIP(sbo::launch_predict(ctx->stream, ctx->aug.as<float>(), ctx->kcoord.as<float>(), ctx->npad, p.qx, p.qy,
                                 p.ms, p.ldp, (float)ctx->hyper.length_scale, (float)ctx->hyper.prior_mean,
-                                ctx->part.as<float>(), ctx->mean.as<float>(), ctx->kernel_variant, p.P,
+                                ctx->part.as<float>(), ctx->mean.as<float>(), ctx->opt.kernel_variant, p.P,
                                 ctx->plan_work.as<void>()));
     return SBO_OK;
 }
@@ -1944,7 +1966,7 @@ sbo_status run_tick(sbo_ctx *ctx, const TickRequest &rq, TickPlan *plan_out) {
     if (p.precise) {
         st = precise_operand(ctx, p);
         if (st == SBO_OK) st = p.chunked ? sweep_precise_chunked(ctx, p) : sweep_precise(ctx, p);
-    } else if (ctx->kernel_variant >= 2) {
+    } else if (ctx->opt.kernel_variant >= 2) {
         st = sweep_fast_x3(ctx, p, rq.m);
     } else {
         st = sweep_fast_f32(ctx, p);
@@ -1965,7 +1987,7 @@ static_assert(sizeof(sbo_stream_info) == 96, "sbo_stream_info: the bindings mirr
 }  // namespace
 void stream_budget(const sbo_ctx *ctx, double &var, double &mean) {
     const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
-    const double share = std::ldexp(1.0, -ctx->skip_budget);
+    const double share = std::ldexp(1.0, -ctx->opt.skip_budget);
     var = share * (ctx->precise ? std::min(std::max(ctx->probe_vmin, 1e-12 * sf2), sf2) : sf2);
     mean = share * std::sqrt(sf2);
 }
@@ -1989,11 +2011,11 @@ int stream_cutoff(const sbo_ctx *ctx, const sbo::StreamHead &h, double budget_va
                   double &mean) {
     const double sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
     var = mean = 0.0;
-    if (ctx->skip_log2 >= 0) {
-        if (ctx->skip_log2 > 0 && ctx->skip_log2 < 150) stream_bounds(sf2, ctx->skip_log2, h, var, mean);
-        return ctx->skip_log2;
+    if (ctx->opt.skip_log2 >= 0) {
+        if (ctx->opt.skip_log2 > 0 && ctx->opt.skip_log2 < 150) stream_bounds(sf2, ctx->opt.skip_log2, h, var, mean);
+        return ctx->opt.skip_log2;
     }
-    const double share = std::ldexp(1.0, -ctx->stream_share);
+    const double share = std::ldexp(1.0, -ctx->opt.stream_share);
     for (int L = 16; L < 150; ++L) {
         stream_bounds(sf2, L, h, var, mean);
         if (var <= share * budget_var && mean <= share * budget_mean) return L;
@@ -2018,7 +2040,7 @@ int stream_decide(const sbo_ctx *ctx, int64_t m, int64_t R) {
     if (k.epoch != ctx->fit_epoch || k.precise != ctx->precise) return SBO_STREAM_REFIT;
     if (k.m != m) return SBO_STREAM_QUERIES_CHANGED;
     if (!(fit_state_complete(ctx, ctx->n) && R >= 0)) return SBO_STREAM_NO_INVERSE;
-    if (R > ctx->stream_max_rows) return SBO_STREAM_ROWS_OVER_CAP;
+    if (R > ctx->opt.stream_max_rows) return SBO_STREAM_ROWS_OVER_CAP;
     return SBO_STREAM_UPDATED;
 }
 
@@ -2207,7 +2229,7 @@ SBO_API void sbo_destroy(sbo_ctx *ctx) {
     if (ctx->ev_panel) (void)hipEventDestroy(ctx->ev_panel);
     if (ctx->ev_trail) (void)hipEventDestroy(ctx->ev_trail);
     if (ctx->ev_pack) (void)hipEventDestroy(ctx->ev_pack);
-    if (ctx->ev_poz) (void)hipEventDestroy(ctx->ev_poz);
+    if (ctx->pop.ev) (void)hipEventDestroy(ctx->pop.ev);
     if (ctx->blas_aux) rocblas_destroy_handle(ctx->blas_aux);
     if (ctx->aux_stream) (void)hipStreamDestroy(ctx->aux_stream);
     if (ctx->inv_stream) (void)hipStreamSynchronize(ctx->inv_stream);
@@ -2265,7 +2287,7 @@ sbo_status fill_and_factor(sbo_ctx *ctx, double base_noise) {
             return SBO_OK;
         }
         ctx->hyper.noise_level = base_noise;
-        if (st != SBO_E_NOT_SPD || r >= ctx->jitter_retries) return st;
+        if (st != SBO_E_NOT_SPD || r >= ctx->opt.jitter_retries) return st;
         drain_guard(ctx);   // (the retry rewrites L)
     }
 }
@@ -2280,8 +2302,8 @@ sbo_status fill_and_factor(sbo_ctx *ctx, double base_noise) {
 // tiles for a fit amortised over that many appends.
 sbo_status resort_append(sbo_ctx *ctx, const float *x, const float *y, const float *obs, int64_t b, uint32_t flags) {
     const int64_t n0 = ctx->n, n1 = n0 + b;
-    SBO_HIP(ctx->restage.reserve(sizeof(float) * 3 * (size_t)n1));
-    float *tx = ctx->restage.as<float>(), *ty = tx + n1, *to = ty + n1;
+    SBO_HIP(ctx->ws.restage.reserve(sizeof(float) * 3 * (size_t)n1));
+    float *tx = ctx->ws.restage.as<float>(), *ty = tx + n1, *to = ty + n1;
     const hipMemcpyKind k = dev(flags) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     SBO_HIP(hipMemcpyAsync(tx, ctx->x.as<float>(), sizeof(float) * n0, hipMemcpyDeviceToDevice, ctx->stream));
     SBO_HIP(hipMemcpyAsync(ty, ctx->y.as<float>(), sizeof(float) * n0, hipMemcpyDeviceToDevice, ctx->stream));
@@ -2432,7 +2454,7 @@ SBO_API sbo_status sbo_fit(sbo_ctx *ctx, const float *x, const float *y, const f
     SBO_CHECK(n < (int64_t)1 << 30, SBO_E_INVAL, "sbo_fit: n too large");
     if (sbo_status st = check_hyper(ctx, hyper)) return st;
     SBO_HIP(hipSetDevice(ctx->device));
-    if (sbo_status st = drain_poz(ctx)) return st;   // (a precise pack may still read x, y, L^-1, alpha64)
+    if (sbo_status st = ctx->pop.drain(ctx)) return st;   // (a precise pack may still read x, y, L^-1, alpha64)
     FitCommit fc(ctx);
     ctx->hyper = hyper;
     ctx->n = n;
@@ -2464,13 +2486,13 @@ SBO_API sbo_status sbo_append(sbo_ctx *ctx, const float *x, const float *y, cons
     SBO_CHECK(b >= 0, SBO_E_INVAL, "sbo_append: b must be >= 0");
     if (b == 0) return SBO_OK;
     SBO_HIP(hipSetDevice(ctx->device));
-    if (sbo_status st = drain_poz(ctx)) return st;   // (a precise pack may still read x, y, L^-1, alpha64)
+    if (sbo_status st = ctx->pop.drain(ctx)) return st;   // (a precise pack may still read x, y, L^-1, alpha64)
     const int64_t n0 = ctx->n, n1 = n0 + b;
     SBO_CHECK(n1 < (int64_t)1 << 30, SBO_E_INVAL, "sbo_append: n too large");
     FitCommit fc(ctx);
     // SBO_OPT_RESORT: once the points appended since the last k-d sort exceed
     // resort_pct % of the sorted ones, re-sort and refactor all of them
-    if (ctx->resort_pct > 0 && ctx->spatial_order != 0 && (n1 - ctx->n_sorted) * 100 > ctx->n_sorted * ctx->resort_pct) {
+    if (ctx->opt.resort_pct > 0 && ctx->opt.spatial_order != 0 && (n1 - ctx->n_sorted) * 100 > ctx->n_sorted * ctx->opt.resort_pct) {
         if (sbo_status st = resort_append(ctx, x, y, obs, b, flags)) return st;
         return fc.commit(finish(ctx, flags));
     }
@@ -2798,7 +2820,7 @@ SBO_API sbo_status sbo_debug_x3_stamps(sbo_ctx *ctx, double *cycles, int n) {
 
 SBO_API sbo_status sbo_debug_x3_operand(sbo_ctx *ctx, void *host_buf, int64_t cap, int64_t *bytes) {
     if (!ctx || !bytes || cap < 0) return SBO_E_INVAL;
-    if (!ctx->fitted || ctx->kernel_variant < 2) return SBO_E_INVAL;
+    if (!ctx->fitted || ctx->opt.kernel_variant < 2) return SBO_E_INVAL;
     SBO_HIP(hipSetDevice(ctx->device));
     // (the eager derivation of a fit or an append runs on aux_stream)
     SBO_HIP(hipStreamSynchronize(ctx->aux_stream));
@@ -2807,8 +2829,19 @@ SBO_API sbo_status sbo_debug_x3_operand(sbo_ctx *ctx, void *host_buf, int64_t ca
     *bytes = need;
     if (!host_buf) return SBO_OK;
     if (cap < need) return SBO_E_INVAL;
-    SBO_HIP(hipMemcpyAsync(host_buf, ctx->ax3.as<char>(), (size_t)need, hipMemcpyDeviceToHost, ctx->stream));
+    SBO_HIP(hipMemcpyAsync(host_buf, ctx->split.ax3.as<char>(), (size_t)need, hipMemcpyDeviceToHost, ctx->stream));
     SBO_HIP(hipStreamSynchronize(ctx->stream));
+    return SBO_OK;
+}
+
+SBO_API sbo_status sbo_debug_state(const sbo_ctx *ctx, int64_t *out, int cap) {
+    if (!ctx || !out || cap < 0) return SBO_E_INVAL;
+    const int xl = sbo::x3_layout(ctx->opt.kernel_variant), pl = precise_kernel_traits(ctx->opt.precise_kernel).layout;
+    const sbo::OperandState &xs = ctx->split.state(), &ps = ctx->pop.state();
+    const int64_t v[13] = {ctx->n, ctx->npad, ctx->fitted, ctx->has_factor, ctx->linv_n, ctx->z_n, ctx->probe_n,
+                           xs.stale_from(xl), xs.layout(), ps.stale_from(pl), ps.layout(), ctx->pop.in_flight(),
+                           (int64_t)ctx->fit_epoch};
+    std::copy(v, v + std::min(cap, 13), out);
     return SBO_OK;
 }
 
@@ -3001,54 +3034,54 @@ SBO_API sbo_status sbo_set_option(sbo_ctx *ctx, int option, int64_t value) {
     switch (option) {
         case SBO_OPT_CHOLESKY:
             SBO_CHECK(value >= 0 && value <= 2, SBO_E_INVAL, "SBO_OPT_CHOLESKY must be 0, 1 or 2");
-            ctx->chol_blocked = value != 0;
-            ctx->chol_trsm_own = value == 1;
+            ctx->opt.chol_blocked = value != 0;
+            ctx->opt.chol_trsm_own = value == 1;
             return SBO_OK;
         case SBO_OPT_JITTER_RETRIES:
             SBO_CHECK(value >= 0 && value <= 8, SBO_E_INVAL, "SBO_OPT_JITTER_RETRIES must be in [0, 8]");
-            ctx->jitter_retries = (int)value;
+            ctx->opt.jitter_retries = (int)value;
             return SBO_OK;
         case SBO_OPT_INVERSE:
             SBO_CHECK(value == 0 || value == 1, SBO_E_INVAL, "SBO_OPT_INVERSE must be 0 or 1");
-            ctx->inverse_rec = value != 0;
+            ctx->opt.inverse_rec = value != 0;
             return SBO_OK;
         case SBO_OPT_INVERSE_BITS:
             SBO_CHECK(value == 32 || value == 64, SBO_E_INVAL, "SBO_OPT_INVERSE_BITS must be 32 or 64");
-            ctx->inverse_bits = (int)value;
+            ctx->opt.inverse_bits = (int)value;
             return SBO_OK;
         case SBO_OPT_SPATIAL_ORDER:
             SBO_CHECK(value >= 0 && value <= 3, SBO_E_INVAL, "SBO_OPT_SPATIAL_ORDER must be 0, 1, 2 or 3");
-            ctx->spatial_order = (int)value;
+            ctx->opt.spatial_order = (int)value;
             return SBO_OK;
         case SBO_OPT_QUERY_ORDER:
             SBO_CHECK(value >= 0 && value <= 2, SBO_E_INVAL, "SBO_OPT_QUERY_ORDER must be 0, 1 or 2");
-            ctx->query_order = (int)value;
+            ctx->opt.query_order = (int)value;
             return SBO_OK;
         case SBO_OPT_SKIP_BUDGET:
             SBO_CHECK(value >= 10 && value <= 60, SBO_E_INVAL, "SBO_OPT_SKIP_BUDGET must be in [10, 60]");
-            ctx->skip_budget = (int)value;
+            ctx->opt.skip_budget = (int)value;
             return SBO_OK;
         case SBO_OPT_SWEEP_GROUPS:
             SBO_CHECK(value >= 0 && value <= 65536, SBO_E_INVAL, "SBO_OPT_SWEEP_GROUPS must be in [0, 65536]");
-            ctx->sweep_groups = (int)value;
+            ctx->opt.sweep_groups = (int)value;
             return SBO_OK;
         case SBO_OPT_KERNEL_VARIANT:
             SBO_CHECK(sbo::variant_allowed((int)value), SBO_E_INVAL,
                       "SBO_OPT_KERNEL_VARIANT: not a sweep of this build (product: 0, 1, 3, 22)");
-            ctx->kernel_variant = (int)value;
+            ctx->opt.kernel_variant = (int)value;
             return SBO_OK;
         case SBO_OPT_INV_BASE:
             SBO_CHECK(value >= 1024 && value <= 8192, SBO_E_INVAL, "SBO_OPT_INV_BASE must be in [1024, 8192]");
-            ctx->inv_base = value / 128 * 128;   // (the split lands on multiples of it: Cholesky block columns)
+            ctx->opt.inv_base = value / 128 * 128;   // (the split lands on multiples of it: Cholesky block columns)
             return SBO_OK;
         case SBO_OPT_INV_LEAVES:
             SBO_CHECK(value >= 0 && value <= 2, SBO_E_INVAL, "SBO_OPT_INV_LEAVES must be 0, 1 or 2");
-            ctx->inv_batched = value >= 1;
-            ctx->inv_leaves_own = value == 2;
+            ctx->opt.inv_batched = value >= 1;
+            ctx->opt.inv_leaves_own = value == 2;
             return SBO_OK;
         case SBO_OPT_INV_PANELS:
             SBO_CHECK(value >= 1 && value <= 64, SBO_E_INVAL, "SBO_OPT_INV_PANELS must be in [1, 64]");
-            ctx->inv_panels = value;
+            ctx->opt.inv_panels = value;
             return SBO_OK;
         case SBO_OPT_CHOL_GEMM:
 #ifdef SBO_DIAG
@@ -3059,26 +3092,26 @@ SBO_API sbo_status sbo_set_option(sbo_ctx *ctx, int option, int64_t value) {
             SBO_CHECK(value >= 0 && value <= 5 && value != 3, SBO_E_INVAL,
                       "SBO_OPT_CHOL_GEMM must be 0, 1, 2, 4 or 5");
 #endif
-            ctx->chol_gemm_own = (int)value;
+            ctx->opt.chol_gemm_own = (int)value;
             return SBO_OK;
         case SBO_OPT_CHOL_DIAG:
             SBO_CHECK(value >= 0 && value <= 2, SBO_E_INVAL, "SBO_OPT_CHOL_DIAG must be 0, 1 or 2");
-            ctx->chol_diag = (int)value;
+            ctx->opt.chol_diag = (int)value;
             return SBO_OK;
         case SBO_OPT_CHOL_OUTER:
             SBO_CHECK(value >= sbo::kCholNB && value <= 4096 && value % sbo::kCholNB == 0, SBO_E_INVAL,
                       "SBO_OPT_CHOL_OUTER must be a multiple of 128 in [128, 4096]");
-            ctx->chol_outer = (int)value;
+            ctx->opt.chol_outer = (int)value;
             return SBO_OK;
         case SBO_OPT_INV_OVERLAP:
             SBO_CHECK(value >= 0 && value < ctx->num_cu, SBO_E_INVAL,
                       "SBO_OPT_INV_OVERLAP must be in [0, compute units)");
-            ctx->inv_overlap = (int)value;
+            ctx->opt.inv_overlap = (int)value;
             return SBO_OK;
         case SBO_OPT_CHOL_RESERVE:
             SBO_CHECK(value >= 0 && value < ctx->num_cu, SBO_E_INVAL,
                       "SBO_OPT_CHOL_RESERVE must be in [0, compute units)");
-            ctx->chol_reserve = (int)value;
+            ctx->opt.chol_reserve = (int)value;
             return SBO_OK;
         case SBO_OPT_PRECISE_KERNEL:
 #ifdef SBO_DIAG
@@ -3089,57 +3122,54 @@ SBO_API sbo_status sbo_set_option(sbo_ctx *ctx, int option, int64_t value) {
                       "SBO_OPT_PRECISE_KERNEL must be 0 (f64 MFMA), 1 (int8), 3 (int8, K* table) or 4 (int8, "
                       "k-tile pairs)");
 #endif
-            // another operand layout: derive it all
-            if (precise_kernel_traits(ctx->precise_kernel).layout != precise_kernel_traits((int)value).layout)
-                ctx->a64_I0 = 0;
-            ctx->precise_kernel = (int)value;
+            ctx->opt.precise_kernel = (int)value;   // (another layout: the operand derives all of it, PreciseOperand)
             return SBO_OK;
         case SBO_OPT_INV_OZ:
             SBO_CHECK(value == 0 || (value >= 4 && value <= 6), SBO_E_INVAL, "SBO_OPT_INV_OZ must be 0, 4, 5 or 6");
-            ctx->inv_oz = (int)value;
+            ctx->opt.inv_oz = (int)value;
             ctx->inv_oz_cur = ctx->inv_oz_next = 0;
             ctx->inv_oz_pinned = false;
             return SBO_OK;
         case SBO_OPT_INV_OZ_ADAPT:
             SBO_CHECK(value == 0 || value == 1, SBO_E_INVAL, "SBO_OPT_INV_OZ_ADAPT must be 0 or 1");
-            ctx->inv_oz_adapt = (int)value;
+            ctx->opt.inv_oz_adapt = (int)value;
             ctx->inv_oz_next = 0;
             ctx->inv_oz_pinned = false;
             return SBO_OK;
         case SBO_OPT_INV_OZ_MIN:
             SBO_CHECK(value == 0 || value == 2048 || value == 4096 || value == 8192, SBO_E_INVAL,
                       "SBO_OPT_INV_OZ_MIN must be 0 (automatic), 2048, 4096 or 8192");
-            ctx->inv_oz_min = value;
+            ctx->opt.inv_oz_min = value;
             return SBO_OK;
         case SBO_OPT_PROBE_SIZE:
             SBO_CHECK(value >= 0 && (value >> 16) >= 4 && (value >> 16) <= 256 && (value & 0xffff) >= 1 &&
                           (value & 0xffff) <= 16384,
                       SBO_E_INVAL, "SBO_OPT_PROBE_SIZE must be grid << 16 | train (grid 4..256, train 1..16384)");
-            ctx->probe_grid = (int)(value >> 16);
-            ctx->probe_train = (int)(value & 0xffff);
+            ctx->opt.probe_grid = (int)(value >> 16);
+            ctx->opt.probe_train = (int)(value & 0xffff);
             ctx->probe_n = 0;   // probe again at the next refresh
             return SBO_OK;
         case SBO_OPT_PLAN_BLOCK:
             SBO_CHECK(value == 0 || ((value >> 8) >= 1 && (value >> 8) <= 64 && (value & 255) >= 1), SBO_E_INVAL,
                       "SBO_OPT_PLAN_BLOCK must be 0 or bi << 8 | bq with 1 <= bi <= 64, 1 <= bq <= 255");
-            ctx->plan_block = (int)value;
+            ctx->opt.plan_block = (int)value;
             return SBO_OK;
         case SBO_OPT_INV_CHECK:
             SBO_CHECK(value >= 0 && value <= 2, SBO_E_INVAL, "SBO_OPT_INV_CHECK must be 0, 1 or 2");
-            ctx->inv_check = (int)value;
+            ctx->opt.inv_check = (int)value;
             return SBO_OK;
         case SBO_OPT_TABLE_MB:
             SBO_CHECK(value >= 0 && value <= (int64_t(1) << 20), SBO_E_INVAL,
                       "SBO_OPT_TABLE_MB must be in [0, 2^20] (0: automatic)");
-            ctx->table_mb = value;
+            ctx->opt.table_mb = value;
             return SBO_OK;
         case SBO_OPT_REPROBE:
             SBO_CHECK(value >= 0 && value <= 1000, SBO_E_INVAL, "SBO_OPT_REPROBE must be in [0, 1000] (percent)");
-            ctx->reprobe_pct = (int)value;
+            ctx->opt.reprobe_pct = (int)value;
             return SBO_OK;
         case SBO_OPT_RESORT:
             SBO_CHECK(value >= 0 && value <= 1000, SBO_E_INVAL, "SBO_OPT_RESORT must be in [0, 1000] (percent)");
-            ctx->resort_pct = (int)value;
+            ctx->opt.resort_pct = (int)value;
             return SBO_OK;
         case SBO_OPT_PRECISION:
             SBO_CHECK(value >= -1 && value <= 1, SBO_E_INVAL, "SBO_OPT_PRECISION must be -1 (auto), 0 or 1");
@@ -3148,38 +3178,38 @@ SBO_API sbo_status sbo_set_option(sbo_ctx *ctx, int option, int64_t value) {
                 const bool avail = ctx->has_factor && inverse_current(ctx, ctx->n);
                 SBO_CHECK(value != 1 || avail, SBO_E_STATE,
                           "SBO_OPT_PRECISION 1: needs the fit's f64 inverse (not an imported state)");
-                ctx->precision_opt = (int)value;
+                ctx->opt.precision_opt = (int)value;
                 if (value != 0 && avail) {
                     SBO_HIP(hipSetDevice(ctx->device));
-                    if (sbo_status st = probe_precision(ctx)) return st;
+                    if (sbo_status st = probe_precision(ctx, ctx->opt.precision_opt)) return st;
                 } else {
                     ctx->precise = false;
                 }
                 return SBO_OK;
             }
-            ctx->precision_opt = (int)value;
+            ctx->opt.precision_opt = (int)value;
             return SBO_OK;
         case SBO_OPT_STREAM_SHARE:
             SBO_CHECK(value >= 0 && value <= 20, SBO_E_INVAL, "SBO_OPT_STREAM_SHARE must be in [0, 20]");
-            ctx->stream_share = (int)value;
+            ctx->opt.stream_share = (int)value;
             return SBO_OK;
         case SBO_OPT_STREAM_MAX_ROWS:
             SBO_CHECK(value >= 0 && value <= 65536, SBO_E_INVAL, "SBO_OPT_STREAM_MAX_ROWS must be in [0, 65536]");
-            ctx->stream_max_rows = value;
+            ctx->opt.stream_max_rows = value;
             return SBO_OK;
         case SBO_OPT_EVIDENCE_BUDGET:
             SBO_CHECK(value == 0 || (value >= 10 && value <= 60), SBO_E_INVAL,
                       "SBO_OPT_EVIDENCE_BUDGET must be 0 (dense) or in [10, 60]");
-            ctx->evidence_budget = (int)value;
+            ctx->opt.evidence_budget = (int)value;
             return SBO_OK;
         case SBO_OPT_WHATIF_GEMM:
             SBO_CHECK(value == 0 || value == 1, SBO_E_INVAL, "SBO_OPT_WHATIF_GEMM must be 0 (dtrmm) or 1 (dgemm)");
-            ctx->whatif_gemm = (int)value;
+            ctx->opt.whatif_gemm = (int)value;
             return SBO_OK;
         case SBO_OPT_TILE_SKIP:
             SBO_CHECK(value == -1 || value == 0 || (value >= 16 && value <= 1000), SBO_E_INVAL,
                       "SBO_OPT_TILE_SKIP must be -1 (auto), 0 (dense) or a cutoff exponent in [16, 1000]");
-            ctx->skip_log2 = (int)value;
+            ctx->opt.skip_log2 = (int)value;
             return SBO_OK;
     }
     ctx->err = "unknown option " + std::to_string(option);
@@ -3204,10 +3234,7 @@ SBO_API sbo_status sbo_trim(sbo_ctx *ctx) {
     if (ctx->aux_stream) SBO_HIP(hipStreamSynchronize(ctx->aux_stream));
     if (ctx->inv_stream) SBO_HIP(hipStreamSynchronize(ctx->inv_stream));
     if (ctx->chk_stream) SBO_HIP(hipStreamSynchronize(ctx->chk_stream));
-    for (sbo::DevBuf *b : {&ctx->scratch, &ctx->gzws, &ctx->gzws_aux, &ctx->chk, &ctx->restage, &ctx->kzt, &ctx->qcost,
-                           &ctx->awork, &ctx->evws, &ctx->evitems, &ctx->wiws, &ctx->smws,
-                           &ctx->cholx3[0], &ctx->cholx3[1]})
-        b->release();
+    ctx->ws.release();
     return SBO_OK;
 }
 
@@ -3252,28 +3279,16 @@ SBO_API sbo_status sbo_warmup(sbo_ctx *ctx, int64_t n_cap, int64_t m_cap, sbo_hy
             hipMemcpy(dq.as<float>(), gq.data(), sizeof(float) * 2 * (size_t)m, hipMemcpyHostToDevice) != hipSuccess)
             st = SBO_E_OOM;
     }
-    const int popt = ctx->precision_opt;
     for (int prec = 0; prec <= 1 && st == SBO_OK; ++prec) {
         if (prec == 1 && !inverse_current(ctx, ctx->n)) break;
-        ctx->precision_opt = prec;
-        if ((st = probe_precision(ctx)) != SBO_OK) break;
+        if ((st = probe_precision(ctx, prec)) != SBO_OK) break;
         st = sbo_tick(ctx, dq.as<float>(), dq.as<float>() + m, m, 2.0, 0.0, SBO_SCORE_WIDTH, 0, nullptr, nullptr,
                       nullptr, nullptr, nullptr, dk.as<sbo_key>(), SBO_DEVICE_PTRS);
     }
-    ctx->precision_opt = popt;
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     // unfitted again; the workspaces keep their sizes (the query buffers go:
     // forget the grid layout cached by their addresses)
-    ctx->fitted = false;
-    ctx->has_factor = false;
-    ctx->n = 0;
-    ctx->linv_n = 0;
-    ctx->z_n = 0;
-    ctx->probe_n = 0;
-    ctx->precise = false;
-    ctx->n_sorted = 0;
-    ctx->order.clear();
-    ctx->chk_res = sbo_inv_check{};
+    unfit(ctx);
     ctx->inv_oz_next = 0;   // (the synthetic fit's guard reading says nothing about the real data)
     ctx->inv_oz_hist_n = 0;
     ctx->inv_oz_pinned = false;
@@ -3295,7 +3310,7 @@ SBO_API sbo_status sbo_get_probe(const sbo_ctx *ctx, sbo_probe *out) {
     if (!ctx->fitted) return SBO_E_STATE;
     *out = sbo_probe{};
     out->precise = ctx->precise ? 1 : 0;
-    out->precise_kernel = ctx->precise_kernel;
+    out->precise_kernel = ctx->opt.precise_kernel;
     out->n_at_probe = ctx->probe_n;
     if (ctx->probe_n == 0) {
         out->err = out->err_grid = out->err_train = -1.0;
@@ -3315,7 +3330,7 @@ SBO_API sbo_status sbo_get_probe(const sbo_ctx *ctx, sbo_probe *out) {
 
 SBO_API sbo_status sbo_get_skip(const sbo_ctx *ctx, int *cutoff_log2, double *max_row_l1, double *alpha_l1) {
     if (!ctx) return SBO_E_INVAL;
-    if (cutoff_log2) *cutoff_log2 = ctx->skip_log2 < 0 ? ctx->auto_skip_log2 : ctx->skip_log2;
+    if (cutoff_log2) *cutoff_log2 = ctx->opt.skip_log2 < 0 ? ctx->auto_skip_log2 : ctx->opt.skip_log2;
     if (max_row_l1) *max_row_l1 = ctx->max_row_l1;
     if (alpha_l1) *alpha_l1 = ctx->alpha_l1;
     return SBO_OK;
@@ -3520,7 +3535,7 @@ StateHeader state_layout(const sbo_ctx *ctx) {
     h.auto_skip_log2 = ctx->auto_skip_log2;
     h.auto_skip_mean_log2 = ctx->auto_skip_mean_log2;
     h.lg_tau_v = ctx->lg_tau_v;
-    h.spatial_order = ctx->spatial_order;
+    h.spatial_order = ctx->opt.spatial_order;
     state_offsets(h);
     return h;
 }
@@ -3570,7 +3585,7 @@ SBO_API sbo_status sbo_import_state(sbo_ctx *ctx, const void *dev_buf, int64_t b
     if (!ctx) return SBO_E_INVAL;
     SBO_CHECK(dev_buf && bytes >= (int64_t)sizeof(StateHeader), SBO_E_INVAL, "sbo_import_state: bad buffer");
     SBO_HIP(hipSetDevice(ctx->device));
-    if (sbo_status st = drain_poz(ctx)) return st;   // (a precise pack may still read x, y, L^-1, alpha64)
+    if (sbo_status st = ctx->pop.drain(ctx)) return st;   // (a precise pack may still read x, y, L^-1, alpha64)
     const char *b = static_cast<const char *>(dev_buf);
     StateHeader h;
     SBO_HIP(hipMemcpyAsync(&h, b, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
@@ -3595,11 +3610,9 @@ SBO_API sbo_status sbo_import_state(sbo_ctx *ctx, const void *dev_buf, int64_t b
         }
     }
     FitCommit fc(ctx);
-    ++ctx->fit_epoch;
-    ctx->has_factor = false;
-    ctx->precise = false;   // no f64 inverse travels: an imported state ticks with the fast sweep
-    ctx->probe_n = 0;
-    ctx->linv_n = 0;
+    // no factor and no f64 inverse travel: an imported state ticks with the
+    // fast sweep and derives its split operand at the first tick
+    unfit(ctx);
     const int64_t nt = h.npad / sbo::kBK;
     const size_t aug_bytes = 4 * (size_t)sbo::total_tiles(h.npad / sbo::kBM) * sbo::kTileFloats;
     SBO_HIP(ctx->aug.reserve(aug_bytes));
@@ -3621,8 +3634,6 @@ SBO_API sbo_status sbo_import_state(sbo_ctx *ctx, const void *dev_buf, int64_t b
         std::vector<uint8_t> seen((size_t)h.n, 0);
         for (int64_t v : ctx->order) {
             if (v < 0 || v >= h.n || seen[(size_t)v]) {
-                ctx->order.clear();
-                ctx->n = 0;
                 ctx->err = "sbo_import_state: training order is not a permutation";
                 return SBO_E_INVAL;
             }
@@ -3639,8 +3650,7 @@ SBO_API sbo_status sbo_import_state(sbo_ctx *ctx, const void *dev_buf, int64_t b
     ctx->auto_skip_log2 = h.auto_skip_log2;
     ctx->auto_skip_mean_log2 = h.auto_skip_mean_log2;
     ctx->lg_tau_v = h.lg_tau_v;
-    ctx->spatial_order = h.spatial_order;
-    ctx->x3_I0 = 0;
+    if (sbo_status st = sbo_set_option(ctx, SBO_OPT_SPATIAL_ORDER, h.spatial_order)) return st;
     return fc.commit(SBO_OK);
 }
 

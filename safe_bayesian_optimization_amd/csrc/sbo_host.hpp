@@ -1,5 +1,5 @@
 // sbo_host.hpp -- what the host sources of libsbo.so share beside the context
-// (sbo_internal.hpp): the status macros of a function that has `ctx` in scope
+// (sbo_ctx.hpp): the status macros of a function that has `ctx` in scope
 // and returns sbo_status, the tests of the fitted state, the scratch carver,
 // the pooled events and the copy-out of a versioned info struct.  Host only.
 #pragma once
@@ -10,7 +10,7 @@
 #include <utility>
 #include <vector>
 
-#include "sbo_internal.hpp"
+#include "sbo_ctx.hpp"
 
 #define SBO_HIP(expr)                                                                   \
     do {                                                                                \
@@ -40,7 +40,7 @@
 
 // Has a blocked factorization run on this context?  Its set-up (chol_streams)
 // leaves aux_stream, its rocBLAS handle and the events ev_panel, ev_trail,
-// ev_pack, ev_poz, which the inverse's two-lane top level and the refresh's
+// ev_pack, pop.ev, which the inverse's two-lane top level and the refresh's
 // side work use without making them.  The four events are created together,
 // so ev_panel stands for all of them.  The answer depends on history, not on
 // the options now: a context whose fits so far all ran rocSOLVER's spotrf
@@ -52,7 +52,7 @@ inline bool dev(uint32_t flags) { return (flags & SBO_DEVICE_PTRS) != 0; }
 
 // The fit's f64 inverse holds exactly n rows: L^-1 in Linv, computed in f64
 // (SBO_OPT_INVERSE_BITS 64), current for the first n training points.
-inline bool inverse_current(const sbo_ctx *ctx, int64_t n) { return ctx->inverse_bits == 64 && ctx->linv_n == n; }
+inline bool inverse_current(const sbo_ctx *ctx, int64_t n) { return ctx->opt.inverse_bits == 64 && ctx->linv_n == n; }
 
 // The fit's factor, f64 inverse and z = L^-1 (y - m0) hold all n rows: what the
 // readers of the fitted state (the streaming update, sbo_evidence, sbo_whatif)
