@@ -19,7 +19,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "sbo_internal.hpp"
+#include "plan_walk.hpp"
 
 namespace sbo {
 namespace {
@@ -1276,7 +1276,6 @@ __global__ __launch_bounds__(kBM, 2) void tile_norm_kernel(const float *__restri
     __shared__ double red[2][kBM / 64];
     __shared__ double fred[3][kBM / 64], rwm[3][kBM / 64];   // per wave: |.|_F^2 sums, row-sum maxima
     const int64_t tile = t0 + blockIdx.x;
-    const float *t = aug + tile * kTileFloats;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     __shared__ float out[6];                     // (rows, spectral) of A; of A1; of A2 (LDS: a plane-indexed array)
     double lg_fro_a = -1000.0;
@@ -1300,7 +1299,7 @@ __global__ __launch_bounds__(kBM, 2) void tile_norm_kernel(const float *__restri
     // pieces' maxima, then the staging)
     auto load16 = [&](int q, float (&v)[16]) {
         const float4 *src = FUSED ? reinterpret_cast<const float4 *>(augw + tile * kTileFloats + q * 64 * kBK + 16 * tid)
-                                  : reinterpret_cast<const float4 *>(t + q * 64 * kBK + 16 * tid);
+                                  : reinterpret_cast<const float4 *>(aug + tile * kTileFloats + q * 64 * kBK + 16 * tid);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float4 f = src[j];
@@ -1719,10 +1718,7 @@ __global__ void tile_box_kernel(const float *__restrict__ x, const float *__rest
 constexpr int kStageFloats = kTileFloats + 3 * kBK;
 constexpr int kPredictWaves = kBN / 16;
 constexpr int kPredictThreads = 64 * kPredictWaves;
-constexpr int kDescWindow = 64;          // item descriptors (int4) per 1 KiB LDS window
-constexpr int kListWindow = 512;         // tile indices (u16) per 1 KiB LDS window
-constexpr int kRecWindow = 64;           // split-sweep step records (int4) per 1 KiB LDS window
-constexpr int kSmemFloats = 2 * kStageFloats + 2 * 256 + 2 * 256;  // stages + 2 desc + 2 list windows
+constexpr int kSmemFloats = 2 * kStageFloats + kPlanWalkLds / 4;  // stages + the plan's windows
 constexpr int kBudgetFloor = 40;        // bounds below 2^-40 of the budget share bin 0
 constexpr int kBinsPerBit = 4;
 constexpr int kBudgetBins = kBudgetFloor * kBinsPerBit + 2;
@@ -1731,8 +1727,6 @@ constexpr int kPlanWaves = kPlanThreads / 64;
 constexpr int kPlanD2 = 2048;           // k-tile distances cached in LDS (N <= 131072; beyond: recomputed)
 constexpr int kPlanBinCache = 256;
 constexpr int kPlanWriteBlocks = 4096;  // plan_write grid cap (four waves each, grid-stride over items)      // per wave: the increment bins of a row block's first tiles (nI <= 64: all)
-constexpr int kPlanKeyShift = 40;       // plan key: kept-tile count (low 40 bits) | non-empty (high bits)
-constexpr unsigned long long kPlanCountMask = (1ull << kPlanKeyShift) - 1ull;
 // Sweep time of a kept tile by precision level, in 1/64 of a full tile
 // (forced-level C4 sweeps: 20.6, 13.5, 10.6 ns per tile): the weight the
 // workgroup ranges and sbo_query_cost balance
@@ -2244,7 +2238,7 @@ __global__ __launch_bounds__(kPlanThreads) void plan_count_kernel(
     __shared__ float red[4 * kPlanWaves];
     __shared__ unsigned long long nearm[kPlanD2 / 64];
     __shared__ int nearp[kPlanD2 / 64 + 1];
-    __shared__ unsigned long long nem[(1 << kLevelShift) / kTilesPerRowBlockStep / 64];  // bit I: item (I, qb) keeps a tile
+    __shared__ unsigned long long nem[kPlanMaxTiles / kTilesPerRowBlockStep / 64];  // bit I: item (I, qb) keeps a tile
     __shared__ unsigned long long bins[kPlanWaves][kBudgetBins];
     __shared__ unsigned long long wtot[kPlanMaxI];
     __shared__ unsigned long long budget_exp;
@@ -2487,7 +2481,7 @@ __global__ __launch_bounds__(kPlanThreads) void plan_count_kernel(
             wsum = (unsigned)((unsigned long long)wsum * (100u * (unsigned)nI + g_rb_slope * (unsigned)I) /
                               (100u * (unsigned)nI));
         if (lane == 0) {
-            key[item] = (unsigned long long)cnt | ((cnt > 0 ? 1ull : 0ull) << kPlanKeyShift);
+            key[item] = plan_key_pack(cnt);
             thr[item] = (unsigned char)(drop_max + 1);
             wkey[item] = wsum;
             if (cnt > 0) atomicOr(&nem[I >> 6], 1ull << (I & 63));
@@ -2535,14 +2529,14 @@ __global__ __launch_bounds__(256) void plan_write_kernel(
     unsigned long long prod = 0, nl1 = 0, nl2 = 0;
     for (int64_t item = gw; item < items; item += nw) {
         const unsigned long long k = key[item];
-        const int cnt = (int)(k & kPlanCountMask);
+        const int cnt = (int)plan_key_count(k);
         if (cnt > 0) {
             int I;
             int64_t qb;
             plan_item_inv(item, nI, nQ, blk, I, qb);
             const unsigned long long ex = scan[item] - k;
-            const uint64_t off = ex & kPlanCountMask;
-            const int64_t ne = (int64_t)(ex >> kPlanKeyShift);
+            const uint64_t off = plan_key_count(ex);
+            const int64_t ne = plan_key_items(ex);
             const int T = kTilesPerRowBlockStep * (I + 1);
             const unsigned long long *ib = bits + item * (int64_t)plan_chunks(nI) * 3;
             uint64_t base = off;
@@ -2551,15 +2545,14 @@ __global__ __launch_bounds__(256) void plan_write_kernel(
                                          l2 = ib[(t0 >> 6) * 3 + 2];
                 if ((kept >> lane) & 1ull) {
                     const int code = ((l1 >> lane) & 1ull) ? 1 : (((l2 >> lane) & 1ull) ? 2 : 0);
-                    tl[base + __popcll(kept & ((1ull << lane) - 1ull))] =
-                        (unsigned short)((t0 + lane) | (code << kLevelShift));
+                    tl[base + __popcll(kept & ((1ull << lane) - 1ull))] = plan_entry_pack(t0 + lane, code);
                     prod += code == 0 ? prod_full : (code == 1 ? 3 : 1);
                     nl1 += code == 1 ? 1 : 0;
                     nl2 += code == 2 ? 1 : 0;
                 }
                 base += __popcll(kept);
             }
-            if (lane == 0) desc[ne] = make_int4(I, (int)qb, (int)(uint32_t)off, cnt | (int)((off >> 32) << 16));
+            if (lane == 0) desc[ne] = plan_item_int4(I, (int)qb, off, cnt);
         }
     }
     if (partial) {
@@ -2608,9 +2601,9 @@ __global__ void plan_seg_kernel(const unsigned long long *__restrict__ scan, int
                                 unsigned long long *__restrict__ tiles_done, const unsigned long long *__restrict__ wkey,
                                 const unsigned long long *__restrict__ wscan, int nI, int64_t nQ, int blk) {
     const unsigned long long last = scan[n_items - 1];
-    const uint64_t total = last & kPlanCountMask;
+    const uint64_t total = plan_key_count(last);
     const uint64_t wtotal = wscan[n_items - 1];
-    const int64_t nne = (int64_t)(last >> kPlanKeyShift);
+    const int64_t nne = plan_key_items(last);
     for (int w = threadIdx.x; w <= P; w += blockDim.x) {
         if (w == P) {
             seg[P] = (int)nne;
@@ -2652,7 +2645,7 @@ __device__ __forceinline__ int64_t xcd_position(int64_t k, const int *__restrict
 __global__ void plan_perm_kernel(const unsigned long long *__restrict__ scan, int64_t n_items,
                                  const int4 *__restrict__ desc, const int *__restrict__ xseg, int G,
                                  int *__restrict__ pos_of, unsigned long long *__restrict__ cnt2) {
-    const int64_t nne = (int64_t)(scan[n_items - 1] >> kPlanKeyShift);
+    const int64_t nne = plan_key_items(scan[n_items - 1]);
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= nne) {
         // (the permutation maps [0, nne) onto itself: the positions past it count 0 for the scan)
@@ -2661,7 +2654,7 @@ __global__ void plan_perm_kernel(const unsigned long long *__restrict__ scan, in
     }
     const int64_t p = xcd_position(k, xseg, G);
     pos_of[k] = (int)p;
-    cnt2[p] = (unsigned long long)(desc[k].w & 0xffff);
+    cnt2[p] = (unsigned long long)plan_item_count(desc[k].w);
 }
 
 __device__ __forceinline__ int4 step_record(int64_t ts, int I, int qb, int te, int i, int cnt);
@@ -2676,13 +2669,13 @@ __global__ __launch_bounds__(256) void plan_move_kernel(const unsigned long long
                                                         const unsigned long long *__restrict__ off2,
                                                         int4 *__restrict__ desc2, unsigned short *__restrict__ tl2,
                                                         int4 *__restrict__ rec) {
-    const int64_t nne = (int64_t)(scan[n_items - 1] >> kPlanKeyShift);
+    const int64_t nne = plan_key_items(scan[n_items - 1]);
     const int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (k >= nne) return;
     const int4 d = desc[k];
-    const int cnt = d.w & 0xffff;
-    const uint64_t off = (uint64_t)(uint32_t)d.z | ((uint64_t)((uint32_t)d.w >> 16) << 32);
+    const int cnt = plan_item_count(d.w);
+    const uint64_t off = plan_item_offset(d.z, d.w);
     const int p = pos_of[k];
     const uint64_t o2 = off2[p];
     const int64_t ts = tile_start(d.x);
@@ -2691,30 +2684,30 @@ __global__ __launch_bounds__(256) void plan_move_kernel(const unsigned long long
         tl2[o2 + i] = te;
         if (rec) rec[o2 + i] = step_record(ts, d.x, d.y, te, i, cnt);
     }
-    if (lane == 0) desc2[p] = make_int4(d.x, d.y, (int)(uint32_t)o2, cnt | (int)((o2 >> 32) << 16));
+    if (lane == 0) desc2[p] = plan_item_int4(d.x, d.y, o2, cnt);
 }
 
-// Step records of the split sweep (kRecFirst in sbo_internal.hpp), one
+// Step records of the split sweep (plan_format.hpp), one
 // wave per non-empty item, in the order the sweep walks the list (after the
 // XCD permutation, where plan_move_kernel writes them): the kernel then
 // stages a tile from one record instead of re-deriving offsets from the
 // descriptor and tile list in every wave.
 __device__ __forceinline__ int4 step_record(int64_t ts, int I, int qb, int te, int i, int cnt) {
-    const int t = te & ((1 << kLevelShift) - 1);
-    const int w = I | ((te >> kLevelShift) << 16) | (i == 0 ? kRecFirst : 0) | (i == cnt - 1 ? kRecLast : 0);
+    const int t = plan_entry_tile(te);
+    const int w = I | (plan_entry_level(te) << kRecLevelShift) | (i == 0 ? kRecFirst : 0) | (i == cnt - 1 ? kRecLast : 0);
     return make_int4((int)(uint32_t)((ts + t) * 96), t * 256, qb, w);
 }
 
 __global__ __launch_bounds__(256) void plan_rec_kernel(const unsigned long long *__restrict__ scan, int64_t n_items,
                                                        const int4 *__restrict__ desc,
                                                        const unsigned short *__restrict__ tl, int4 *__restrict__ rec) {
-    const int64_t nne = (int64_t)(scan[n_items - 1] >> kPlanKeyShift);
+    const int64_t nne = plan_key_items(scan[n_items - 1]);
     const int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (k >= nne) return;
     const int4 d = desc[k];
-    const int cnt = d.w & 0xffff;
-    const uint64_t off = (uint64_t)(uint32_t)d.z | ((uint64_t)((uint32_t)d.w >> 16) << 32);
+    const int cnt = plan_item_count(d.w);
+    const uint64_t off = plan_item_offset(d.z, d.w);
     const int64_t ts = tile_start(d.x);
     for (int i = lane; i < cnt; i += 64) rec[off + i] = step_record(ts, d.x, d.y, tl[off + i], i, cnt);
 }
@@ -2769,10 +2762,8 @@ __global__ __launch_bounds__(kPredictThreads, 1) void predict_kernel(
     const float *__restrict__ qx, const float *__restrict__ qy, int64_t m, int64_t ldp, float cexp, float m0,
     float *__restrict__ part, float *__restrict__ mean) {
     __shared__ __attribute__((aligned(16))) float smem[kSmemFloats];
-    const int bid = blockIdx.x;
-    const int rng = (P % 8 == 0) ? (bid % 8) * (P / 8) + bid / 8 : bid;
-    // (bounds are clamped so that a corrupt plan cannot address outside the buffers)
-    const int k0 = max(seg[rng], 0), k1 = min(seg[rng + 1], n_items);
+    const PlanRange range = plan_range(seg, P, n_items);
+    const int k0 = range.k0, k1 = range.k1;
     if (k0 >= k1) return;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -2780,18 +2771,9 @@ __global__ __launch_bounds__(kPredictThreads, 1) void predict_kernel(
     const int g = lane >> 4;   // k within the step
     const int r = lane & 15;   // row within a 16-row block / query within the wave
 
-    // LDS: two stages, then two descriptor windows and two tile-list windows
-    // (1 KiB each), refilled one window ahead by LDS-DMA
-    const int4 *dwin = reinterpret_cast<const int4 *>(smem + 2 * kStageFloats);
-    const unsigned short *lwin = reinterpret_cast<const unsigned short *>(smem + 2 * kStageFloats + 512);
-
-    // LDS-DMA (global_load_lds_dwordx4): each wave instruction moves 1 KiB,
-    // lane-linear, no staging registers.  A stage = the 64 KiB [BK][BM] tile
-    // (16 instructions per loader wave) + 768 B of per-k coordinates.  The
-    // DMA is issued from inline asm so that hipcc does not see an LDS write
-    // in flight: with a compiler-visible one pending it drains every ds_read
-    // wait to lgkmcnt(0) (waiting on reads issued one instruction earlier)
-    // instead of counting.  Every stage and window is retired by the
+    // LDS: two stages, then the plan's windows.  A stage = the 64 KiB
+    // [BK][BM] tile (16 LDS-DMA instructions per loader wave, lds_dma16) +
+    // 768 B of per-k coordinates.  Every stage and window is retired by the
     // explicit vmcnt(0) + barrier at the end of each step.
     typedef __attribute__((address_space(3))) char lds_char;
     constexpr int kTileBytes = kTileFloats * 4, kStageBytes = kStageFloats * 4, kCBytes = 3 * kBK * 4;
@@ -2803,74 +2785,32 @@ __global__ __launch_bounds__(kPredictThreads, 1) void predict_kernel(
     const bool loader = lw >= 0;
     const char *gA = reinterpret_cast<const char *>(aug) + (loader ? lw : 0) * 1024 + lane * 16;
     const char *gC = reinterpret_cast<const char *>(kcoord) + lane * 16;
-    const char *gD = reinterpret_cast<const char *>(desc) + lane * 16;
-    const char *gL = reinterpret_cast<const char *>(tl) + lane * 16;
     const uint32_t lds_smem = (uint32_t)(uintptr_t)(lds_char *)(smem);
     const uint32_t lds_wave = lds_smem + (uint32_t)__builtin_amdgcn_readfirstlane(loader ? lw : 0) * 1024u;
-    const uint32_t lds_dwin = lds_smem + 2u * kStageBytes;
-    const uint32_t lds_lwin = lds_dwin + 2048u;
-#define SBO_DMA16(gsrc, ldst)                                                                           \
-    do {                                                                                                \
-        uint32_t keep_;                                                                                 \
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t" \
-                     "s_mov_b32 m0, %0"                                                                 \
-                     : "=&s"(keep_)                                                                     \
-                     : "v"(gsrc), "s"(ldst)                                                             \
-                     : "memory");                                                                       \
-    } while (0)
+    const char *wbase = reinterpret_cast<const char *>(smem + 2 * kStageFloats);
+    const PlanWindows win(wbase, nI);
+    const PlanRefill refill(wbase, desc, tl, lane, lw == 1, lw == 2);
 #define SBO_STAGE(I_, t_, buf)                                                                          \
     do {                                                                                                \
         if (loader) {                                                                                   \
             const char *s_ = gA + (tile_start(I_) + (t_)) * (int64_t)kTileBytes;                       \
             const uint32_t d_ = lds_wave + (uint32_t)(buf) * kStageBytes;                               \
             _Pragma("unroll") for (int j = 0; j < kWaveStride / 1024; ++j)                              \
-                SBO_DMA16(s_ + j * LOADERS * 1024, d_ + (uint32_t)(j * LOADERS * 1024));                \
+                lds_dma16(s_ + j * LOADERS * 1024, d_ + (uint32_t)(j * LOADERS * 1024));                \
         }                                                                                               \
         if (lw == 0 && lane < kCBytes / 16)                                                             \
-            SBO_DMA16(gC + (int64_t)(t_) * kCBytes, lds_smem + (uint32_t)((buf) * kStageBytes + kTileBytes)); \
+            lds_dma16(gC + (int64_t)(t_) * kCBytes, lds_smem + (uint32_t)((buf) * kStageBytes + kTileBytes)); \
     } while (0)
-    // descriptor window w (items [64w, 64w+64)) and tile-list window w
-    // (entries [512w, 512w+512)), each into LDS buffer w & 1
-#define SBO_DESC_WINDOW(w_)                                                                             \
-    do {                                                                                                \
-        if (lw == 1) SBO_DMA16(gD + (int64_t)(w_) * 1024, lds_dwin + (uint32_t)((w_) & 1) * 1024u);     \
-    } while (0)
-#define SBO_LIST_WINDOW(w_)                                                                             \
-    do {                                                                                                \
-        if (lw == 2) SBO_DMA16(gL + (int64_t)(w_) * 1024, lds_lwin + (uint32_t)((w_) & 1) * 1024u);     \
-    } while (0)
-    auto desc_at = [&](int k) {  // a descriptor from its (loaded) window; wave-uniform
-        const int4 d = dwin[((k / kDescWindow) & 1) * kDescWindow + k % kDescWindow];
-        const int I = min(max(__builtin_amdgcn_readfirstlane(d.x), 0), nI - 1);
-        return make_int4(I, __builtin_amdgcn_readfirstlane(d.y), __builtin_amdgcn_readfirstlane(d.z),
-                         __builtin_amdgcn_readfirstlane(d.w));
-    };
-    auto entry_off = [](const int4 &d) {
-        return (uint64_t)(uint32_t)d.z | ((uint64_t)((uint32_t)d.w >> 16) << 32);
-    };
-    auto list_at = [&](uint64_t e, int I) {
-        // (every level at full f32 precision here: the level code is ignored)
-        const int t = __builtin_amdgcn_readfirstlane((int)lwin[((e / kListWindow) & 1) * kListWindow + e % kListWindow]) &
-                      ((1 << kLevelShift) - 1);
-        return min(t, kTilesPerRowBlockStep * (I + 1) - 1);
-    };
 
     // ---- prologue: the first two windows of each kind, the first stage
-    SBO_DESC_WINDOW(k0 / kDescWindow);
-    SBO_DESC_WINDOW(k0 / kDescWindow + 1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int4 dc = desc_at(k0);
+    refill.begin_items(k0);
+    int4 dc = win.desc_at(k0);
     uint64_t e = entry_off(dc);
-    SBO_LIST_WINDOW(e / kListWindow);
-    SBO_LIST_WINDOW(e / kListWindow + 1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    SBO_STAGE(dc.x, list_at(e, dc.x), 0);
+    refill.begin_entries(e);
+    SBO_STAGE(dc.x, win.list_at(e, dc.x), 0);
     int64_t q = (int64_t)dc.y * kBN + wave * 16 + r;
     float xq = qx[q < m ? q : m - 1], yq = qy[q < m ? q : m - 1];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    plan_dma_landed();
 
     OT outer[kRowBlocks][4];
 #pragma unroll
@@ -2881,7 +2821,7 @@ __global__ __launch_bounds__(kPredictThreads, 1) void predict_kernel(
     f32x4 acc[kRowBlocks];
     int k = k0, j = 0, cur = 0;
     for (;;) {
-        const int cnt = dc.w & 0xffff;
+        const int cnt = plan_item_count(dc.w);
         // the next step: (k, j+1), or the first tile of item k+1
         int kn = k, jn = j + 1;
         if (jn >= cnt) {
@@ -2893,15 +2833,15 @@ __global__ __launch_bounds__(kPredictThreads, 1) void predict_kernel(
         float xqn = xq, yqn = yq;
         if (more) {
             if (kn != k) {
-                dn = desc_at(kn);
-                if (kn % kDescWindow == 0) SBO_DESC_WINDOW(kn / kDescWindow + 1);
+                dn = win.desc_at(kn);
+                refill.enter_item(kn);
                 const int64_t qn = (int64_t)dn.y * kBN + wave * 16 + r;
                 xqn = qx[qn < m ? qn : m - 1];
                 yqn = qy[qn < m ? qn : m - 1];
             }
             const uint64_t en = e + 1;
-            if (en % kListWindow == 0) SBO_LIST_WINDOW(en / kListWindow + 1);
-            SBO_STAGE(dn.x, list_at(en, dn.x), cur ^ 1);
+            refill.enter_entry(en);
+            SBO_STAGE(dn.x, win.list_at(en, dn.x), cur ^ 1);
         }
         // per-lane bases; every k step is a constant offset from them
         const float4 *pa = reinterpret_cast<const float4 *>(smem + cur * kStageFloats) + g * 16 + r;
@@ -2937,8 +2877,7 @@ __global__ __launch_bounds__(kPredictThreads, 1) void predict_kernel(
                 mu = 0.0;
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        plan_dma_landed();
         if (!more) break;
         if (kn != k) {
             k = kn;
@@ -2952,9 +2891,6 @@ __global__ __launch_bounds__(kPredictThreads, 1) void predict_kernel(
         cur ^= 1;
     }
 #undef SBO_STAGE
-#undef SBO_DESC_WINDOW
-#undef SBO_LIST_WINDOW
-#undef SBO_DMA16
 }
 
 // ------------------------------------------------------ a6+a7+a10 acquire
@@ -3260,8 +3196,10 @@ hipError_t launch_pack_tile_norms(hipStream_t s, const double *Linv, int64_t ld,
     const int64_t nI = npad / kBM;
     const int64_t t0 = tile_start(I0), t1 = tile_start(nI);
     if (t1 <= t0) return hipSuccess;
-    hipLaunchKernelGGL(tile_norm_kernel<true>, dim3((unsigned)(t1 - t0)), dim3(kBM), 0, s, aug, t0, lgn, Linv, ld, n,
-                       sf2, aug);
+    // (the fused kernel writes the tile and reads it back through augw alone: no second, const __restrict__
+    // alias of the buffer)
+    hipLaunchKernelGGL(tile_norm_kernel<true>, dim3((unsigned)(t1 - t0)), dim3(kBM), 0, s,
+                       static_cast<const float *>(nullptr), t0, lgn, Linv, ld, n, sf2, aug);
     return hipGetLastError();
 }
 
@@ -3355,10 +3293,10 @@ PlanLayout plan_layout(int64_t nI, int64_t nQ, int P) {
     L.nemask = take(8 * (size_t)nQ * (size_t)((nI + 63) / 64));
     L.lvcnt = take(8 * 3 * 4 * (size_t)kPlanWriteBlocks);
     L.bits = take(8 * 3 * (size_t)items * (size_t)plan_chunks((int)nI));
-    L.desc = take(16 * (size_t)(items + 2 * kDescWindow));
-    L.tl = take(2 * (size_t)(cap + 2 * kListWindow));
+    L.desc = take(16 * (size_t)plan_desc_slots(items));
+    L.tl = take(2 * (size_t)plan_list_slots(cap));
     L.seg = take(4 * (size_t)(P + 1));
-    L.rec = take(16 * (size_t)(cap + 2 * kRecWindow));
+    L.rec = take(16 * (size_t)plan_rec_slots(cap));
     size_t tb = 0;
     (void)rocprim::inclusive_scan(nullptr, tb, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
                                   (size_t)items, rocprim::plus<unsigned long long>());
@@ -3370,8 +3308,8 @@ PlanLayout plan_layout(int64_t nI, int64_t nQ, int P) {
         L.pos_of = take(4 * (size_t)items);
         L.cnt2 = take(8 * (size_t)items);
         L.off2 = take(8 * (size_t)items);
-        L.desc2 = take(16 * (size_t)(items + 2 * kDescWindow));
-        L.tl2 = take(2 * (size_t)(cap + 2 * kListWindow));
+        L.desc2 = take(16 * (size_t)plan_desc_slots(items));
+        L.tl2 = take(2 * (size_t)plan_list_slots(cap));
         L.seg2 = take(4 * (size_t)(P + 1));
         size_t t2 = 0;
         (void)rocprim::exclusive_scan(nullptr, t2, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
@@ -3401,9 +3339,7 @@ hipError_t launch_plan(hipStream_t s, const float4 *kbox, int64_t npad, const fl
     const int64_t nQ = (m + kBN - 1) / kBN;
     const int64_t items = (int64_t)nI * nQ;
     if (m <= 0 || nI <= 0) return hipSuccess;
-    // key fields: items < 2^24, every kept-tile count < 2^40; tile index < 2^14 (level code above)
-    if (nQ > 0x7fffffff || items >= (1ll << (64 - kPlanKeyShift)) ||
-        2 * (int64_t)nI * (nI + 1) * nQ >= (1ll << kPlanKeyShift) || kTilesPerRowBlockStep * (int64_t)nI > (1 << kLevelShift) - 1)
+    if (!plan_fits(nQ, items, 2 * (int64_t)nI * (nI + 1) * nQ, kTilesPerRowBlockStep * (int64_t)nI))
         return hipErrorInvalidValue;
     const PlanLayout L = plan_layout(nI, nQ, P);
     if (work_bytes < L.total) return hipErrorInvalidValue;

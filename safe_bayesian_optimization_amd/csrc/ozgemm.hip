@@ -30,7 +30,7 @@
 #include <cstdint>
 #include <type_traits>
 
-#include "sbo_internal.hpp"
+#include "plan_walk.hpp"   // lds_dma16
 
 namespace sbo {
 namespace {
@@ -228,15 +228,6 @@ __global__ __launch_bounds__(256, 1) void gz_gemm_kernel(const char *__restrict_
     const uint32_t lds_smem = (uint32_t)(uintptr_t)(lds_char *)(smem);
     const char *gA = Ad + (i0 / 16) * (int64_t)Kb * ND * 1024 + lane * 16;
     const char *gB = Bd + (j0 / 16) * (int64_t)Kb * ND * 1024 + lane * 16;
-#define SBO_GZ_DMA16(gsrc, ldst)                                                                         \
-    do {                                                                                                 \
-        uint32_t keep_;                                                                                  \
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t" \
-                     "s_mov_b32 m0, %0"                                                                  \
-                     : "=&s"(keep_)                                                                      \
-                     : "v"(gsrc), "s"(ldst)                                                              \
-                     : "memory");                                                                        \
-    } while (0)
     // stage k-block kb_ into buffer buf_: piece p = wave + 4 q; A's pieces
     // first (row block p / ND, digit p % ND), then B's
     auto stage = [&](int kb_, int buf_) {
@@ -247,7 +238,7 @@ __global__ __launch_bounds__(256, 1) void gz_gemm_kernel(const char *__restrict_
             const int blk = pa / ND, s = pa % ND;
             const char *src = (p < (kGzTM / 16) * ND ? gA : gB) + ((int64_t)blk * Kb + kb_) * ND * 1024 + s * 1024;
             const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_smem + (uint32_t)(buf_ * kStage + p * 1024));
-            SBO_GZ_DMA16(src, dst);
+            lds_dma16(src, dst);
         }
     };
     static_assert(kPieces % 4 == 0, "whole pieces per wave");
@@ -291,7 +282,6 @@ __global__ __launch_bounds__(256, 1) void gz_gemm_kernel(const char *__restrict_
         __syncthreads();
         cur ^= 1;
     }
-#undef SBO_GZ_DMA16
     // combine: lane l holds rows 4 (l >> 4) + v of each A block, column l & 15
     // of each B block
     const int g = lane >> 4, cl = lane & 15;
@@ -362,15 +352,6 @@ __global__ __launch_bounds__(64 * NW, 1) void gz_gemm8_kernel(const char *__rest
     const uint32_t lds_smem = (uint32_t)(uintptr_t)(lds_char *)(smem);
     const char *gA = Ad + (i0 / 16) * (int64_t)Kb * ND * 1024 + lane * 16;
     const char *gB = Bd + (j0 / 16) * (int64_t)Kb * ND * 1024 + lane * 16;
-#define SBO_GZ_DMA16(gsrc, ldst)                                                                         \
-    do {                                                                                                 \
-        uint32_t keep_;                                                                                  \
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t" \
-                     "s_mov_b32 m0, %0"                                                                  \
-                     : "=&s"(keep_)                                                                      \
-                     : "v"(gsrc), "s"(ldst)                                                              \
-                     : "memory");                                                                        \
-    } while (0)
     auto stage = [&](int kb_, int buf_) {
 #pragma unroll
         for (int q = 0; q < kPerWave; ++q) {
@@ -380,7 +361,7 @@ __global__ __launch_bounds__(64 * NW, 1) void gz_gemm8_kernel(const char *__rest
             const int blk = pa / ND, s = pa % ND;
             const char *src = (p < (kGzTM / 16) * ND ? gA : gB) + ((int64_t)blk * Kb + kb_) * ND * 1024 + s * 1024;
             const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_smem + (uint32_t)(buf_ * kStage + p * 1024));
-            SBO_GZ_DMA16(src, dst);
+            lds_dma16(src, dst);
         }
     };
 
@@ -417,7 +398,6 @@ __global__ __launch_bounds__(64 * NW, 1) void gz_gemm8_kernel(const char *__rest
         __syncthreads();
         cur ^= 1;
     }
-#undef SBO_GZ_DMA16
     const int g = lane >> 4, cl = lane & 15;
 #pragma unroll
     for (int c = 0; c < kBW; ++c) {

@@ -25,7 +25,7 @@
 // operand of one 16x16x4 MFMA is one conflict-free ds_read_b64.
 #include <cstdint>
 
-#include "sbo_internal.hpp"
+#include "plan_walk.hpp"
 
 namespace sbo {
 namespace {
@@ -40,9 +40,7 @@ constexpr int kDC = 3 * kDH * 8;              // x, y, sf2 alpha of the stage's 
 constexpr int kDSlot = kDA + kDC;
 constexpr int kDWaves = kBN / 16;             // 8
 constexpr int kDThreads = 64 * kDWaves;
-constexpr int kDDescWin = 64;                 // item descriptors (int4) per 1 KiB window
-constexpr int kDListWin = 512;                // tile-list entries (u16) per 1 KiB window
-constexpr int kDSmem = 2 * kDSlot + 4096;     // two stage slots + two descriptor and two list windows
+constexpr int kDSmem = 2 * kDSlot + kPlanWalkLds;   // two stage slots + the plan's windows
 
 __device__ __forceinline__ f64x4 mfma_f64(double a, double b, f64x4 c) {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
@@ -102,93 +100,48 @@ __global__ __launch_bounds__(kDThreads, 1) void predict_f64_kernel(
     const float *__restrict__ qx, const float *__restrict__ qy, int64_t m, int64_t ldp, double cexp, double m0,
     double *__restrict__ part, double *__restrict__ mean) {
     __shared__ __attribute__((aligned(16))) char smem[kDSmem];
-    const int bid = blockIdx.x;
-    const int rng = (P % 8 == 0) ? (bid % 8) * (P / 8) + bid / 8 : bid;
-    // (bounds are clamped so that a corrupt plan cannot address outside the buffers)
-    const int k0 = max(seg[rng], 0), k1 = min(seg[rng + 1], n_items);
+    const PlanRange range = plan_range(seg, P, n_items);
+    const int k0 = range.k0, k1 = range.k1;
     if (k0 >= k1) return;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int r = lane & 15;
     const int g = lane >> 4;
-    const int4 *dwin = reinterpret_cast<const int4 *>(smem + 2 * kDSlot);
-    const unsigned short *lwin = reinterpret_cast<const unsigned short *>(smem + 2 * kDSlot + 2048);
+    const PlanWindows win(smem + 2 * kDSlot, nI);
+    const PlanRefill refill(smem + 2 * kDSlot, desc, tl, lane, wave == 1, wave == 2);
 
-    // LDS-DMA (global_load_lds_dwordx4, 1 KiB per wave instruction, lane
-    // linear), issued from inline asm as in predict_kernel: every wave moves
-    // 8 KiB of each 64 KiB A stage, wave 0 also the 768 B of coordinates.
+    // LDS-DMA (lds_dma16): every wave moves 8 KiB of each 64 KiB A stage,
+    // wave 0 also the 768 B of coordinates.
     typedef __attribute__((address_space(3))) char lds_char;
     const uint32_t lds_smem = (uint32_t)(uintptr_t)(lds_char *)(smem);
     const uint32_t lds_wave = lds_smem + (uint32_t)__builtin_amdgcn_readfirstlane(wave) * 1024u;
-    const uint32_t lds_dwin = lds_smem + 2u * kDSlot;
-    const uint32_t lds_lwin = lds_dwin + 2048u;
     const char *gA = reinterpret_cast<const char *>(a64) + wave * 1024 + lane * 16;
     const char *gC = reinterpret_cast<const char *>(kc64) + lane * 16;
-    const char *gD = reinterpret_cast<const char *>(desc) + lane * 16;
-    const char *gL = reinterpret_cast<const char *>(tl) + lane * 16;
-#define SBO_D_DMA16(gsrc, ldst)                                                                          \
-    do {                                                                                                 \
-        uint32_t keep_;                                                                                  \
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t" \
-                     "s_mov_b32 m0, %0"                                                                  \
-                     : "=&s"(keep_)                                                                      \
-                     : "v"(gsrc), "s"(ldst)                                                              \
-                     : "memory");                                                                        \
-    } while (0)
     // stage (packed tile T, half h) into slot buf
 #define SBO_D_STAGE(T_, h_, buf)                                                                         \
     do {                                                                                                 \
         const char *s_ = gA + ((int64_t)(T_) * 2 + (h_)) * (int64_t)kDA;                                 \
         const uint32_t d_ = lds_wave + (uint32_t)(buf) * kDSlot;                                         \
         _Pragma("unroll") for (int j_ = 0; j_ < kDA / (1024 * kDWaves); ++j_)                            \
-            SBO_D_DMA16(s_ + j_ * kDWaves * 1024, d_ + (uint32_t)(j_ * kDWaves * 1024));                 \
+            lds_dma16(s_ + j_ * kDWaves * 1024, d_ + (uint32_t)(j_ * kDWaves * 1024));                   \
         if (wave == 0 && lane < kDC / 16)                                                                \
-            SBO_D_DMA16(gC + ((int64_t)(kt_of_T_) * 2 + (h_)) * kDC, lds_smem + (uint32_t)((buf) * kDSlot + kDA)); \
+            lds_dma16(gC + ((int64_t)(kt_of_T_) * 2 + (h_)) * kDC, lds_smem + (uint32_t)((buf) * kDSlot + kDA)); \
     } while (0)
-#define SBO_D_DESC_WINDOW(w_)                                                                            \
-    do {                                                                                                 \
-        if (wave == 1) SBO_D_DMA16(gD + (int64_t)(w_) * 1024, lds_dwin + (uint32_t)((w_) & 1) * 1024u);  \
-    } while (0)
-#define SBO_D_LIST_WINDOW(w_)                                                                            \
-    do {                                                                                                 \
-        if (wave == 2) SBO_D_DMA16(gL + (int64_t)(w_) * 1024, lds_lwin + (uint32_t)((w_) & 1) * 1024u);  \
-    } while (0)
-    auto desc_at = [&](int k) {  // wave-uniform descriptor from its (loaded) window
-        const int4 d = dwin[((k / kDDescWin) & 1) * kDDescWin + k % kDDescWin];
-        const int I = min(max(__builtin_amdgcn_readfirstlane(d.x), 0), nI - 1);
-        return make_int4(I, __builtin_amdgcn_readfirstlane(d.y), __builtin_amdgcn_readfirstlane(d.z),
-                         __builtin_amdgcn_readfirstlane(d.w));
-    };
-    auto entry_off = [](const int4 &d) {
-        return (uint64_t)(uint32_t)d.z | ((uint64_t)((uint32_t)d.w >> 16) << 32);
-    };
-    auto list_at = [&](uint64_t e, int I) {  // the k-tile of tile-list entry e (level code ignored: all f64)
-        const int t = __builtin_amdgcn_readfirstlane((int)lwin[((e / kDListWin) & 1) * kDListWin + e % kDListWin]) &
-                      ((1 << kLevelShift) - 1);
-        return min(t, kTilesPerRowBlockStep * (I + 1) - 1);
-    };
 
     // ---- prologue: the first two windows of each kind, the first stage
-    SBO_D_DESC_WINDOW(k0 / kDDescWin);
-    SBO_D_DESC_WINDOW(k0 / kDDescWin + 1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int4 dc = desc_at(k0);
+    refill.begin_items(k0);
+    int4 dc = win.desc_at(k0);
     uint64_t e = entry_off(dc);
-    SBO_D_LIST_WINDOW(e / kDListWin);
-    SBO_D_LIST_WINDOW(e / kDListWin + 1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int t = list_at(e, dc.x);
+    refill.begin_entries(e);
+    int t = win.list_at(e, dc.x);
     {
         const int kt_of_T_ = t;
         SBO_D_STAGE(tile_start(dc.x) + t, 0, 0);
     }
     int64_t q = (int64_t)dc.y * kBN + wave * 16 + r;
     double xq = (double)qx[q < m ? q : m - 1], yq = (double)qy[q < m ? q : m - 1];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    plan_dma_landed();
 
     f64x4 acc[kDRB];
 #pragma unroll
@@ -196,7 +149,7 @@ __global__ __launch_bounds__(kDThreads, 1) void predict_f64_kernel(
     double mu = 0.0;
     int k = k0, j = 0, h = 0, cur = 0;
     for (;;) {
-        const int cnt = dc.w & 0xffff;
+        const int cnt = plan_item_count(dc.w);
         // the next stage: the other half of this tile, the next tile of this
         // item, or the first tile of item k + 1
         int kn = k, jn = j, hn = h + 1;
@@ -214,16 +167,16 @@ __global__ __launch_bounds__(kDThreads, 1) void predict_f64_kernel(
         double xqn = xq, yqn = yq;
         if (more) {
             if (kn != k) {
-                dn = desc_at(kn);
-                if (kn % kDDescWin == 0) SBO_D_DESC_WINDOW(kn / kDDescWin + 1);
+                dn = win.desc_at(kn);
+                refill.enter_item(kn);
                 const int64_t qn = (int64_t)dn.y * kBN + wave * 16 + r;
                 xqn = (double)qx[qn < m ? qn : m - 1];
                 yqn = (double)qy[qn < m ? qn : m - 1];
             }
             if (hn == 0) {
                 const uint64_t en = e + 1;
-                if (en % kDListWin == 0) SBO_D_LIST_WINDOW(en / kDListWin + 1);
-                tn = list_at(en, dn.x);
+                refill.enter_entry(en);
+                tn = win.list_at(en, dn.x);
             }
             const int kt_of_T_ = tn;
             SBO_D_STAGE(tile_start(dn.x) + tn, hn, cur ^ 1);
@@ -253,8 +206,7 @@ __global__ __launch_bounds__(kDThreads, 1) void predict_f64_kernel(
                 mu = 0.0;
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        plan_dma_landed();
         if (!more) break;
         if (kn != k) {
             k = kn;
@@ -270,9 +222,6 @@ __global__ __launch_bounds__(kDThreads, 1) void predict_f64_kernel(
         cur ^= 1;
     }
 #undef SBO_D_STAGE
-#undef SBO_D_DESC_WINDOW
-#undef SBO_D_LIST_WINDOW
-#undef SBO_D_DMA16
 }
 
 // A = sf2 L^-1 in f64 (from the fit's f64 inverse, lower, column-major, lda

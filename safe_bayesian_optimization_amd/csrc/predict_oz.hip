@@ -49,7 +49,7 @@
 // ds_read_b128.
 #include <cstdint>
 
-#include "sbo_internal.hpp"
+#include "plan_walk.hpp"
 
 namespace sbo {
 namespace {
@@ -71,9 +71,7 @@ constexpr int kOzC = 3 * kBK * 8 + 2 * kBK * 4;   // per k-tile: x, y, sf2 alpha
 constexpr int kOzSlot = kOzA + kOzE + kOzC;
 constexpr int kOzWaves = kBN / 16;                // 8
 constexpr int kOzThreads = 64 * kOzWaves;
-constexpr int kOzDescWin = 64;                    // item descriptors (int4) per 1 KiB window
-constexpr int kOzListWin = 512;                   // tile-list entries (u16) per 1 KiB window
-constexpr int kOzSmem = 2 * kOzSlot + 4096 + 512; // two stage slots + two descriptor and two list windows + 2^(j/64)
+constexpr int kOzSmem = 2 * kOzSlot + kPlanWalkLds + 512; // two stage slots + the plan's windows + 2^(j/64)
 // K*'s digits: X = rint(K* 2^(31 - eK)) + bias, bias = 128 at the three lower
 // base-256 positions, by one f64 add of 2^52 + bias (the add rounds to an
 // integer and leaves X + bias in the low mantissa bits)
@@ -88,7 +86,7 @@ constexpr int kKztE = kKztDigits;                          // + 512 B
 constexpr int kKztMu = kKztE + kBN * 4;                    // + 1 KiB
 constexpr int kKzt = kKztMu + kBN * 8;                     // 34304 B per (query block, k-tile)
 constexpr int kOzSlotT = kOzA + kOzE + kKzt;
-constexpr int kOzSmemT = 2 * kOzSlotT + 4096 + 512;
+constexpr int kOzSmemT = 2 * kOzSlotT + kPlanWalkLds + 512;
 static_assert(kOzSmemT <= 160 * 1024, "two table-mode stage slots must fit the LDS");
 static_assert(kOzA % (1024 * kOzWaves) == 0, "stage digits: whole 1 KiB LDS-DMA pieces per wave");
 
@@ -266,47 +264,31 @@ __global__ __launch_bounds__(kOzThreads, 1) void predict_oz_kernel(
     constexpr bool NOKSTAR = MODE == 1, TABLE = MODE >= 2, DMA_A = MODE != 3, DMA_T = MODE == 2;
     constexpr int kSlot = TABLE ? kOzSlotT : kOzSlot;
     __shared__ __attribute__((aligned(16))) char smem[TABLE ? kOzSmemT : kOzSmem];
-    const int bid = blockIdx.x;
-    const int rng = (P % 8 == 0) ? (bid % 8) * (P / 8) + bid / 8 : bid;
-    // (bounds are clamped so that a corrupt plan cannot address outside the buffers)
-    const int k0 = max(seg[rng], 0), k1 = min(seg[rng + 1], n_items);
+    const PlanRange range = plan_range(seg, P, n_items);
+    const int k0 = range.k0, k1 = range.k1;
     if (k0 >= k1) return;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int r = lane & 15;
     const int g = lane >> 4;
-    const int4 *dwin = reinterpret_cast<const int4 *>(smem + 2 * kSlot);
-    const unsigned short *lwin = reinterpret_cast<const unsigned short *>(smem + 2 * kSlot + 2048);
-    double *T2 = reinterpret_cast<double *>(smem + 2 * kSlot + 4096);
+    const PlanWindows win(smem + 2 * kSlot, nI);
+    const PlanRefill refill(smem + 2 * kSlot, desc, tl, lane, wave == 1, wave == 2);
+    double *T2 = reinterpret_cast<double *>(smem + 2 * kSlot + kPlanWalkLds);
     if (tid < 64) T2[tid] = exp2((double)tid * 0.015625);   // (visible after the prologue's barriers)
 
-    // LDS-DMA (global_load_lds_dwordx4, 1 KiB per wave instruction, lane
-    // linear), issued from inline asm as in predict_f64_kernel: every wave
-    // moves 5 KiB of each 40 KiB stage; wave 0 lanes 0-1 the stage's eight
-    // block exponents, wave 1 the tile's coordinates on its first half.
+    // LDS-DMA (lds_dma16): every wave moves 5 KiB of each 40 KiB stage; wave
+    // 0 lanes 0-1 the stage's eight block exponents, wave 1 the tile's
+    // coordinates on its first half.
     typedef __attribute__((address_space(3))) char lds_char;
     const uint32_t lds_smem = (uint32_t)(uintptr_t)(lds_char *)(smem);
     const uint32_t lds_wave = lds_smem + (uint32_t)__builtin_amdgcn_readfirstlane(wave) * 1024u;
-    const uint32_t lds_dwin = lds_smem + 2u * kSlot;
-    const uint32_t lds_lwin = lds_dwin + 2048u;
     const char *gA = aoz + wave * 1024 + lane * 16;
     const char *gE = reinterpret_cast<const char *>(eoz) + lane * 16;
     const char *gC = koz + lane * 16;
-    const char *gD = reinterpret_cast<const char *>(desc) + lane * 16;
-    const char *gL = reinterpret_cast<const char *>(tl) + lane * 16;
     const char *gZ = kzt + lane * 16;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const int nkt = kTilesPerRowBlockStep * nI;
-#define SBO_OZ_DMA16(gsrc, ldst)                                                                         \
-    do {                                                                                                 \
-        uint32_t keep_;                                                                                  \
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t" \
-                     "s_mov_b32 m0, %0"                                                                  \
-                     : "=&s"(keep_)                                                                      \
-                     : "v"(gsrc), "s"(ldst)                                                              \
-                     : "memory");                                                                        \
-    } while (0)
     // stage (packed tile T_, row half h_) into slot buf, with the coordinates
     // of k-tile kt_ (TABLE: its K* table piece for query block qb_; none: kt_ < 0)
 #define SBO_OZ_STAGE(T_, kt_, h_, buf, qb_)                                                              \
@@ -315,64 +297,35 @@ __global__ __launch_bounds__(kOzThreads, 1) void predict_oz_kernel(
         const uint32_t d_ = __builtin_amdgcn_readfirstlane(lds_wave + (uint32_t)(buf) * kSlot);          \
         if (DMA_A)                                                                                       \
             _Pragma("unroll") for (int j_ = 0; j_ < kOzA / (1024 * kOzWaves); ++j_)                      \
-                SBO_OZ_DMA16(s_ + j_ * kOzWaves * 1024, d_ + (uint32_t)(j_ * kOzWaves * 1024));          \
+                lds_dma16(s_ + j_ * kOzWaves * 1024, d_ + (uint32_t)(j_ * kOzWaves * 1024));             \
         if (DMA_A && wave == 0 && lane < 2)                                                              \
-            SBO_OZ_DMA16(gE + (int64_t)(T_) * 64 + (h_) * 32,                                            \
+            lds_dma16(gE + (int64_t)(T_) * 64 + (h_) * 32,                                               \
                          __builtin_amdgcn_readfirstlane(lds_smem + (uint32_t)((buf) * kSlot + kOzA)));       \
         if (TABLE) {                                                                                     \
             if (DMA_T && (kt_) >= 0) {                                                                   \
                 const char *z_ = gZ + ((int64_t)(qb_) * nkt + (kt_)) * kKzt;                              \
                 const uint32_t zd_ = __builtin_amdgcn_readfirstlane(lds_smem + (uint32_t)((buf) * kSlot + kOzA + kOzE)); \
                 _Pragma("unroll") for (int u_ = 0; u_ < kOzKDigits; ++u_)                                \
-                    SBO_OZ_DMA16(z_ + wave * 4096 + u_ * 1024, zd_ + (uint32_t)(wave_u * 4096 + u_ * 1024)); \
-                if (wave == 0 && lane < 32) SBO_OZ_DMA16(z_ + kKztE, zd_ + (uint32_t)kKztE);             \
-                if (wave == 1) SBO_OZ_DMA16(z_ + kKztMu, zd_ + (uint32_t)kKztMu);                        \
+                    lds_dma16(z_ + wave * 4096 + u_ * 1024, zd_ + (uint32_t)(wave_u * 4096 + u_ * 1024)); \
+                if (wave == 0 && lane < 32) lds_dma16(z_ + kKztE, zd_ + (uint32_t)kKztE);                \
+                if (wave == 1) lds_dma16(z_ + kKztMu, zd_ + (uint32_t)kKztMu);                           \
             }                                                                                            \
         } else if ((kt_) >= 0 && (wave == 1 || wave == 3))                                               \
-            SBO_OZ_DMA16(gC + (int64_t)(kt_) * kOzC + (wave == 3 ? 1024 : 0),                            \
+            lds_dma16(gC + (int64_t)(kt_) * kOzC + (wave == 3 ? 1024 : 0),                               \
                          __builtin_amdgcn_readfirstlane(lds_smem + (uint32_t)((buf) * kSlot + kOzA + kOzE +     \
                                                                               (wave == 3 ? 1024 : 0))));     \
     } while (0)
-#define SBO_OZ_DESC_WINDOW(w_)                                                                           \
-    do {                                                                                                 \
-        if (wave == 1) SBO_OZ_DMA16(gD + (int64_t)(w_) * 1024, lds_dwin + (uint32_t)((w_) & 1) * 1024u); \
-    } while (0)
-#define SBO_OZ_LIST_WINDOW(w_)                                                                           \
-    do {                                                                                                 \
-        if (wave == 2) SBO_OZ_DMA16(gL + (int64_t)(w_) * 1024, lds_lwin + (uint32_t)((w_) & 1) * 1024u); \
-    } while (0)
-    auto desc_at = [&](int k) {  // wave-uniform descriptor from its (loaded) window
-        const int4 d = dwin[((k / kOzDescWin) & 1) * kOzDescWin + k % kOzDescWin];
-        const int I = min(max(__builtin_amdgcn_readfirstlane(d.x), 0), nI - 1);
-        return make_int4(I, __builtin_amdgcn_readfirstlane(d.y), __builtin_amdgcn_readfirstlane(d.z),
-                         __builtin_amdgcn_readfirstlane(d.w));
-    };
-    auto entry_off = [](const int4 &d) {
-        return (uint64_t)(uint32_t)d.z | ((uint64_t)((uint32_t)d.w >> 16) << 32);
-    };
-    auto list_at = [&](uint64_t e, int I) {  // the k-tile of tile-list entry e (level code ignored)
-        const int t = __builtin_amdgcn_readfirstlane((int)lwin[((e / kOzListWin) & 1) * kOzListWin + e % kOzListWin]) &
-                      ((1 << kLevelShift) - 1);
-        return min(t, kTilesPerRowBlockStep * (I + 1) - 1);
-    };
 
     // ---- prologue: the first two windows of each kind, the first stage
-    SBO_OZ_DESC_WINDOW(k0 / kOzDescWin);
-    SBO_OZ_DESC_WINDOW(k0 / kOzDescWin + 1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int4 dc = desc_at(k0);
+    refill.begin_items(k0);
+    int4 dc = win.desc_at(k0);
     uint64_t e = entry_off(dc);
-    SBO_OZ_LIST_WINDOW(e / kOzListWin);
-    SBO_OZ_LIST_WINDOW(e / kOzListWin + 1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int t = list_at(e, dc.x);
+    refill.begin_entries(e);
+    int t = win.list_at(e, dc.x);
     SBO_OZ_STAGE(tile_start(dc.x) + t, t, 0, 0, dc.y);
     int64_t q = (int64_t)dc.y * kBN + wave * 16 + r;
     double xq = (double)qx[q < m ? q : m - 1], yq = (double)qy[q < m ? q : m - 1];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    plan_dma_landed();
 
     f64x4 acc[kOzRB];
 #pragma unroll
@@ -382,7 +335,7 @@ __global__ __launch_bounds__(kOzThreads, 1) void predict_oz_kernel(
     double mu = 0.0;
     int k = k0, j = 0, h = 0, cur = 0;
     for (;;) {
-        const int cnt = dc.w & 0xffff;
+        const int cnt = plan_item_count(dc.w);
         // the next stage: the other half of this tile, the next tile of this
         // item, or the first tile of item k + 1
         int kn = k, jn = j, hn = h + 1;
@@ -400,16 +353,16 @@ __global__ __launch_bounds__(kOzThreads, 1) void predict_oz_kernel(
         double xqn = xq, yqn = yq;
         if (more) {
             if (kn != k) {
-                dn = desc_at(kn);
-                if (kn % kOzDescWin == 0) SBO_OZ_DESC_WINDOW(kn / kOzDescWin + 1);
+                dn = win.desc_at(kn);
+                refill.enter_item(kn);
                 const int64_t qn = (int64_t)dn.y * kBN + wave * 16 + r;
                 xqn = (double)qx[qn < m ? qn : m - 1];
                 yqn = (double)qy[qn < m ? qn : m - 1];
             }
             if (hn == 0) {
                 const uint64_t en = e + 1;
-                if (en % kOzListWin == 0) SBO_OZ_LIST_WINDOW(en / kOzListWin + 1);
-                tn = list_at(en, dn.x);
+                refill.enter_entry(en);
+                tn = win.list_at(en, dn.x);
             }
             SBO_OZ_STAGE(tile_start(dn.x) + tn, hn == 0 ? tn : -1, hn, cur ^ 1, dn.y);
         }
@@ -457,8 +410,7 @@ __global__ __launch_bounds__(kOzThreads, 1) void predict_oz_kernel(
                 mu = 0.0;
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        plan_dma_landed();
         if (!more) break;
         if (kn != k) {
             k = kn;
@@ -474,9 +426,6 @@ __global__ __launch_bounds__(kOzThreads, 1) void predict_oz_kernel(
         cur ^= 1;
     }
 #undef SBO_OZ_STAGE
-#undef SBO_OZ_DESC_WINDOW
-#undef SBO_OZ_LIST_WINDOW
-#undef SBO_OZ_DMA16
 }
 
 #ifdef SBO_DIAG
@@ -507,7 +456,7 @@ __device__ __forceinline__ const char *sgpr_ptr(const char *p) {
 constexpr int kOz3Slot = kOzA + kOzE;                       // A digits + block exponents
 constexpr int kOz3Table = 3 * kOz3Slot;                     // the K* table piece (per-wave parts)
 constexpr int kOz3Win = kOz3Table + kKzt;                   // descriptor + list windows
-constexpr int kOz3Smem = kOz3Win + 4096;
+constexpr int kOz3Smem = kOz3Win + kPlanWalkLds;
 constexpr int kOz3AGroup = kOzA / (1024 * kOzWaves) + 1;    // A DMA instructions per wave per stage (5 + exponents)
 constexpr int kOz3TGroup = kOzKDigits + 2;                  // table DMA instructions per wave per tile (6)
 static_assert(kOz3Smem <= 160 * 1024, "three A slots and one table piece must fit the LDS");
@@ -518,23 +467,21 @@ __global__ __launch_bounds__(kOzThreads, 1) void predict_oz3_kernel(
     const unsigned short *__restrict__ tl, const int *__restrict__ seg, int P, int n_items, int nI, int64_t m,
     int64_t ldp, double m0, double *__restrict__ part, double *__restrict__ mean, const char *__restrict__ kzt) {
     __shared__ __attribute__((aligned(16))) char smem[kOz3Smem];
-    const int bid = blockIdx.x;
-    const int rng = (P % 8 == 0) ? (bid % 8) * (P / 8) + bid / 8 : bid;
-    const int k0 = max(seg[rng], 0), k1 = min(seg[rng + 1], n_items);
+    const PlanRange range = plan_range(seg, P, n_items);
+    const int k0 = range.k0, k1 = range.k1;
     if (k0 >= k1) return;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int r = lane & 15;
     const int g = lane >> 4;
-    const int4 *dwin = reinterpret_cast<const int4 *>(smem + kOz3Win);
-    const unsigned short *lwin = reinterpret_cast<const unsigned short *>(smem + kOz3Win + 2048);
+    const PlanWindows win(smem + kOz3Win, nI);
     typedef __attribute__((address_space(3))) char lds_char;
     const uint32_t lds_smem = (uint32_t)(uintptr_t)(lds_char *)(smem);
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const uint32_t lds_wave = lds_smem + (uint32_t)wave_u * 1024u;
     const uint32_t lds_dwin = lds_smem + kOz3Win;
-    const uint32_t lds_lwin = lds_dwin + 2048u;
+    const uint32_t lds_lwin = lds_dwin + 2u * kPlanWindowBytes;
     const uint32_t lds_tab = lds_smem + kOz3Table;
     const int nkt = kTilesPerRowBlockStep * nI;
     // LDS-DMA with an SGPR base (global_load_lds_dwordx4 v_off, s_base), as in
@@ -548,7 +495,8 @@ __global__ __launch_bounds__(kOzThreads, 1) void predict_oz3_kernel(
     const char *sE = reinterpret_cast<const char *>(eoz);
     const char *sD = reinterpret_cast<const char *>(desc);
     const char *sL = reinterpret_cast<const char *>(tl);
-    // (the windows: wave 1 the descriptors, wave 2 the list; masks in SGPRs)
+    // (the plan's windows go by this DMA form too, under a mask, not by
+    // PlanRefill: wave 1 the descriptors, wave 2 the list; masks in SGPRs)
     const uint64_t win_mask1 = (uint64_t)0 - (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(wave == 1 ? 1 : 0);
     const uint64_t win_mask2 = (uint64_t)0 - (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(wave == 2 ? 1 : 0);
 #define SBO_OZ3_DMA16(sbase, ldst)                                                                       \
@@ -585,38 +533,22 @@ __global__ __launch_bounds__(kOzThreads, 1) void predict_oz3_kernel(
         SBO_OZ3_DMA16M(z_ + kKztMu + wave_u * 128, lds_tab + (uint32_t)(kKztMu + wave_u * 128), 0xffull); \
     } while (0)
 #define SBO_OZ3_DESC_WINDOW(w_)                                                                          \
-    SBO_OZ3_DMA16M(sD + (int64_t)(w_) * 1024, lds_dwin + (uint32_t)((w_) & 1) * 1024u, win_mask1)
+    SBO_OZ3_DMA16M(sD + (int64_t)(w_) * kPlanWindowBytes, lds_dwin + (uint32_t)((w_) & 1) * kPlanWindowBytes, win_mask1)
 #define SBO_OZ3_LIST_WINDOW(w_)                                                                          \
-    SBO_OZ3_DMA16M(sL + (int64_t)(w_) * 1024, lds_lwin + (uint32_t)((w_) & 1) * 1024u, win_mask2)
-    auto desc_at = [&](int k) {
-        const int4 d = dwin[((k / kOzDescWin) & 1) * kOzDescWin + k % kOzDescWin];
-        const int I = min(max(__builtin_amdgcn_readfirstlane(d.x), 0), nI - 1);
-        return make_int4(I, __builtin_amdgcn_readfirstlane(d.y), __builtin_amdgcn_readfirstlane(d.z),
-                         __builtin_amdgcn_readfirstlane(d.w));
-    };
-    auto entry_off = [](const int4 &d) {
-        return (uint64_t)(uint32_t)d.z | ((uint64_t)((uint32_t)d.w >> 16) << 32);
-    };
-    auto list_at = [&](uint64_t e, int I) {
-        const int t = __builtin_amdgcn_readfirstlane((int)lwin[((e / kOzListWin) & 1) * kOzListWin + e % kOzListWin]) &
-                      ((1 << kLevelShift) - 1);
-        return min(t, kTilesPerRowBlockStep * (I + 1) - 1);
-    };
+    SBO_OZ3_DMA16M(sL + (int64_t)(w_) * kPlanWindowBytes, lds_lwin + (uint32_t)((w_) & 1) * kPlanWindowBytes, win_mask2)
 
     // ---- prologue: windows, the first tile (both halves and its table piece)
-    SBO_OZ3_DESC_WINDOW(k0 / kOzDescWin);
-    SBO_OZ3_DESC_WINDOW(k0 / kOzDescWin + 1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    SBO_OZ3_DESC_WINDOW(k0 / kPlanDescWindow);
+    SBO_OZ3_DESC_WINDOW(k0 / kPlanDescWindow + 1);
+    plan_dma_landed();
     // the current tile (k, j: item and its j-th tile; e: its tile-list entry)
-    int4 dc = desc_at(k0);
+    int4 dc = win.desc_at(k0);
     uint64_t e = entry_off(dc);
-    SBO_OZ3_LIST_WINDOW(e / kOzListWin);
-    SBO_OZ3_LIST_WINDOW(e / kOzListWin + 1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    SBO_OZ3_LIST_WINDOW(e / kPlanListWindow);
+    SBO_OZ3_LIST_WINDOW(e / kPlanListWindow + 1);
+    plan_dma_landed();
     int j = 0;
-    const int t = list_at(e, dc.x);
+    const int t = win.list_at(e, dc.x);
     SBO_OZ3_TABLE(t, dc.y);
     SBO_OZ3_A(tile_start(dc.x) + t, 0, 0);
     SBO_OZ3_A(tile_start(dc.x) + t, 1, 1);
@@ -626,22 +558,21 @@ __global__ __launch_bounds__(kOzThreads, 1) void predict_oz3_kernel(
     uint64_t eN = e + 1;
     int4 dN = dc;
     auto advance = [&]() {
-        if (jN >= (dN.w & 0xffff)) {
+        if (jN >= plan_item_count(dN.w)) {
             ++kN;
             jN = 0;
             if (kN < k1) {
-                dN = desc_at(kN);
-                if (kN % kOzDescWin == 0) SBO_OZ3_DESC_WINDOW(kN / kOzDescWin + 1);
+                dN = win.desc_at(kN);
+                if (kN % kPlanDescWindow == 0) SBO_OZ3_DESC_WINDOW(kN / kPlanDescWindow + 1);
             }
         }
         if (kN < k1) {
-            if (eN % kOzListWin == 0) SBO_OZ3_LIST_WINDOW(eN / kOzListWin + 1);
-            tN = list_at(eN, dN.x);
+            if (eN % kPlanListWindow == 0) SBO_OZ3_LIST_WINDOW(eN / kPlanListWindow + 1);
+            tN = win.list_at(eN, dN.x);
         }
     };
     advance();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    plan_dma_landed();
 
     f64x4 acc[kOzRB];
 #pragma unroll
@@ -672,7 +603,7 @@ __global__ __launch_bounds__(kOzThreads, 1) void predict_oz3_kernel(
         } else {
             stage_blocks<1>(slot, lane, kd, eK, acc);
         }
-        if (h == 1 && j == (dc.w & 0xffff) - 1) {
+        if (h == 1 && j == plan_item_count(dc.w) - 1) {
             // item done: column sums of V^2 over its 256 rows
             double sum = 0.0;
 #pragma unroll
@@ -883,7 +814,7 @@ constexpr int kKzt2Digits = kOzWaves * 2 * kOzKDigits * 1024;   // 64 KiB
 constexpr int kKzt2E = kKzt2Digits;
 constexpr int kKzt2Mu = kKzt2E + kBN * 4;
 constexpr int kKzt2 = kKzt2Mu + kBN * 8;                     // 67072 B per (query block, pair)
-constexpr int kOz2Smem = 2 * kOz2Slot + kKzt2 + 4096;        // two stage slots, the table, the windows
+constexpr int kOz2Smem = 2 * kOz2Slot + kKzt2 + kPlanWalkLds;        // two stage slots, the table, the windows
 constexpr int kOz2TableDma = 2 * kOzKDigits + 2;            // DMA instructions per wave per table piece
 static_assert(kOz2Smem <= 160 * 1024, "pair-mode LDS");
 static_assert(kOz2A == 2 * kOzA / 2 && 4 * kOz2A == 2 * kOzTileBytes, "a pair is two kernel-1 tiles");
@@ -983,50 +914,36 @@ __global__ __launch_bounds__(kOzThreads, 1) void predict_oz2_kernel(
     int64_t m, int64_t ldp, double m0, double *__restrict__ part, double *__restrict__ mean,
     const char *__restrict__ kzt) {
     __shared__ __attribute__((aligned(16))) char smem[kOz2Smem];
-    const int bid = blockIdx.x;
-    const int rng = (P % 8 == 0) ? (bid % 8) * (P / 8) + bid / 8 : bid;
-    const int k0 = max(seg[rng], 0), k1 = min(seg[rng + 1], n_items);
+    const PlanRange range = plan_range(seg, P, n_items);
+    const int k0 = range.k0, k1 = range.k1;
     if (k0 >= k1) return;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int r = lane & 15;
     const int g = lane >> 4;
-    const int4 *dwin = reinterpret_cast<const int4 *>(smem + 2 * kOz2Slot + kKzt2);
-    const unsigned short *lwin = reinterpret_cast<const unsigned short *>(smem + 2 * kOz2Slot + kKzt2 + 2048);
+    const PlanWindows win(smem + 2 * kOz2Slot + kKzt2, nI);
+    const PlanRefill refill(smem + 2 * kOz2Slot + kKzt2, desc, tl, lane, wave == 1, wave == 2);
     const char *tz = smem + 2 * kOz2Slot;   // the (pair, half)'s K* table piece
 
     typedef __attribute__((address_space(3))) char lds_char;
     const uint32_t lds_smem = (uint32_t)(uintptr_t)(lds_char *)(smem);
     const uint32_t lds_wave = lds_smem + (uint32_t)__builtin_amdgcn_readfirstlane(wave) * 1024u;
     const uint32_t lds_tz = lds_smem + 2u * kOz2Slot;
-    const uint32_t lds_dwin = lds_tz + (uint32_t)kKzt2;
-    const uint32_t lds_lwin = lds_dwin + 2048u;
     const char *gA = aoz + wave * 1024 + lane * 16;
     const char *gE = reinterpret_cast<const char *>(eoz) + lane * 16;
-    const char *gD = reinterpret_cast<const char *>(desc) + lane * 16;
-    const char *gL = reinterpret_cast<const char *>(tl) + lane * 16;
     const char *gZ = kzt + lane * 16;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const int npr = kTilesPerRowBlockStep * nI / 2;   // pairs per query block in the table
-#define SBO_OZ_DMA16(gsrc, ldst)                                                                         \
-    do {                                                                                                 \
-        uint32_t keep_;                                                                                  \
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t" \
-                     "s_mov_b32 m0, %0"                                                                  \
-                     : "=&s"(keep_)                                                                      \
-                     : "v"(gsrc), "s"(ldst)                                                              \
-                     : "memory");                                                                        \
-    } while (0)
     // quarter q_ of pair (first packed tile Tp_) into slot buf
 #define SBO_OZ2_STAGE(Tp_, q_, buf)                                                                      \
     do {                                                                                                 \
         const char *s_ = gA + (int64_t)(Tp_) * kOzTileBytes + (q_) * kOz2A;                              \
         const uint32_t d_ = __builtin_amdgcn_readfirstlane(lds_wave + (uint32_t)(buf) * kOz2Slot);       \
         _Pragma("unroll") for (int j_ = 0; j_ < kOz2A / (1024 * kOzWaves); ++j_)                         \
-            SBO_OZ_DMA16(s_ + j_ * kOzWaves * 1024, d_ + (uint32_t)(j_ * kOzWaves * 1024));              \
+            lds_dma16(s_ + j_ * kOzWaves * 1024, d_ + (uint32_t)(j_ * kOzWaves * 1024));                 \
         if (wave == 0 && lane < 4)                                                                       \
-            SBO_OZ_DMA16(gE + (int64_t)(Tp_) * 64,                                                       \
+            lds_dma16(gE + (int64_t)(Tp_) * 64,                                                          \
                          __builtin_amdgcn_readfirstlane(lds_smem + (uint32_t)((buf) * kOz2Slot + kOz2A)));    \
     } while (0)
     // the table piece of (query block qb_, pair pr_): each wave moves exactly
@@ -1037,60 +954,31 @@ __global__ __launch_bounds__(kOzThreads, 1) void predict_oz2_kernel(
     do {                                                                                                 \
         const char *z_ = gZ + ((int64_t)(qb_) * npr + (pr_)) * kKzt2;                                    \
         _Pragma("unroll") for (int u_ = 0; u_ < 2 * kOzKDigits; ++u_)                                    \
-            SBO_OZ_DMA16(z_ + wave * 8192 + u_ * 1024, lds_tz + (uint32_t)(wave_u * 8192 + u_ * 1024));  \
-        if (lane < 4) SBO_OZ_DMA16(z_ + kKzt2E + wave * 64, lds_tz + (uint32_t)(kKzt2E + wave_u * 64));  \
-        if (lane < 8) SBO_OZ_DMA16(z_ + kKzt2Mu + wave * 128, lds_tz + (uint32_t)(kKzt2Mu + wave_u * 128)); \
+            lds_dma16(z_ + wave * 8192 + u_ * 1024, lds_tz + (uint32_t)(wave_u * 8192 + u_ * 1024));     \
+        if (lane < 4) lds_dma16(z_ + kKzt2E + wave * 64, lds_tz + (uint32_t)(kKzt2E + wave_u * 64));     \
+        if (lane < 8) lds_dma16(z_ + kKzt2Mu + wave * 128, lds_tz + (uint32_t)(kKzt2Mu + wave_u * 128)); \
     } while (0)
-#define SBO_OZ_DESC_WINDOW(w_)                                                                           \
-    do {                                                                                                 \
-        if (wave == 1) SBO_OZ_DMA16(gD + (int64_t)(w_) * 1024, lds_dwin + (uint32_t)((w_) & 1) * 1024u); \
-    } while (0)
-#define SBO_OZ_LIST_WINDOW(w_)                                                                           \
-    do {                                                                                                 \
-        if (wave == 2) SBO_OZ_DMA16(gL + (int64_t)(w_) * 1024, lds_lwin + (uint32_t)((w_) & 1) * 1024u); \
-    } while (0)
-    auto desc_at = [&](int k) {
-        const int4 d = dwin[((k / kOzDescWin) & 1) * kOzDescWin + k % kOzDescWin];
-        const int I = min(max(__builtin_amdgcn_readfirstlane(d.x), 0), nI - 1);
-        return make_int4(I, __builtin_amdgcn_readfirstlane(d.y), __builtin_amdgcn_readfirstlane(d.z),
-                         __builtin_amdgcn_readfirstlane(d.w));
-    };
-    auto entry_off = [](const int4 &d) {
-        return (uint64_t)(uint32_t)d.z | ((uint64_t)((uint32_t)d.w >> 16) << 32);
-    };
-    auto list_at = [&](uint64_t e, int I) {
-        const int t = __builtin_amdgcn_readfirstlane((int)lwin[((e / kOzListWin) & 1) * kOzListWin + e % kOzListWin]) &
-                      ((1 << kLevelShift) - 1);
-        return min(t, kTilesPerRowBlockStep * (I + 1) - 1);
-    };
     // the pair of list entry e (the item's j-th of cnt): its index, and how
     // many entries it takes (2 when entry e + 1 is the partner)
     auto pair_at = [&](uint64_t e, int I, int j, int cnt, int &ne) {
-        const int t0 = list_at(e, I);
+        const int t0 = win.list_at(e, I);
         ne = 1;
-        if ((t0 & 1) == 0 && j + 1 < cnt && list_at(e + 1, I) == t0 + 1) ne = 2;
+        if ((t0 & 1) == 0 && j + 1 < cnt && win.list_at(e + 1, I) == t0 + 1) ne = 2;
         return t0 >> 1;
     };
 
     // ---- prologue
-    SBO_OZ_DESC_WINDOW(k0 / kOzDescWin);
-    SBO_OZ_DESC_WINDOW(k0 / kOzDescWin + 1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int4 dc = desc_at(k0);
+    refill.begin_items(k0);
+    int4 dc = win.desc_at(k0);
     uint64_t e = entry_off(dc);
-    SBO_OZ_LIST_WINDOW(e / kOzListWin);
-    SBO_OZ_LIST_WINDOW(e / kOzListWin + 1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    refill.begin_entries(e);
     int ne = 1;
-    int pr = pair_at(e, dc.x, 0, dc.w & 0xffff, ne);
+    int pr = pair_at(e, dc.x, 0, plan_item_count(dc.w), ne);
     int pr0 = pr, ne0 = ne;      // the item's first pair (the second half starts there again)
     SBO_OZ2_STAGE(tile_start(dc.x) + 2 * pr, 0, 0);
     SBO_OZ2_TABLE(dc.y, pr);
     int64_t q = (int64_t)dc.y * kBN + wave * 16 + r;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    plan_dma_landed();
 
     f64x4 acc[kOzHalfRB];
 #pragma unroll
@@ -1103,7 +991,7 @@ __global__ __launch_bounds__(kOzThreads, 1) void predict_oz2_kernel(
     int k = k0, hp = 0, j = 0, sq = 0, cur = 0;
     bool table_ahead = false;
     for (;;) {
-        const int cnt = dc.w & 0xffff;
+        const int cnt = plan_item_count(dc.w);
         // the next stage: the pair's other quarter of this half, the next pair
         // of this half, the item's first pair again for the second half, or
         // the first pair of item k + 1
@@ -1130,19 +1018,19 @@ __global__ __launch_bounds__(kOzThreads, 1) void predict_oz2_kernel(
         int4 dn = dc;
         if (more) {
             if (kn != k) {
-                dn = desc_at(kn);
-                if (kn % kOzDescWin == 0) SBO_OZ_DESC_WINDOW(kn / kOzDescWin + 1);
+                dn = win.desc_at(kn);
+                refill.enter_item(kn);
             }
             if (restart) {
                 // the item's entries again: its first pair from registers, the
                 // list windows reloaded for the pairs after it
                 prn = pr0;
                 nen = ne0;
-                SBO_OZ_LIST_WINDOW(en / kOzListWin);
-                SBO_OZ_LIST_WINDOW(en / kOzListWin + 1);
+                refill.list_window(en / kPlanListWindow);
+                refill.list_window(en / kPlanListWindow + 1);
             } else if (sn == 0) {
-                if (en / kOzListWin != e / kOzListWin) SBO_OZ_LIST_WINDOW(en / kOzListWin + 1);
-                prn = pair_at(en, dn.x, jn, dn.w & 0xffff, nen);
+                refill.move_entry(e, en);
+                prn = pair_at(en, dn.x, jn, plan_item_count(dn.w), nen);
             }
             SBO_OZ2_STAGE(tile_start(dn.x) + 2 * prn, 2 * hn + sn, cur ^ 1);
         }
@@ -1173,8 +1061,8 @@ __global__ __launch_bounds__(kOzThreads, 1) void predict_oz2_kernel(
                     prN = pr0;
                     qbN = dc.y;
                 } else if (k + 1 < k1) {
-                    const int4 d2 = desc_at(k + 1);
-                    prN = pair_at(entry_off(d2), d2.x, 0, d2.w & 0xffff, neN);
+                    const int4 d2 = win.desc_at(k + 1);
+                    prN = pair_at(entry_off(d2), d2.x, 0, plan_item_count(d2.w), neN);
                     qbN = d2.y;
                 }
                 if (qbN >= 0) {
@@ -1242,9 +1130,6 @@ __global__ __launch_bounds__(kOzThreads, 1) void predict_oz2_kernel(
     }
 #undef SBO_OZ2_STAGE
 #undef SBO_OZ2_TABLE
-#undef SBO_OZ_DESC_WINDOW
-#undef SBO_OZ_LIST_WINDOW
-#undef SBO_OZ_DMA16
 }
 
 // The pair-mode K* table (SBO_OPT_PRECISE_KERNEL 4): one workgroup per (pair,

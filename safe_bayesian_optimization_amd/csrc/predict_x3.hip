@@ -48,6 +48,9 @@ namespace {
 
 constexpr int kXH = x3r::kXH;
 constexpr int kXA = x3r::kXA;
+// the split sweep reads its step records by windows of its own; the plan's
+// buffers are padded for plan_format.hpp's
+static_assert(x3r::kRecWin == kPlanRecWindow, "the record window the plan pads for");
 
 // Per k-tile coordinates in natural order per half: kc3[t*256 + h*128 + c*32 + i]
 // = (x, y, sf2 alpha, 0)[c] of k = 64t + 32h + i, from the kcoord layout

@@ -2875,8 +2875,7 @@ SBO_API sbo_status sbo_debug_plan(sbo_ctx *ctx, const float *qx, const float *qy
     SBO_HIP(hipMemcpyAsync(hthr.data(), thr, (size_t)items, hipMemcpyDeviceToHost, ctx->stream));
     SBO_HIP(hipMemcpyAsync(&last, scan + items - 1, 8, hipMemcpyDeviceToHost, ctx->stream));
     SBO_HIP(hipStreamSynchronize(ctx->stream));
-    const unsigned long long cmask = (1ull << 40) - 1ull;
-    const int64_t total = (int64_t)(last & cmask), nne = (int64_t)(last >> 40);
+    const int64_t total = (int64_t)sbo::plan_key_count(last), nne = sbo::plan_key_items(last);
     const int64_t need = 4 + 2 * items + 4 * total;
     *n_out = need;
     if (!host_buf) return SBO_OK;
@@ -2895,21 +2894,21 @@ SBO_API sbo_status sbo_debug_plan(sbo_ctx *ctx, const float *qx, const float *qy
         for (int64_t qb = 0; qb < nQ; ++qb) {
             const int64_t item = (nI - 1 - I) * nQ + qb;   // plan_item, row-block-major
             it[2 * (I * nQ + qb)] = (int32_t)hthr[(size_t)item];
-            it[2 * (I * nQ + qb) + 1] = (int32_t)(hkey[(size_t)item] & cmask);
+            it[2 * (I * nQ + qb) + 1] = (int32_t)sbo::plan_key_count(hkey[(size_t)item]);
         }
     int64_t r = 0;
     for (int64_t k = 0; k < nne; ++k) {
         const int4 d = hdesc[(size_t)k];
-        const int cnt = d.w & 0xffff;
-        const uint64_t off = (uint64_t)(uint32_t)d.z | ((uint64_t)((uint32_t)d.w >> 16) << 32);
+        const int cnt = sbo::plan_item_count(d.w);
+        const uint64_t off = sbo::plan_item_offset(d.z, d.w);
         SBO_CHECK(off + (uint64_t)cnt <= (uint64_t)total && r + cnt <= total, SBO_E_DEVICE,
                   "sbo_debug_plan: a descriptor points outside the tile list");
         for (int i = 0; i < cnt; ++i, ++r) {
             const unsigned short te = htl[(size_t)off + i];
             rec[4 * r] = d.x;
             rec[4 * r + 1] = d.y;
-            rec[4 * r + 2] = te & ((1 << sbo::kLevelShift) - 1);
-            rec[4 * r + 3] = te >> sbo::kLevelShift;
+            rec[4 * r + 2] = sbo::plan_entry_tile(te);
+            rec[4 * r + 3] = sbo::plan_entry_level(te);
         }
     }
     SBO_CHECK(r == total, SBO_E_DEVICE, "sbo_debug_plan: the descriptors' counts do not sum to the plan's total");

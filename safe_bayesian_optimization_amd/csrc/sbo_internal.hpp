@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/sbo.h"
+#include "plan_format.hpp"
 
 namespace sbo {
 
@@ -204,8 +205,8 @@ hipError_t launch_plan_cost(hipStream_t s, int64_t npad, int64_t m, int P, const
 void plan_views(int64_t npad, int64_t m, int P, const void *work, const int4 **desc, const unsigned short **tl,
                 const int **seg, const int4 **rec = nullptr);
 // Per item of the plan in `work` (index: plan_item order, row-block-major for
-// order_blk 0: (nI - 1 - I) * nQ + qb): key = kept-tile count (low 40 bits) |
-// non-empty << 40, its inclusive scan, and the budget threshold + 1.
+// order_blk 0: (nI - 1 - I) * nQ + qb): the plan key (plan_key_pack), its
+// inclusive scan, and the budget threshold + 1.
 // nonempty (may be null): per query block (nI + 63) / 64 words, bit I set when
 // item (I, qb) keeps a tile (launch_acquire).
 void plan_item_views(int64_t npad, int64_t m, int P, const void *work, const unsigned long long **key,
@@ -222,14 +223,12 @@ size_t x3_coord_bytes(int64_t npad);
 // (ax3 null: the coordinates only; kc3 null: the planes only)
 hipError_t launch_pack_x3(hipStream_t s, const float *aug, const float *kcoord, int64_t npad, int64_t I0, int layout,
                           char *ax3, float *kc3);
-// tile-list entry of the plan: k-tile index | precision level code << kLevelShift
-constexpr int kLevelShift = 14;
-// Step record of the split sweep (plan_rec_kernel), one int4 per kept tile in
-// sweep order: x = the packed tile's offset in the split operand (KiB, two
-// stages of 48: the tile's halves), y = its k-tile's coordinate offset in kc3 (floats),
-// z = query block, w = row block | level code << 16 | first / last tile of
-// its item (kRecFirst, kRecLast).
-constexpr int kRecFirst = 1 << 20, kRecLast = 1 << 21;
+// (the plan's descriptors, tile-list entries, keys and the split sweep's step
+// records: plan_format.hpp)
+__host__ __device__ inline int4 plan_item_int4(int I, int qb, uint64_t off, int cnt) {
+    const PlanItemWords p = plan_item_pack(I, qb, off, cnt);
+    return make_int4(p.x, p.y, p.z, p.w);
+}
 // the split sweeps that honour the plan's precision levels
 inline bool x3_levels(int variant) { return variant == 3 || variant == 23 || variant == 24 || variant == 30 || variant == 32 || variant == 33 || variant == 39 || variant == 41 || variant == 42 || variant == 43 || variant == 46 || variant == 47 || variant == 48 || variant == 49 || variant == 51 || variant == 52 || variant == 53 || variant == 54 || variant == 55 || variant == 56 || variant == 57 || (variant >= 58 && variant <= 62); }
 // Sweeps the product library accepts (all compute the full result; 3 is the
