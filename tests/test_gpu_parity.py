@@ -656,7 +656,9 @@ def test_tile_skip_exact_and_bounded(dev, mapper):
     at most 1 ulp on a vanishing fraction of points.  Auto cutoff (default):
     within its stated error budget (2^-B sf2 on sigma^2, 2^-B sf on mu, B =
     SBO_OPT_SKIP_BUDGET, default 20; also checked at B = 27)
-    of the dense sweep, same argmax."""
+    of the dense sweep, same argmax.
+    (The exact check of the budget lives in test_gpu_plan_budget.py; the + 4 ulp
+    here is the f32 output noise.)"""
     wl = synthetic(8192, 200, 160, seed=21)
     gm = TerrainMapper(0, wl.hyper, ctx=mapper.ctx)
     gm.fit(wl.x, wl.y, wl.obs)
@@ -713,7 +715,9 @@ def test_loose_budgets_hold(mapper, budget):
     at reduced precision or are dropped, so the effect of the plan's bounds is
     far above the f32 noise: mu and sigma^2 still stay within 2^-B of the
     dense all-six-products sweep, i.e. the per-piece level increments and the
-    drop bounds are upper bounds in practice too."""
+    drop bounds are upper bounds in practice too.
+    (The exact check of the budget lives in test_gpu_plan_budget.py; the + 4 ulp
+    here is the f32 output noise.)"""
     wl = synthetic(4096, 160, 120, seed=33)
     gm = TerrainMapper(0, wl.hyper, ctx=mapper.ctx)
     gm.fit(wl.x, wl.y, wl.obs)
@@ -748,7 +752,9 @@ def test_plan_beyond_the_bin_cache(mapper):
     re-evaluated) and five 64-tile chunks in the plan's code bitmap.  At a
     loose budget (B = 13: every level and drops in use) and at the default
     B = 20, mu and sigma^2 stay within 2^-B of the dense all-six-products
-    sweep, as in test_loose_budgets_hold."""
+    sweep, as in test_loose_budgets_hold.
+    (The exact check of the budget lives in test_gpu_plan_budget.py; the + 4 ulp
+    here is the f32 output noise.)"""
     wl = synthetic(20480, 96, 96, seed=35)
     gm = TerrainMapper(0, wl.hyper, ctx=mapper.ctx)
     gm.fit(wl.x, wl.y, wl.obs)
