@@ -673,20 +673,28 @@ SBO_API sbo_status sbo_debug_inverse_plan(int64_t n, int64_t ld, int64_t base, i
  * exported state use it too) and sbo_get_jitter reports it; 0 keeps the
  * reference's behaviour of reporting the failure. */
 #define SBO_OPT_JITTER_RETRIES 10
-/* SBO_OPT_PRECISION (-1 auto default | 0 fast | 1 f64): the predictive
+/* SBO_OPT_PRECISION (-1 auto default | 0 fast | 1 precise): the predictive
  * sweep's arithmetic.  0: the split-operand bf16 sweep (f32-accurate products,
  * f32 accumulation, A = sf2 L^-1 rounded to f32).  1: the precise sweep -- A
- * in f64 from the fit's f64 inverse, K* in f64, f64 MFMA
- * (v_mfma_f64_16x16x4_f64) and f64 sums; about 3-5x the fast sweep's time on
- * the same tiles.  -1: every sbo_fit (and an sbo_append once N grew by a
- * quarter since the last probe, SBO_OPT_REPROBE) sweeps a probe set -- a
- * 32 x 32 grid over the training box and up to 512 training locations
- * (sbo_get_probe) -- both ways and ticks with the precise sweep when the fast
- * sweep's variance error there, max |d var| / max var, exceeds 5e-6 (the 1e-5 contract over the largest whole-grid / probe ratio measured, 1.77;
- * 5e-6 * 2^(20 - B) for a looser SBO_OPT_SKIP_BUDGET B < 20):
- * dense data, where the variance is orders below sf2 and sf2 - |V|^2 cancels
- * (config/lpsc.yaml's own box at N = 16384).  The precise sweep's skip budget
- * is 2^-B times the smallest probe variance (SBO_OPT_SKIP_BUDGET = B).  Needs
+ * in f64 from the fit's f64 inverse, products and sums to f64 accuracy by
+ * the kernel SBO_OPT_PRECISE_KERNEL names (default 3: int8 digit slices on
+ * the int8 matrix cores, K*'s digits from a table; 0: f64 MFMA); about 3-5x
+ * the fast sweep's time on the same tiles.  -1: every sbo_fit, and an
+ * sbo_append once N has grown by SBO_OPT_REPROBE percent (default 25) since
+ * the last probe, sweeps a probe set both ways -- a 32 x 32 lattice over the
+ * training box and at most 512 training locations, the stored points at
+ * positions stride / 2 + i stride over all of [0, n) with stride =
+ * ceil(n / 512) (SBO_OPT_PROBE_SIZE, sbo_get_probe) -- and ticks with the
+ * precise sweep when the fast sweep's variance error there, max |d var| /
+ * max var, exceeds 5e-6 (5e-6 * 2^(20 - B) for a looser SBO_OPT_SKIP_BUDGET
+ * B < 20).  The threshold rests on the envelope whole-grid error <=
+ * 1.62 * probe + 1e-6 (9.1e-6 at the threshold, inside the 1e-5 contract),
+ * calibrated at N = 8192 and held at the threshold itself by
+ * tests/test_gpu_probe_decision.py: dense data, where the
+ * variance is orders below sf2 and sf2 - |V|^2 cancels (config/lpsc.yaml's
+ * own box from a few hundred points on), runs precise.  The precise sweep's
+ * skip budget is 2^-B times the smallest probe variance
+ * (SBO_OPT_SKIP_BUDGET = B).  Needs
  * SBO_OPT_INVERSE_BITS 64 and a fitted factor: an imported state always runs
  * the fast sweep.  Setting it on a fitted context takes effect at once. */
 #define SBO_OPT_PRECISION 11
@@ -899,16 +907,17 @@ SBO_API sbo_status sbo_trim(sbo_ctx *ctx);
  * options are unchanged.  Synchronous. */
 SBO_API sbo_status sbo_warmup(sbo_ctx *ctx, int64_t n_cap, int64_t m_cap, sbo_hyper hyper);
 
-/* The sweep the ticks run (precise = 1: the f64 sweep) and the last probe
+/* The sweep the ticks run (precise = 1: the precise sweep) and the last probe
  * (SBO_OPT_PRECISION): the fast sweep's normwise variance error against the
- * precise one on the 32 x 32 probe grid and that grid's smallest and largest
- * variance (-1 when no probe ran).  SBO_E_STATE before a fit. */
+ * precise one on the probe set (lattice and training locations) and that
+ * set's smallest and largest variance (-1 when no probe ran).  SBO_E_STATE
+ * before a fit. */
 SBO_API sbo_status sbo_get_precision(const sbo_ctx *ctx, int *precise, double *probe_err, double *probe_var_min,
                                      double *probe_var_max);
 
 /* The last precision probe in detail (SBO_OPT_PRECISION): its query set is a
  * 32 x 32 grid over the training box (m_grid points) and m_train training
- * locations (every (n / m_train)-th stored point); err = the fast sweep's
+ * locations (every ceil(n / 512)-th stored point over all n); err = the fast sweep's
  * max |d var| over both / the largest variance of both (the decision's
  * number, also sbo_get_precision's probe_err), err_grid / err_train = each
  * part's own max |d var| / its own largest variance.  err* = -1 when no
