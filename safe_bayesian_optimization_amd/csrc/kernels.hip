@@ -250,894 +250,6 @@ __global__ void pack_kcoord_kernel(const float *__restrict__ x, const float *__r
     c[2 * kBK + o] = in ? sf2 * alpha[k] : 0.0f;
 }
 
-// ---- blocked Cholesky (a2), the factorization step rocSOLVER's spotrf
-// spends most of its time in (unblocked potf2 panels, one small workgroup
-// each): the kb x kb diagonal block of step k0, in LDS, right-looking in
-// panels of kCholPanel columns.  A panel is factored by wave 0 alone in
-// registers (lane l holds rows jb + l and jb + 64 + l of the panel; the pivot
-// row's values come from their lane by v_readlane, no barrier per column);
-// the trailing lower triangle then takes the panel's rank-kCholPanel update
-// from all four waves in 4 x 4 element tiles.  Every element sees the same
-// fmaf sequence as the column-by-column algorithm (column j ascending,
-// fmaf(-L[i][j], L[l][j], a)), so the factor is bitwise that of a plain
-// right-looking Cholesky of the block.  f32 as spotrf, correctly rounded sqrt
-// and division.  A pivot that is not > 0 (or NaN) stops the factorization:
-// info = k0 + j + 1 (the leading minor, rocSOLVER's convention); later blocks
-// see info != 0 and leave their data alone.  Column-major, lda = ld; only
-// i >= j is written.
-constexpr int kCholPanel = 8;
-#ifdef SBO_CHOL_STAMPS
-// tools/chol_micro.hip only: s_memtime phase stamps of the fit's chain kernels
-__device__ unsigned long long g_chol_stamps[16];
-#define SBO_CSTAMP(i) do { if (threadIdx.x == 0 && blockIdx.x == 0) g_chol_stamps[i] = __builtin_amdgcn_s_memtime(); } while (0)
-#define SBO_CSTAMP_ADD(i, t0) do { if (threadIdx.x == 0 && blockIdx.x == 0) g_chol_stamps[i] += __builtin_amdgcn_s_memtime() - (t0); } while (0)
-#else
-#define SBO_CSTAMP(i) do { } while (0)
-#define SBO_CSTAMP_ADD(i, t0) do { } while (0)
-#endif
-__device__ __forceinline__ float lane_value(float v, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__global__ __launch_bounds__(256) void chol_diag_kernel(float *__restrict__ A, int64_t ld, int kb, int64_t k0,
-                                                        int *__restrict__ info) {
-    static_assert(kCholNB <= 128, "two panel rows per lane of wave 0");
-    // row stride 132: a row's 8 panel columns are two aligned float4 reads
-    __shared__ __attribute__((aligned(16))) float a[kCholNB][kCholNB + 4];
-    __shared__ int s_bad;
-    if (*info != 0) return;
-    SBO_CSTAMP(0);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // the block in, kCholLoad independent loads per thread in flight at a time
-    // (one at a time, the reads' latency was most of this kernel)
-    constexpr int kCholLoad = 16;
-    for (int e0 = 0; e0 < kb * kb; e0 += 256 * kCholLoad) {
-        float v[kCholLoad];
-#pragma unroll
-        for (int u = 0; u < kCholLoad; ++u) {
-            const int e = e0 + u * 256 + tid;
-            const int i = e % kb, j = e / kb;
-            v[u] = (e < kb * kb && i >= j) ? A[i + (int64_t)j * ld] : 0.0f;
-        }
-#pragma unroll
-        for (int u = 0; u < kCholLoad; ++u) {
-            const int e = e0 + u * 256 + tid;
-            const int i = e % kb, j = e / kb;
-            if (e < kb * kb && i >= j) a[i][j] = v[u];
-        }
-    }
-    if (tid == 0) s_bad = 0;
-    __syncthreads();
-    SBO_CSTAMP(1);
-#ifdef SBO_CHOL_STAMPS
-    if (threadIdx.x == 0) { g_chol_stamps[4] = 0; g_chol_stamps[5] = 0; }
-#endif
-    for (int jb = 0; jb < kb; jb += kCholPanel) {
-        const int w = min(kCholPanel, kb - jb);
-#ifdef SBO_CHOL_STAMPS
-        const unsigned long long tp0 = __builtin_amdgcn_s_memtime();
-#endif
-        if (wave == 0) {
-            const int r0 = jb + lane, r1 = jb + 64 + lane;
-            float p0[kCholPanel], p1[kCholPanel];
-#pragma unroll
-            for (int c = 0; c < kCholPanel; ++c) {
-                p0[c] = (r0 < kb && c < w) ? a[r0][jb + c] : 0.0f;
-                p1[c] = (r1 < kb && c < w) ? a[r1][jb + c] : 0.0f;
-            }
-            int bad = 0;
-#pragma unroll
-            for (int c = 0; c < kCholPanel; ++c) {
-                if (c >= w || bad) continue;   // uniform
-                const int j = jb + c;
-                const float djj = lane_value(p0[c], c);   // row j is lane c's first row
-                // a pivot below FLT_MIN (denormal, flushed or zero) is not
-                // positive definite either: its v_rsq_f32 may overflow
-                if (!(djj >= 1.17549435e-38f) || !(djj < __builtin_huge_valf())) {
-                    bad = j + 1;
-                    continue;
-                }
-                // 1/sqrt(djj) once (v_rsq_f32), the column scaled by it and
-                // the pivot as djj * (1/sqrt(djj)): one transcendental on the
-                // serial chain instead of a sqrt and two divisions
-                const float rs = __builtin_amdgcn_rsqf(djj);
-                if (r0 > j) p0[c] = p0[c] * rs;
-                else if (r0 == j) p0[c] = djj * rs;
-                p1[c] = p1[c] * rs;   // r1 > j always
-#pragma unroll
-                for (int c2 = c + 1; c2 < kCholPanel; ++c2) {
-                    if (c2 >= w) continue;
-                    const float lc2 = lane_value(p0[c], c2);   // L[jb + c2][j], lane c2's (already scaled)
-                    if (r0 >= jb + c2) p0[c2] = fmaf(-p0[c], lc2, p0[c2]);
-                    p1[c2] = fmaf(-p1[c], lc2, p1[c2]);
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < kCholPanel; ++c) {
-                if (c < w && r0 < kb && r0 >= jb + c) a[r0][jb + c] = p0[c];
-                if (c < w && r1 < kb) a[r1][jb + c] = p1[c];
-            }
-            if (lane == 0 && bad) s_bad = bad;
-        }
-        __syncthreads();
-        SBO_CSTAMP_ADD(4, tp0);
-        if (s_bad) break;
-#ifdef SBO_CHOL_STAMPS
-        const unsigned long long tu0 = __builtin_amdgcn_s_memtime();
-#endif
-        // rank-w update of the trailing lower triangle [t0, kb) in 4 x 4 tiles
-        const int t0 = jb + w, n2 = kb - t0;
-        const int nt = (n2 + 3) >> 2, ntiles = nt * (nt + 1) / 2;
-        for (int q = tid; q < ntiles; q += 256) {
-            int ti = (int)((sqrtf(8.0f * (float)q + 1.0f) - 1.0f) * 0.5f);
-            while ((ti + 1) * (ti + 2) / 2 <= q) ++ti;
-            while (ti * (ti + 1) / 2 > q) --ti;
-            const int tl = q - ti * (ti + 1) / 2;
-            const int i0 = t0 + 4 * ti, l0 = t0 + 4 * tl;
-            float li[4][kCholPanel], ll[4][kCholPanel];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                // rows past kb read (finite) padding rows of the array; columns
-                // past w are masked below
-                const float4 *pi = reinterpret_cast<const float4 *>(&a[min(i0 + r, kCholNB - 1)][jb]);
-                const float4 *pl = reinterpret_cast<const float4 *>(&a[min(l0 + r, kCholNB - 1)][jb]);
-                const float4 i0v = pi[0], i1v = pi[1], l0v = pl[0], l1v = pl[1];
-                const float iv[8] = {i0v.x, i0v.y, i0v.z, i0v.w, i1v.x, i1v.y, i1v.z, i1v.w};
-                const float lv[8] = {l0v.x, l0v.y, l0v.z, l0v.w, l1v.x, l1v.y, l1v.z, l1v.w};
-#pragma unroll
-                for (int c = 0; c < kCholPanel; ++c) {
-                    li[r][c] = (i0 + r < kb && c < w) ? iv[c] : 0.0f;
-                    ll[r][c] = (l0 + r < kb && c < w) ? lv[c] : 0.0f;
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int i = i0 + r, l = l0 + u;
-                    if (i < kb && l <= i) {
-                        float v = a[i][l];
-#pragma unroll
-                        for (int c = 0; c < kCholPanel; ++c)
-                            if (c < w) v = fmaf(-li[r][c], ll[u][c], v);
-                        a[i][l] = v;
-                    }
-                }
-        }
-        __syncthreads();
-        SBO_CSTAMP_ADD(5, tu0);
-    }
-    SBO_CSTAMP(2);
-    if (s_bad) {
-        if (tid == 0) atomicCAS(info, 0, (int)(k0 + s_bad));
-        return;
-    }
-    for (int e = tid; e < kb * kb; e += 256) {
-        const int i = e % kb, j = e / kb;
-        if (i >= j) A[i + (int64_t)j * ld] = a[i][j];
-    }
-    SBO_CSTAMP(3);
-}
-
-// The same diagonal block in 16-column panels with the trailing updates on
-// the matrix cores (chol_diag_kernel's default replacement).  The block is
-// padded to 128 x 128 with the identity (pivots 1, zero coupling: the real
-// part sees exactly the arithmetic of the kb x kb factorization).  Panel:
-// wave 0 in registers, as above (16 columns).  Trailing update: the lower
-// triangle of 16 x 16 blocks behind the panel, spread over the four waves,
-// each block C -= L_i L_l^T as four v_mfma_f32_16x16x4_f32 over the panel's
-// 16 columns -- an MFMA is bit for bit a k-ordered fmaf chain
-// (cdna_hip_programming.md section 3), so every element still sees
-// fmaf(-L[i][j], L[l][j], a) with j ascending and the factor is bitwise that
-// of chol_diag_kernel.  The block in: all 64 loads per thread in flight;
-// out: 64 stores per thread issued back to back.
-constexpr int kCholPW = 16;
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void chol_diag_mfma_kernel(float *__restrict__ A, int64_t ld, int kb, int64_t k0,
-                                                             int *__restrict__ info) {
-    static_assert(kCholNB == 128, "two panel rows per lane of wave 0, 8 x 16 blocks");
-    __shared__ __attribute__((aligned(16))) float a[kCholNB][kCholNB + 4];
-    __shared__ int s_bad;
-    if (*info != 0) return;
-    SBO_CSTAMP(0);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // thread (i, h): row i = tid & 127 of columns h, h + 2, h + 4, ... (coalesced
-    // over i), 16 loads in flight per batch
-    // (every load unconditional, from inside the kb x kb block: the rows and
-    // columns past kb read its last row / column and are replaced after)
-    const int li = tid & (kCholNB - 1), lh = tid >> 7;
-    const float *colp = A + min(li, kb - 1);
-    for (int j0 = 0; j0 < kCholNB; j0 += 32) {
-        float v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = colp[(int64_t)min(j0 + 2 * u + lh, kb - 1) * ld];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int j = j0 + 2 * u + lh;
-            a[li][j] = (li < kb && j < kb && li >= j) ? v[u] : (li == j ? 1.0f : 0.0f);
-        }
-    }
-    if (tid == 0) s_bad = 0;
-    __syncthreads();
-    SBO_CSTAMP(1);
-#ifdef SBO_CHOL_STAMPS
-    if (threadIdx.x == 0) { g_chol_stamps[4] = 0; g_chol_stamps[5] = 0; }
-#endif
-    for (int jb = 0; jb < kCholNB; jb += kCholPW) {
-#ifdef SBO_CHOL_STAMPS
-        const unsigned long long tp0 = __builtin_amdgcn_s_memtime();
-#endif
-        if (wave == 0) {
-            const int r0 = jb + lane, r1 = jb + 64 + lane;
-            const int q0 = min(r0, kCholNB - 1), q1 = min(r1, kCholNB - 1);
-            float p0[kCholPW], p1[kCholPW];
-#pragma unroll
-            for (int c4 = 0; c4 < kCholPW / 4; ++c4) {
-                const float4 u0 = reinterpret_cast<const float4 *>(&a[q0][jb])[c4];
-                const float4 u1 = reinterpret_cast<const float4 *>(&a[q1][jb])[c4];
-                p0[4 * c4] = u0.x; p0[4 * c4 + 1] = u0.y; p0[4 * c4 + 2] = u0.z; p0[4 * c4 + 3] = u0.w;
-                p1[4 * c4] = u1.x; p1[4 * c4 + 1] = u1.y; p1[4 * c4 + 2] = u1.z; p1[4 * c4 + 3] = u1.w;
-            }
-            int bad = 0;
-#pragma unroll
-            for (int c = 0; c < kCholPW; ++c) {
-                // (no early exit inside the unrolled panel: a failed pivot is
-                // recorded and the rest of the panel computes garbage that the
-                // block never stores)
-                const int j = jb + c;
-                const float djj = lane_value(p0[c], c);   // row j is lane c's first row
-                // (pivots below FLT_MIN fail too: v_rsq_f32 of a denormal may overflow)
-                if (bad == 0 && (!(djj >= 1.17549435e-38f) || !(djj < __builtin_huge_valf()))) bad = j + 1;
-                // every lane, no row tests: the lanes above the diagonal
-                // (row < column) compute values of the upper triangle that
-                // nothing reads (the lane-mask per column and row would be
-                // 136 live SGPR pairs); the diagonal lane's p0[c] is djj, so
-                // L_jj = djj * rs there
-                const float rs = __builtin_amdgcn_rsqf(djj);
-                p0[c] = p0[c] * rs;
-                p1[c] = p1[c] * rs;
-#pragma unroll
-                for (int c2 = c + 1; c2 < kCholPW; ++c2) {
-                    const float lc2 = lane_value(p0[c], c2);   // L[jb + c2][j], lane c2's (already scaled)
-                    p0[c2] = fmaf(-p0[c], lc2, p0[c2]);
-                    p1[c2] = fmaf(-p1[c], lc2, p1[c2]);
-                }
-            }
-            if (r0 < kCholNB) {
-#pragma unroll
-                for (int c = 0; c < kCholPW; ++c) a[r0][jb + c] = p0[c];
-            }
-            if (r1 < kCholNB) {
-#pragma unroll
-                for (int c = 0; c < kCholPW; ++c) a[r1][jb + c] = p1[c];
-            }
-            if (lane == 0 && bad) s_bad = bad;
-        }
-        __syncthreads();
-        SBO_CSTAMP_ADD(4, tp0);
-        if (s_bad) break;
-#ifdef SBO_CHOL_STAMPS
-        const unsigned long long tu0 = __builtin_amdgcn_s_memtime();
-#endif
-        // rank-16 update of the trailing lower triangle, 16 x 16 blocks
-        const int t0 = jb + kCholPW, nbt = (kCholNB - t0) / 16, nblk = nbt * (nbt + 1) / 2;
-        const int fi = lane & 15, fk = lane >> 4;   // operand lane map: A[fi][fk], B[fk][fi]; C row 4 fk + v, col fi
-        for (int q = wave; q < nblk; q += 4) {
-            int bi = 0, r = q;
-            while (r > bi) { r -= bi + 1; ++bi; }
-            const int i0 = t0 + 16 * bi, l0 = t0 + 16 * r;
-            f32x4_t acc;
-#pragma unroll
-            for (int v = 0; v < 4; ++v) acc[v] = a[i0 + 4 * fk + v][l0 + fi];
-#pragma unroll
-            for (int kk = 0; kk < kCholPW / 4; ++kk) {
-                const float av = -a[i0 + fi][jb + 4 * kk + fk];
-                const float bv = a[l0 + fi][jb + 4 * kk + fk];
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int v = 0; v < 4; ++v) a[i0 + 4 * fk + v][l0 + fi] = acc[v];
-        }
-        __syncthreads();
-        SBO_CSTAMP_ADD(5, tu0);
-    }
-    SBO_CSTAMP(2);
-    if (s_bad) {
-        if (tid == 0) atomicCAS(info, 0, (int)(k0 + s_bad));
-        return;
-    }
-    float *colw = A + li + (int64_t)lh * ld;
-    for (int j0 = 0; j0 < kCholNB; j0 += 32) {
-        float v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = a[li][j0 + 2 * u + lh];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int j = j0 + 2 * u + lh;
-            if (li < kb && j < kb && li >= j) colw[(int64_t)(j0 + 2 * u) * ld] = v[u];
-        }
-    }
-    SBO_CSTAMP(3);
-}
-
-// The same diagonal block, left-looking (round 5; SBO_OPT_CHOL_DIAG 1, the
-// default -- 2 keeps the right-looking chol_diag_mfma_kernel): before wave 0
-// factors a 16-column panel, the four waves bring the panel's columns up to
-// date with every factored column in one MFMA chain per 16 x 16 block, the
-// accumulator in registers -- each element sees fmaf(-L[i][j], L[l][j], a)
-// for j ascending as in the right-looking kernel's per-panel updates, so the
-// factor is bitwise the same -- instead of updating the whole trailing
-// triangle through LDS after every panel; and the panel itself on all four
-// waves (one row per lane) instead of wave 0 (two).
-__global__ __launch_bounds__(256) void chol_diag_ll_kernel(float *__restrict__ A, int64_t ld, int kb, int64_t k0,
-                                                           int *__restrict__ info) {
-    static_assert(kCholNB == 128, "two panel rows per lane of wave 0, 8 x 16 blocks");
-    __shared__ __attribute__((aligned(16))) float a[kCholNB][kCholNB + 4];
-    __shared__ int s_bad;
-    if (*info != 0) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // thread (i, h): row i = tid & 127 of columns h, h + 2, h + 4, ... (coalesced
-    // over i), 16 loads in flight per batch
-    // (every load unconditional, from inside the kb x kb block: the rows and
-    // columns past kb read its last row / column and are replaced after)
-    const int li = tid & (kCholNB - 1), lh = tid >> 7;
-    const float *colp = A + min(li, kb - 1);
-    for (int j0 = 0; j0 < kCholNB; j0 += 32) {
-        float v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = colp[(int64_t)min(j0 + 2 * u + lh, kb - 1) * ld];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int j = j0 + 2 * u + lh;
-            a[li][j] = (li < kb && j < kb && li >= j) ? v[u] : (li == j ? 1.0f : 0.0f);
-        }
-    }
-    if (tid == 0) s_bad = 0;
-    __syncthreads();
-    const int fi = lane & 15, fk = lane >> 4;   // operand lane map: A[fi][fk], B[fk][fi]; C row 4 fk + v, col fi
-    for (int jb = 0; jb < kCholNB; jb += kCholPW) {
-        if (jb > 0) {
-            // the panel's columns jb .. jb + 15, rows jb .. 127, from every
-            // factored column 0 .. jb - 1: one MFMA chain per 16 x 16 block
-            for (int q = wave; q < (kCholNB - jb) / 16; q += 4) {
-                const int i0 = jb + 16 * q;
-                f32x4_t acc;
-#pragma unroll
-                for (int v = 0; v < 4; ++v) acc[v] = a[i0 + 4 * fk + v][jb + fi];
-                for (int k16 = 0; k16 < jb; k16 += 16) {
-                    float av[4], bv[4];
-#pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) {
-                        av[kk] = -a[i0 + fi][k16 + 4 * kk + fk];
-                        bv[kk] = a[jb + fi][k16 + 4 * kk + fk];
-                    }
-#pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kk], bv[kk], acc, 0, 0, 0);
-                }
-#pragma unroll
-                for (int v = 0; v < 4; ++v) a[i0 + 4 * fk + v][jb + fi] = acc[v];
-            }
-            __syncthreads();
-        }
-        {
-            // the panel on all four waves: every wave factors the panel's top
-            // 16 x 16 triangle in lanes 0-15 (the pivot rows its other lanes
-            // need) and 48 of the rows below it in lanes 16-63; wave 0 writes
-            // the triangle.  Each row sees the same operations as on one wave.
-            const int r = lane < 16 ? jb + lane : jb + 16 + 48 * wave + (lane - 16);
-            const int q = min(r, kCholNB - 1);
-            float p0[kCholPW];
-#pragma unroll
-            for (int c4 = 0; c4 < kCholPW / 4; ++c4) {
-                const float4 u0 = reinterpret_cast<const float4 *>(&a[q][jb])[c4];
-                p0[4 * c4] = u0.x; p0[4 * c4 + 1] = u0.y; p0[4 * c4 + 2] = u0.z; p0[4 * c4 + 3] = u0.w;
-            }
-            __syncthreads();   // (every wave has read the triangle before wave 0 writes it)
-            int bad = 0;
-#pragma unroll
-            for (int c = 0; c < kCholPW; ++c) {
-                // (no early exit inside the unrolled panel: a failed pivot is
-                // recorded and the rest of the panel computes garbage that the
-                // block never stores)
-                const int j = jb + c;
-                const float djj = lane_value(p0[c], c);   // row j is lane c's
-                // (pivots below FLT_MIN fail too: v_rsq_f32 of a denormal may overflow)
-                if (bad == 0 && (!(djj >= 1.17549435e-38f) || !(djj < __builtin_huge_valf()))) bad = j + 1;
-                const float rs = __builtin_amdgcn_rsqf(djj);
-                p0[c] = p0[c] * rs;
-#pragma unroll
-                for (int c2 = c + 1; c2 < kCholPW; ++c2) {
-                    const float lc2 = lane_value(p0[c], c2);   // L[jb + c2][j], lane c2's (already scaled)
-                    p0[c2] = fmaf(-p0[c], lc2, p0[c2]);
-                }
-            }
-            if (r < kCholNB && (lane >= 16 || wave == 0)) {
-#pragma unroll
-                for (int c = 0; c < kCholPW; ++c) a[r][jb + c] = p0[c];
-            }
-            if (tid == 0 && bad) s_bad = bad;
-        }
-        __syncthreads();
-        if (s_bad) break;
-    }
-    if (s_bad) {
-        if (tid == 0) atomicCAS(info, 0, (int)(k0 + s_bad));
-        return;
-    }
-    float *colw = A + li + (int64_t)lh * ld;
-    for (int j0 = 0; j0 < kCholNB; j0 += 32) {
-        float v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = a[li][j0 + 2 * u + lh];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int j = j0 + 2 * u + lh;
-            if (li < kb && j < kb && li >= j) colw[(int64_t)(j0 + 2 * u) * ld] = v[u];
-        }
-    }
-}
-
-// The blocked Cholesky's trailing updates (a2): C[r][c] -= sum_k P[r][k] Q[c][k]
-// over 128 x 128 tiles of C (all tiles of an m x nc block, or, lower != 0,
-// the tiles on and below the diagonal of an m x m block), f32 in and out,
-// column-major with leading dimension ld, K columns of P and Q.  The products
-// on the matrix cores (v_mfma_f32_16x16x4_f32: exact f32 products, bit for
-// bit a k-ordered fmaf chain) with C itself as the accumulator's start, so
-// every element sees fmaf(-P[r][k], Q[c][k], C) in k order, as in a
-// right-looking factorization.  rocBLAS ssyrk / sgemm ran these at 55-75 TF
-// (tools/r3_gemm_probe.cpp).  Workgroup: 4 waves as 2 x 2 of 64 x 64; the
-// MFMA's A side takes Q (the tile's columns) and its B side P (rows), so a
-// lane's result column is a row of C: the stores run down C's columns.
-// K in chunks of 32 staged through LDS as [k][row] (row stride 144 floats:
-// the 16 rows x 4 k of one fragment read hit 64 distinct banks), double
-// buffered, the next chunk's global loads in flight during the MFMAs.
-constexpr int kUpBM = 128, kUpBK = 32, kUpLd = kUpBM + 16;
-__global__ __launch_bounds__(256, 2) void chol_update_kernel(const float *__restrict__ P, const float *__restrict__ Q,
-                                                             int64_t ld, int m, int nc, int K, int lower,
-                                                             float *__restrict__ C) {
-    __shared__ float Ps[2][kUpBK][kUpLd], Qs[2][kUpBK][kUpLd];
-    int ti, tj;
-    if (lower) {
-        const int q = blockIdx.x;
-        ti = (int)((sqrtf(8.0f * (float)q + 1.0f) - 1.0f) * 0.5f);
-        while ((ti + 1) * (ti + 2) / 2 <= q) ++ti;
-        while (ti * (ti + 1) / 2 > q) --ti;
-        tj = q - ti * (ti + 1) / 2;
-    } else {
-        const int ntj = (nc + kUpBM - 1) / kUpBM;
-        ti = blockIdx.x / ntj;
-        tj = blockIdx.x % ntj;
-    }
-    const int r0 = ti * kUpBM, c0 = tj * kUpBM;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
-    // loader: row (tid & 127) of the chunk's k = (tid >> 7) + 2 u, u < 16, for P and Q
-    const int lrow = tid & (kUpBM - 1), lk = tid >> 7;
-    const bool prow = r0 + lrow < m, qrow = c0 + lrow < nc;
-    const float *pp = P + (prow ? r0 + lrow : 0), *qp = Q + (qrow ? c0 + lrow : 0);
-    float vp[16], vq[16];
-    auto gload = [&](int k0) {
-        // (K is a multiple of kUpBK: every k in range; rows past m / nc read
-        // row 0 and are zeroed)
-        const float *p0 = pp + (int64_t)(k0 + lk) * ld, *q0 = qp + (int64_t)(k0 + lk) * ld;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const float a = p0[(int64_t)(2 * u) * ld], c = q0[(int64_t)(2 * u) * ld];
-            vp[u] = prow ? a : 0.0f;
-            vq[u] = qrow ? c : 0.0f;
-        }
-    };
-    auto lstore = [&](int b) {
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            Ps[b][lk + 2 * u][lrow] = vp[u];
-            Qs[b][lk + 2 * u][lrow] = vq[u];
-        }
-    };
-    // accumulators from C: acc[cb][rb] holds C[r0 + 64 wr + 16 rb + (lane & 15)][c0 + 64 wc + 16 cb + 4 (lane >> 4) + v]
-    const int fr = lane & 15, fg = lane >> 4;
-    // a tile inside the block (uniform) needs no per-element tests
-    const bool interior = r0 + kUpBM <= m && c0 + kUpBM <= nc;
-    float *cw = C + (int64_t)(r0 + 64 * wr + fr) + (int64_t)(c0 + 64 * wc + 4 * fg) * ld;
-    f32x4_t acc[4][4];
-    if (interior) {
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-            for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) acc[cb][rb][v] = cw[16 * rb + (int64_t)(16 * cb + v) * ld];
-    } else {
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-            for (int rb = 0; rb < 4; ++rb) {
-                const int r = r0 + 64 * wr + 16 * rb + fr;
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int c = c0 + 64 * wc + 16 * cb + 4 * fg + v;
-                    acc[cb][rb][v] = (r < m && c < nc) ? cw[16 * rb + (int64_t)(16 * cb + v) * ld] : 0.0f;
-                }
-            }
-    }
-    gload(0);
-    lstore(0);
-    __syncthreads();
-    const int nchunk = K / kUpBK;
-    for (int ch = 0; ch < nchunk; ++ch) {
-        const int b = ch & 1;
-        if (ch + 1 < nchunk) gload((ch + 1) * kUpBK);
-#pragma unroll
-        for (int kk = 0; kk < kUpBK / 4; ++kk) {
-            const int k = 4 * kk + fg;
-            float qa[4], pb[4];
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) qa[cb] = Qs[b][k][64 * wc + 16 * cb + fr];
-#pragma unroll
-            for (int rb = 0; rb < 4; ++rb) pb[rb] = -Ps[b][k][64 * wr + 16 * rb + fr];
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-                for (int rb = 0; rb < 4; ++rb)
-                    acc[cb][rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[cb], pb[rb], acc[cb][rb], 0, 0, 0);
-        }
-        if (ch + 1 < nchunk) lstore(b ^ 1);
-        __syncthreads();
-    }
-    if (interior) {
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-            for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) cw[16 * rb + (int64_t)(16 * cb + v) * ld] = acc[cb][rb][v];
-    } else {
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-            for (int rb = 0; rb < 4; ++rb) {
-                const int r = r0 + 64 * wr + 16 * rb + fr;
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int c = c0 + 64 * wc + 16 * cb + 4 * fg + v;
-                    if (r < m && c < nc) cw[16 * rb + (int64_t)(16 * cb + v) * ld] = acc[cb][rb][v];
-                }
-            }
-    }
-}
-
-// The blocked Cholesky's panel (a2): A21 := A21 L11^-T for the m2 x kb panel
-// below a factored kb x kb diagonal block (rocBLAS strsm right / lower /
-// transpose ran as ~10 launches, ~100 us per step, on the factorization's
-// critical path).  Forward substitution row by row, x L11^T = a: 128 panel
-// rows per workgroup, two threads per row (t and t + 128, one wave per SIMD);
-// L11 row-major in LDS (stride 132: a row's 16-column blocks are aligned
-// float4 reads, every lane reading the same address -- broadcast), the rows
-// being solved in LDS column-major (lane-linear, conflict-free).
-// Right-looking in 16-column blocks: both threads of a row solve the block's
-// 16 values in registers, x_j = (a_j - sum_{u<j} x_u L_ju) * (1 / L_jj)
-// (ascending u; the block of L read into registers first so that the chain
-// waits on no LDS read), then each takes every other later column and
-// subtracts the block's 16 terms.  Each x_j sees its terms in ascending
-// column order, as in the plain forward substitution; the reciprocal of the
-// pivot is the one extra rounding strsm's inverted diagonal has too.  kb <
-// 128 (the last step) pads L11 with the identity.
-constexpr int kTrsmLd = 132;
-__global__ __launch_bounds__(256) void chol_trsm_kernel(const float *__restrict__ L11, int64_t ld, int kb,
-                                                        float *__restrict__ A21, int64_t m2) {
-    __shared__ __attribute__((aligned(16))) float Ls[kCholNB * kTrsmLd];
-    __shared__ float X[kCholNB * kCholNB];
-    SBO_CSTAMP(8);
-    const int tid = threadIdx.x, t = tid & (kCholNB - 1), h = tid >> 7;
-    const int64_t row = (int64_t)blockIdx.x * kCholNB + t;
-    const bool in = row < m2;
-    // columns of L11 and of the panel rows (coalesced over t), 16 columns of
-    // loads in flight at a time, half the columns per thread of the pair;
-    // identity padding past kb
-    // (one predicate per thread for the loads, so all 16 of a batch are in
-    // flight together; the upper triangle and the padding are fixed up after)
-    const bool lin = t < kb;
-    for (int j0 = 8 * h; j0 < kCholNB; j0 += 16) {
-        float lv[8], xv[8];
-        if (j0 + 8 <= kb) {
-            if (lin) {
-#pragma unroll
-                for (int u = 0; u < 8; ++u) lv[u] = L11[t + (int64_t)(j0 + u) * ld];
-            }
-            if (in) {
-#pragma unroll
-                for (int u = 0; u < 8; ++u) xv[u] = A21[row + (int64_t)(j0 + u) * ld];
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                lv[u] = (lin && j0 + u < kb) ? L11[t + (int64_t)(j0 + u) * ld] : 0.0f;
-                xv[u] = (in && j0 + u < kb) ? A21[row + (int64_t)(j0 + u) * ld] : 0.0f;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int j = j0 + u;
-            Ls[t * kTrsmLd + j] = (j < kb && lin && t >= j) ? lv[u] : (t == j && j >= kb ? 1.0f : 0.0f);
-            X[j * kCholNB + t] = (in && j < kb) ? xv[u] : 0.0f;
-        }
-    }
-    __syncthreads();
-    SBO_CSTAMP(9);
-    for (int B = 0; B < kCholNB / 16; ++B) {
-        const int j0 = 16 * B;
-        // the 16 x 16 diagonal block of L (lower: row q needs q + 1 values)
-        float4 lb[16][4];
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-#pragma unroll
-            for (int v = 0; v < 4; ++v)
-                if (4 * v <= q) lb[q][v] = reinterpret_cast<const float4 *>(Ls + (j0 + q) * kTrsmLd + j0)[v];
-        float xb[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) xb[u] = X[(j0 + u) * kCholNB + t];
-        float rinv[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const float4 d = lb[q][q >> 2];
-            rinv[q] = __fdiv_rn(1.0f, (q & 3) == 0 ? d.x : (q & 3) == 1 ? d.y : (q & 3) == 2 ? d.z : d.w);
-        }
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            float s = xb[q];
-#pragma unroll
-            for (int u = 0; u < q; ++u) {
-                const float4 l4 = lb[q][u >> 2];
-                const float l = (u & 3) == 0 ? l4.x : (u & 3) == 1 ? l4.y : (u & 3) == 2 ? l4.z : l4.w;
-                s = fmaf(-xb[u], l, s);
-            }
-            xb[q] = s * rinv[q];
-        }
-        __syncthreads();   // every read of this block's columns is done
-        if (h == 0) {
-#pragma unroll
-            for (int u = 0; u < 16; ++u) X[(j0 + u) * kCholNB + t] = xb[u];
-        }
-        // later columns of this thread (every other one), four at a time:
-        // four independent FMA chains in flight instead of one
-        for (int c0 = j0 + 16 + h; c0 < kCholNB; c0 += 8) {
-            float v[4];
-            float lv[4][16];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int c = min(c0 + 2 * k, kCholNB - 1);
-                const float4 *lr = reinterpret_cast<const float4 *>(Ls + c * kTrsmLd + j0);
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) {
-                    const float4 l4 = lr[q4];
-                    lv[k][4 * q4] = l4.x;
-                    lv[k][4 * q4 + 1] = l4.y;
-                    lv[k][4 * q4 + 2] = l4.z;
-                    lv[k][4 * q4 + 3] = l4.w;
-                }
-                v[k] = X[c * kCholNB + t];
-            }
-#pragma unroll
-            for (int u = 0; u < 16; ++u)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) v[k] = fmaf(-xb[u], lv[k][u], v[k]);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (c0 + 2 * k < kCholNB) X[(c0 + 2 * k) * kCholNB + t] = v[k];
-        }
-        __syncthreads();
-    }
-    SBO_CSTAMP(10);
-    if (in)
-        for (int j = h; j < kb; j += 2) A21[row + (int64_t)j * ld] = X[j * kCholNB + t];
-    SBO_CSTAMP(11);
-}
-
-// The same panel solve with the later columns' updates on the matrix cores
-// (chol_trsm_kernel's default replacement).  Per 16-column block: the rows
-// solve the block in registers, right-looking -- after x_q, every later s_q'
-// of the block takes fmaf(-x_q, L[q'][q], s_q'), so each s still sees its
-// terms in ascending column order, as in the forward substitution -- with the
-// pivots' reciprocals computed once per workgroup; then the block's rank-16
-// update of the later columns, X[c][t] -= sum_u L[c][u] x_u(t), as
-// v_mfma_f32_16x16x4_f32 (a k-ordered fmaf chain from X itself: the same
-// terms in the same order as chol_trsm_kernel's VALU loop, so the panel is
-// bitwise the same).  The MFMA's A side takes L (result rows = columns c of
-// X), its B side the solved x (result columns = panel rows t, contiguous in
-// X's [c][t] layout, row stride 132: conflict-free result reads and writes).
-// The block of L11 and the 128 panel rows in: two batches of 64 loads per
-// thread in flight.
-constexpr int kTrX = kCholNB + 4;
-__global__ __launch_bounds__(256) void chol_trsm_mfma_kernel(const float *__restrict__ L11, int64_t ld, int kb,
-                                                             float *__restrict__ A21, int64_t m2) {
-    __shared__ __attribute__((aligned(16))) float Ls[kCholNB * kTrsmLd];
-    __shared__ float X[kCholNB * kTrX];
-    __shared__ float rinv[kCholNB];
-    SBO_CSTAMP(8);
-    const int tid = threadIdx.x, t = tid & (kCholNB - 1), h = tid >> 7;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int64_t row = (int64_t)blockIdx.x * kCholNB + t;
-    const bool in = row < m2, lin = t < kb;
-    // loads: thread (t, h) takes columns h, h + 2, ... of L11's row t and of panel row t
-    // (every load unconditional, clamped into the block; padding replaced below)
-    const float *lp = L11 + min(t, kb - 1);
-    const float *xp = A21 + (in ? row : 0);
-    for (int jb = 0; jb < kCholNB; jb += 64) {
-        float lv[32], xv[32];
-#pragma unroll
-        for (int u = 0; u < 32; ++u) {
-            const int64_t off = (int64_t)min(jb + 2 * u + h, kb - 1) * ld;
-            lv[u] = lp[off];
-            xv[u] = xp[off];
-        }
-#pragma unroll
-        for (int u = 0; u < 32; ++u) {
-            const int j = jb + 2 * u + h;
-            Ls[t * kTrsmLd + j] = (j < kb && lin && t >= j) ? lv[u] : (t == j && j >= kb ? 1.0f : 0.0f);
-            X[j * kTrX + t] = (in && j < kb) ? xv[u] : 0.0f;
-        }
-    }
-    __syncthreads();
-    if (tid < kCholNB) rinv[tid] = __fdiv_rn(1.0f, Ls[tid * kTrsmLd + tid]);
-    __syncthreads();
-    SBO_CSTAMP(9);
-    const int fr = lane & 15, fg = lane >> 4;
-    for (int B = 0; B < kCholNB / 16; ++B) {
-        const int j0 = 16 * B;
-        if (h == 0) {
-            // the block's 16 x 16 lower triangle of L (broadcast reads)
-            float4 lb[16][4];
-#pragma unroll
-            for (int q = 0; q < 16; ++q)
-#pragma unroll
-                for (int v = 0; v < 4; ++v)
-                    if (4 * v <= q) lb[q][v] = reinterpret_cast<const float4 *>(Ls + (j0 + q) * kTrsmLd + j0)[v];
-            float sb[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) sb[q] = X[(j0 + q) * kTrX + t];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                sb[q] = sb[q] * rinv[j0 + q];
-#pragma unroll
-                for (int q2 = q + 1; q2 < 16; ++q2) {
-                    const float4 l4 = lb[q2][q >> 2];
-                    const float l = (q & 3) == 0 ? l4.x : (q & 3) == 1 ? l4.y : (q & 3) == 2 ? l4.z : l4.w;
-                    sb[q2] = fmaf(-sb[q], l, sb[q2]);
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 16; ++q) X[(j0 + q) * kTrX + t] = sb[q];
-        }
-        __syncthreads();
-        // rank-16 update of the later columns: 16 x 16 result blocks (column
-        // block ci, row block ri), spread over the four waves
-        const int c1 = j0 + 16, nci = (kCholNB - c1) / 16, nblk = nci * (kCholNB / 16);
-        for (int qb = wave; qb < nblk; qb += 4) {
-            const int ci = qb / (kCholNB / 16), ri = qb % (kCholNB / 16);
-            const int cb0 = c1 + 16 * ci, rb0 = 16 * ri;
-            f32x4_t acc;
-#pragma unroll
-            for (int v = 0; v < 4; ++v) acc[v] = X[(cb0 + 4 * fg + v) * kTrX + rb0 + fr];
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const int u = 4 * kk + fg;
-                const float av = -Ls[(cb0 + fr) * kTrsmLd + j0 + u];
-                const float bv = X[(j0 + u) * kTrX + rb0 + fr];
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int v = 0; v < 4; ++v) X[(cb0 + 4 * fg + v) * kTrX + rb0 + fr] = acc[v];
-        }
-        __syncthreads();
-    }
-    SBO_CSTAMP(10);
-    if (in)
-        for (int j = h; j < kb; j += 2) A21[row + (int64_t)j * ld] = X[j * kTrX + t];
-    SBO_CSTAMP(11);
-}
-
-// The same panel solve, left-looking (round 5; SBO_OPT_CHOL_DIAG 1, the
-// default -- 2 keeps the right-looking chol_trsm_mfma_kernel): before the
-// rows solve 16-column block B, the four waves bring its columns up to date
-// with every solved column 0 .. 16B - 1 in one MFMA chain per 16 x 16 result
-// block, the accumulator in registers from X itself -- X[c][t] sees
-// fmaf(-L[c][u], x_u(t), .) for u ascending, the same terms in the same order
-// as the right-looking kernel's per-block updates (and the VALU kernel's
-// loop), so the panel is bitwise the same; the right-looking kernel read and
-// wrote every later block's accumulators through LDS after every block (56
-// 16 x 16 updates per wave, each a four-MFMA chain) where this issues 8B
-// MFMAs per wave as two interleaved chains.  Wave w owns row blocks 2w and
-// 2w + 1 (rows 32w .. 32w + 31).
-__global__ __launch_bounds__(256) void chol_trsm_ll_kernel(const float *__restrict__ L11, int64_t ld, int kb,
-                                                           float *__restrict__ A21, int64_t m2) {
-    __shared__ __attribute__((aligned(16))) float Ls[kCholNB * kTrsmLd];
-    __shared__ float X[kCholNB * kTrX];
-    __shared__ float rinv[kCholNB];
-    const int tid = threadIdx.x, t = tid & (kCholNB - 1), h = tid >> 7;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int64_t row = (int64_t)blockIdx.x * kCholNB + t;
-    const bool in = row < m2, lin = t < kb;
-    const float *lp = L11 + min(t, kb - 1);
-    const float *xp = A21 + (in ? row : 0);
-    for (int jb = 0; jb < kCholNB; jb += 64) {
-        float lv[32], xv[32];
-#pragma unroll
-        for (int u = 0; u < 32; ++u) {
-            const int64_t off = (int64_t)min(jb + 2 * u + h, kb - 1) * ld;
-            lv[u] = lp[off];
-            xv[u] = xp[off];
-        }
-#pragma unroll
-        for (int u = 0; u < 32; ++u) {
-            const int j = jb + 2 * u + h;
-            Ls[t * kTrsmLd + j] = (j < kb && lin && t >= j) ? lv[u] : (t == j && j >= kb ? 1.0f : 0.0f);
-            X[j * kTrX + t] = (in && j < kb) ? xv[u] : 0.0f;
-        }
-    }
-    __syncthreads();
-    if (tid < kCholNB) rinv[tid] = __fdiv_rn(1.0f, Ls[tid * kTrsmLd + tid]);
-    __syncthreads();
-    const int fr = lane & 15, fg = lane >> 4;
-    const int rb0 = 32 * wave, rb1 = rb0 + 16;
-    for (int B = 0; B < kCholNB / 16; ++B) {
-        const int j0 = 16 * B;
-        if (B > 0) {
-            f32x4_t acc0, acc1;
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                acc0[v] = X[(j0 + 4 * fg + v) * kTrX + rb0 + fr];
-                acc1[v] = X[(j0 + 4 * fg + v) * kTrX + rb1 + fr];
-            }
-            for (int k16 = 0; k16 < B; ++k16) {   // (16 columns at a time: operand reads batched)
-                float av[4], b0[4], b1[4];
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    const int u = 16 * k16 + 4 * kk + fg;
-                    av[kk] = -Ls[(j0 + fr) * kTrsmLd + u];
-                    b0[kk] = X[u * kTrX + rb0 + fr];
-                    b1[kk] = X[u * kTrX + rb1 + fr];
-                }
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kk], b0[kk], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kk], b1[kk], acc1, 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                X[(j0 + 4 * fg + v) * kTrX + rb0 + fr] = acc0[v];
-                X[(j0 + 4 * fg + v) * kTrX + rb1 + fr] = acc1[v];
-            }
-            __syncthreads();
-        }
-        if (h == 0) {
-            float4 lb[16][4];
-#pragma unroll
-            for (int q = 0; q < 16; ++q)
-#pragma unroll
-                for (int v = 0; v < 4; ++v)
-                    if (4 * v <= q) lb[q][v] = reinterpret_cast<const float4 *>(Ls + (j0 + q) * kTrsmLd + j0)[v];
-            float sb[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) sb[q] = X[(j0 + q) * kTrX + t];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                sb[q] = sb[q] * rinv[j0 + q];
-#pragma unroll
-                for (int q2 = q + 1; q2 < 16; ++q2) {
-                    const float4 l4 = lb[q2][q >> 2];
-                    const float l = (q & 3) == 0 ? l4.x : (q & 3) == 1 ? l4.y : (q & 3) == 2 ? l4.z : l4.w;
-                    sb[q2] = fmaf(-sb[q], l, sb[q2]);
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 16; ++q) X[(j0 + q) * kTrX + t] = sb[q];
-        }
-        __syncthreads();
-    }
-    if (in)
-        for (int j = h; j < kb; j += 2) A21[row + (int64_t)j * ld] = X[j * kTrX + t];
-}
-
-// Row 1-norms of the packed operand: block I, thread r sums |A[I*BM + r][:]|.
 // Row 1-norms of the packed operand, |A[I*BM + r][:]|_1: block (c, I)
 // sums row r over k-tiles [c*kRowL1Tiles, (c+1)*kRowL1Tiles) of row block I
 // and adds into row_l1 (zeroed by the launcher).
@@ -1218,9 +330,9 @@ constexpr int kTnGmLd = kBK + 4;
 // contraction runs over that storage order (any order of the rows serves).
 constexpr int kTnPq = kBK + 8;                 // bf16 per staged k row: 144 B, conflict-free b128 reads
 constexpr double kTnDelta = 1.0 / 65536.0;     // 2^-16
-typedef float f32x4_t2 __attribute__((ext_vector_type(4)));
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ f32x4_t2 mfma_bf16(uint4 a, uint4 b, f32x4_t2 c) {
+__device__ __forceinline__ f32x4_t mfma_bf16(uint4 a, uint4 b, f32x4_t c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b),
                                                    c, 0, 0, 0);
 }
@@ -1230,8 +342,8 @@ __device__ __forceinline__ f32x4_t2 mfma_bf16(uint4 a, uint4 b, f32x4_t2 c) {
 // a01 + 2^(s0 - s2) a02 + 2^(2 (s0 - s1)) a1 in f64 (exact scalings); the
 // entries above the diagonal of a diagonal block are left 0 (the stores
 // mirror the lower ones)
-__device__ __forceinline__ void gram_values(double (&x)[4], int bi, int bj, int lane, int pi, f32x4_t2 a00,
-                                            f32x4_t2 a01, f32x4_t2 a02, f32x4_t2 a1, f32x4_t2 a2,
+__device__ __forceinline__ void gram_values(double (&x)[4], int bi, int bj, int lane, int pi, f32x4_t a00,
+                                            f32x4_t a01, f32x4_t a02, f32x4_t a1, f32x4_t a2,
                                             const int (&sp)[3]) {
     const double c01 = ldexp(1.0, sp[0] - sp[1]), c02 = ldexp(1.0, sp[0] - sp[2]), c11 = c01 * c01;
 #pragma unroll
@@ -1286,9 +398,9 @@ __global__ __launch_bounds__(kBM, 2) void tile_norm_kernel(const float *__restri
     const int tbj[3] = {wave < 3 ? 0 : 2, wave == 0 ? 0 : (wave == 1 ? 1 : (wave == 2 ? 1 : 3)), wave == 0 ? 1 : 2};
     // the Gram accumulators: A (its five cross terms), A1, A2
     // G_A's terms A0^T A0, A1^T A0 + A0^T A1, A2^T A0 + A0^T A2 (scaled 2^(s0 + s_p)), then G1, G2
-    f32x4_t2 acc00[3], acc01[3], acc02[3], acc1[3], acc2[3];
+    f32x4_t acc00[3], acc01[3], acc02[3], acc1[3], acc2[3];
 #pragma unroll
-    for (int b = 0; b < 3; ++b) acc00[b] = acc01[b] = acc02[b] = acc1[b] = acc2[b] = f32x4_t2{0.f, 0.f, 0.f, 0.f};
+    for (int b = 0; b < 3; ++b) acc00[b] = acc01[b] = acc02[b] = acc1[b] = acc2[b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     double rmax[3] = {0.0, 0.0, 0.0}, fro[3] = {0.0, 0.0, 0.0};
     const int sk = tid >> 2, sc = 16 * (tid & 3);   // staging: k row sk, storage columns sc .. sc + 15
     const int rc = tid & 63, rk = tid >> 6;         // row sums: column rc, k in [16 rk, 16 rk + 16)
@@ -1550,9 +662,9 @@ __global__ __launch_bounds__(kBM, 2) void tile_norm_kernel(const float *__restri
                 }
             }
             __syncthreads();
-            f32x4_t2 sq[3];
+            f32x4_t sq[3];
 #pragma unroll
-            for (int b = 0; b < 3; ++b) sq[b] = f32x4_t2{0.f, 0.f, 0.f, 0.f};
+            for (int b = 0; b < 3; ++b) sq[b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 const int co = 32 * ks + 8 * (lane >> 4);
@@ -3148,46 +2260,6 @@ hipError_t launch_row_l1(hipStream_t s, const float *aug, int64_t npad, int64_t 
     if (e != hipSuccess) return e;
     const int64_t chunks = (nI * kTilesPerRowBlockStep + kRowL1Tiles - 1) / kRowL1Tiles;
     hipLaunchKernelGGL(row_l1_kernel, dim3((unsigned)chunks, (unsigned)(nI - I0)), dim3(kBM), 0, s, aug, I0, row_l1);
-    return hipGetLastError();
-}
-
-hipError_t launch_chol_diag(hipStream_t s, float *A, int64_t ld, int kb, int64_t k0, int *info, int version) {
-    if (kb <= 0 || kb > kCholNB) return hipErrorInvalidValue;
-    if (version == 1)
-        hipLaunchKernelGGL(chol_diag_ll_kernel, dim3(1), dim3(256), 0, s, A, ld, kb, k0, info);
-    else if (version == 2)
-        hipLaunchKernelGGL(chol_diag_mfma_kernel, dim3(1), dim3(256), 0, s, A, ld, kb, k0, info);
-    else
-        hipLaunchKernelGGL(chol_diag_kernel, dim3(1), dim3(256), 0, s, A, ld, kb, k0, info);
-    return hipGetLastError();
-}
-
-hipError_t launch_chol_update(hipStream_t s, const float *P, const float *Q, int64_t ld, int64_t m, int64_t nc,
-                              int64_t K, bool lower, float *C) {
-    if (m < 0 || nc < 0 || K < 0 || m > INT32_MAX / 2 || nc > INT32_MAX / 2 || K > INT32_MAX / 2 || (lower && nc != m) ||
-        K % kUpBK != 0)
-        return hipErrorInvalidValue;
-    if (m == 0 || nc == 0 || K == 0) return hipSuccess;
-    const int64_t nti = (m + kUpBM - 1) / kUpBM, ntj = (nc + kUpBM - 1) / kUpBM;
-    const int64_t tiles = lower ? nti * (nti + 1) / 2 : nti * ntj;
-    if (tiles > INT32_MAX) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(chol_update_kernel, dim3((unsigned)tiles), dim3(256), 0, s, P, Q, ld, (int)m, (int)nc, (int)K,
-                       lower ? 1 : 0, C);
-    return hipGetLastError();
-}
-
-hipError_t launch_chol_trsm(hipStream_t s, const float *L11, int64_t ld, int kb, float *A21, int64_t m2, int version) {
-    if (kb <= 0 || kb > kCholNB || m2 < 0) return hipErrorInvalidValue;
-    if (m2 == 0) return hipSuccess;
-    if (version == 1)
-        hipLaunchKernelGGL(chol_trsm_ll_kernel, dim3((unsigned)((m2 + kCholNB - 1) / kCholNB)), dim3(2 * kCholNB), 0,
-                           s, L11, ld, kb, A21, m2);
-    else if (version == 2)
-        hipLaunchKernelGGL(chol_trsm_mfma_kernel, dim3((unsigned)((m2 + kCholNB - 1) / kCholNB)), dim3(2 * kCholNB), 0,
-                           s, L11, ld, kb, A21, m2);
-    else
-        hipLaunchKernelGGL(chol_trsm_kernel, dim3((unsigned)((m2 + kCholNB - 1) / kCholNB)), dim3(2 * kCholNB), 0, s,
-                           L11, ld, kb, A21, m2);
     return hipGetLastError();
 }
 

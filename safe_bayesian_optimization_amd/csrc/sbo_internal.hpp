@@ -264,11 +264,11 @@ hipError_t launch_tile_norms(hipStream_t s, const float *aug, int64_t npad, int6
 // the f64 operand's pack (launch_pack_tiles) and the tile norms in one pass
 hipError_t launch_pack_tile_norms(hipStream_t s, const double *Linv, int64_t ld, int64_t n, int64_t npad, int64_t I0,
                                   double sf2, float *aug, float4 *lgn);
-// Blocked Cholesky: factor the kb x kb diagonal block at A (column-major,
-// lda = ld) of step k0 in place (kb <= kCholNB); info as rocSOLVER's.
+// Blocked Cholesky, the chain (csrc/chol_chain.hip): factor the kb x kb
+// diagonal block at A (column-major, lda = ld) of step k0 in place (kb <=
+// kCholNB); info as rocSOLVER's.
 constexpr int kCholNB = 128;
-// version (SBO_OPT_CHOL_DIAG) 1: chol_diag_ll_kernel (left-looking, one MFMA chain per block; default),
-// 2: chol_diag_mfma_kernel (right-looking, 16-column panels), 0: chol_diag_kernel (VALU); bitwise equal
+// version (SBO_OPT_CHOL_DIAG) 1: left-looking MFMA (default), 2: right-looking MFMA, 0: VALU; bitwise equal
 hipError_t launch_chol_diag(hipStream_t s, float *A, int64_t ld, int kb, int64_t k0, int *info, int version = 1);
 // C -= P Q^T over 128 x 128 tiles (lower: the tiles on and below the diagonal of an m x m C), f32, lda ld, K columns
 hipError_t launch_chol_update(hipStream_t s, const float *P, const float *Q, int64_t ld, int64_t m, int64_t nc,
@@ -282,9 +282,8 @@ size_t chol_x3_bytes(int64_t m, int64_t K);
 hipError_t launch_chol_split(hipStream_t s, const float *P, int64_t ld, int64_t m, int64_t K, char *planes);
 hipError_t launch_chol_update_x3(hipStream_t s, const char *planes, int64_t m, int64_t K, int64_t r0, int64_t rows,
                                  int64_t c0, int64_t cols, bool lower, float *C, int64_t ld);
-// The panel below it: A21 (m2 x kb, lda ld) := A21 L11^-T (forward substitution, f32).
-// version 1: chol_trsm_ll_kernel (left-looking MFMA; default), 2: chol_trsm_mfma_kernel (right-looking),
-// 0: chol_trsm_kernel (VALU); bitwise equal
+// The panel below it (csrc/chol_chain.hip): A21 (m2 x kb, lda ld) := A21 L11^-T (forward substitution, f32);
+// version as launch_chol_diag's
 hipError_t launch_chol_trsm(hipStream_t s, const float *L11, int64_t ld, int kb, float *A21, int64_t m2, int version = 1);
 // d = (double)in - v;  out = (float)d
 hipError_t launch_widen_sub(hipStream_t s, const float *in, double v, int64_t n, double *d);

@@ -31,7 +31,7 @@ The pieces.  A's are the round-to-nearest-even split of the f32 operand
 split test_tile_gain_bounds_are_bounds uses.  K*'s are the same split3 of the
 f32 value the sweep forms in registers (kstar1, :119-122): dx = xk - xq,
 dy = yk - yq in f32, s = fmaf(dy, dy, dx * dx), e = exp2(s * cexp) with
-cexp = (float)(-1 / (2 (float)l^2 ln 2)) (exp2_coef, kernels.hip:3328); then
+cexp = (float)(-1 / (2 (float)l^2 ln 2)) (exp2_coef, kernels.hip:2400); then
 split3(e) (:201-202, :271).  The device evaluates exp2 with v_exp_f32 (one ulp,
 results below 2^-126 flushed to zero); here it is the correctly rounded f32 of
 the f64 exp2, flushed the same way.  That difference enters reference and plan

@@ -164,14 +164,17 @@ def test_blocked_cholesky_matches_spotrf(mapper, n):
         assert nrel(res[ch][1][1].astype(np.float64) ** 2, res[0][1][1].astype(np.float64) ** 2) < REL_TOL
 
 
-@pytest.mark.parametrize("n", [77, 300, 4100])
+@pytest.mark.parametrize("n", [77, 128, 129, 257, 300, 4100])
 def test_chol_diag_kernels_bitwise(mapper, n):
-    """The diagonal-block kernels (SBO_OPT_CHOL_DIAG 1: 16-column panels with
-    matrix-core trailing updates and the left-looking panel solve, 2: the same
-    with the right-looking one, 0: 8-column VALU panels) give the same
-    factor bit for bit: every element sees fmaf(-L[i][j], L[l][j], a) with j
-    ascending either way (an f32 MFMA is a k-ordered fmaf chain).  n = 77 and
-    300 end in a partial block (the identity padding)."""
+    """The chain kernels (csrc/chol_chain.hip; SBO_OPT_CHOL_DIAG 1: 16-column
+    panels with left-looking matrix-core updates, 2: the same right-looking,
+    0: 8-column VALU panels) give the same factor bit for bit: every element
+    sees fmaf(-L[i][j], L[l][j], a) with j ascending either way (an f32 MFMA
+    is a k-ordered fmaf chain).  n = 77 and 300 end in a partial block (the
+    identity padding); 128 is one exactly full block with no panel below it;
+    129 ends in a block of kb = 1 (every clamped load reads index 0) below a
+    panel solve of one row; 257 has two panel-solve workgroups, the second
+    with one live row."""
     wl = synthetic(n, 16, 12, seed=n + 5)
     got = []
     for dv in (0, 1, 2):
@@ -185,20 +188,37 @@ def test_chol_diag_kernels_bitwise(mapper, n):
 
 def test_blocked_cholesky_not_spd_past_first_block(mapper):
     """A leading minor that fails beyond the first 128-column block is
-    reported as NOT_SPD by the blocked factorization too."""
-    wl = synthetic(300, 8, seed=4)
-    x, y = f32(wl.x), f32(wl.y)
-    x[200], y[200] = x[10], y[10]          # a duplicated point with no noise: K singular
-    msgs = []
-    for dv in (0, 1):   # both diagonal-block kernels report the same leading minor
-        gm = TerrainMapper(0, Hyper(noise_level=0.0), ctx=mapper.ctx)
-        gm.set_option(N.SBO_OPT_CHOLESKY, 1)
-        gm.set_option(N.SBO_OPT_CHOL_DIAG, dv)
-        with pytest.raises(N.NotSPDError) as ei:
-            gm.fit(x, y, wl.obs)
-        msgs.append(str(ei.value))
-    gm.set_option(N.SBO_OPT_CHOL_DIAG, 1)
-    assert msgs[0] == msgs[1] and "leading minor" in msgs[0], msgs
+    reported as NOT_SPD by the blocked factorization too, the same minor by
+    all three diagonal-block kernels.  The dense synthetic layout without
+    noise is singular to f32 long before its duplicated row (minor 39 in the
+    k-d storage order), so the two lattice cases place the pivot: points 20
+    length scales apart make K the identity in f32 (exp(-200) is 0), the copy
+    of point 10 at row `dup` makes pivot `dup` 1 - 1 * 1 = 0 exactly, and the
+    caller's storage order keeps it at column `dup`: row 200 fails in the
+    second block, row 290 in the last, partial one (kb = 44, beside the
+    identity padding of the shared block load)."""
+    n = 300
+    wl = synthetic(n, 8, seed=4)
+    i = np.arange(n)
+    cases = [(f32(wl.x), f32(wl.y), 200, 3, None)]
+    cases += [(f32(8.0 * (i % 20)), f32(8.0 * (i // 20)), dup, 0, dup + 1) for dup in (200, 290)]
+    try:
+        for x, y, dup, order, minor in cases:
+            x[dup], y[dup] = x[10], y[10]          # a duplicated point with no noise: K singular
+            msgs = []
+            for dv in (0, 1, 2):
+                gm = TerrainMapper(0, Hyper(noise_level=0.0), ctx=mapper.ctx)
+                gm.set_option(N.SBO_OPT_SPATIAL_ORDER, order)
+                gm.set_option(N.SBO_OPT_CHOLESKY, 1)
+                gm.set_option(N.SBO_OPT_CHOL_DIAG, dv)
+                with pytest.raises(N.NotSPDError) as ei:
+                    gm.fit(x, y, wl.obs)
+                msgs.append(str(ei.value))
+            assert msgs[0] == msgs[1] == msgs[2] and "leading minor" in msgs[0], msgs
+            assert minor is None or f"leading minor {minor} " in msgs[0], msgs
+    finally:
+        mapper.set_option(N.SBO_OPT_CHOL_DIAG, 1)
+        mapper.set_option(N.SBO_OPT_SPATIAL_ORDER, 3)
 
 
 @pytest.mark.parametrize("gemm", [2, 4])

@@ -1,9 +1,11 @@
 // Micro-benchmark of the blocked Cholesky's chain kernels in isolation
-// (chol_diag_kernel, chol_diag_mfma_kernel, chol_trsm_kernel) at C4's leading dimension, with
-// s_memtime phase stamps (-DSBO_CHOL_STAMPS).  GPU diagnostic:
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -DSBO_CHOL_STAMPS -I/opt/rocm/include \
+// (csrc/chol_chain.hip: the diagonal block and the panel solve, versions 0
+// VALU, 1 left-looking MFMA -- the default -- and 2 right-looking MFMA) at
+// C4's leading dimension, with s_memtime phase stamps (-DSBO_CHOL_STAMPS),
+// and the three versions' outputs compared bit for bit.  GPU diagnostic:
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -DSBO_CHOL_STAMPS -I/opt/rocm/include \
 //         tools/chol_micro.hip -o /tmp/chol_micro && /tmp/chol_micro
-#include "../safe_bayesian_optimization_amd/csrc/kernels.hip"
+#include "../safe_bayesian_optimization_amd/csrc/chol_chain.hip"
 
 #include <cstdio>
 #include <vector>
@@ -22,9 +24,9 @@ int main() {
     (void)hipEventCreate(&e0);
     (void)hipEventCreate(&e1);
     unsigned long long st[16];
-    std::vector<float> out[2], pan[2];
-    for (int rep = 0; rep < 6; ++rep) {
-        const int ver = rep % 2;   // 0: chol_diag_kernel, 1: chol_diag_mfma_kernel
+    std::vector<float> out[3], pan[3];
+    for (int rep = 0; rep < 9; ++rep) {
+        const int ver = rep % 3;   // SBO_OPT_CHOL_DIAG
         (void)hipMemcpy(dA, h.data(), sizeof(float) * (size_t)kb * ld, hipMemcpyHostToDevice);
         (void)hipMemset(info, 0, sizeof(int));
         (void)hipEventRecord(e0, 0);
@@ -55,13 +57,17 @@ int main() {
     }
     int hinfo = 0;
     (void)hipMemcpy(&hinfo, info, sizeof(int), hipMemcpyDeviceToHost);
-    size_t diff = 0;
-    for (int j = 0; j < kb; ++j)
-        for (int i = j; i < kb; ++i) diff += out[0][i + (size_t)j * kb] != out[1][i + (size_t)j * kb];
-    size_t pdiff = 0;
-    for (size_t i = 0; i < pan[0].size(); ++i) pdiff += pan[0][i] != pan[1][i];
-    printf("info %d; diagonal block factors v0 vs v1: %zu of %lld lower entries differ; panels: %zu of %zu differ "
-           "(s_memtime ticks = shader cycles)\n",
-           hinfo, diff, (long long)kb * (kb + 1) / 2, pdiff, pan[0].size());
-    return 0;
+    size_t bad = 0;
+    for (int ver = 1; ver < 3; ++ver) {
+        size_t diff = 0;
+        for (int j = 0; j < kb; ++j)
+            for (int i = j; i < kb; ++i) diff += out[0][i + (size_t)j * kb] != out[ver][i + (size_t)j * kb];
+        size_t pdiff = 0;
+        for (size_t i = 0; i < pan[0].size(); ++i) pdiff += pan[0][i] != pan[ver][i];
+        printf("v0 vs v%d: diagonal block factors: %zu of %lld lower entries differ; panels: %zu of %zu differ\n", ver,
+               diff, (long long)kb * (kb + 1) / 2, pdiff, pan[0].size());
+        bad += diff + pdiff;
+    }
+    printf("info %d (s_memtime ticks = shader cycles)\n", hinfo);
+    return bad != 0 || hinfo != 0;
 }
