@@ -106,6 +106,63 @@ SBO_API sbo_status sbo_fit(sbo_ctx *ctx, const float *x, const float *y, const f
 SBO_API sbo_status sbo_append(sbo_ctx *ctx, const float *x, const float *y, const float *obs,
                               int64_t b, uint32_t flags);
 
+/* The inverse of sbo_append: drop b training points without a refit.  Deleting
+ * a row of a Cholesky factor is a chain of Givens rotations, and the same
+ * rotations applied to the rows of the f64 inverse give the new inverse:
+ * O(n (n - i)) per point stored at position i, against n^3 / 3 for a refit
+ * (csrc/remove.hip; all arithmetic f64, the factor rounded to f32 once per
+ * call).  idx: a HOST array (also with SBO_DEVICE_PTRS) of b caller indices in
+ * sbo_get_order's numbering -- positions in the fit's input, appends numbered
+ * after the fit.  Afterwards the remaining points keep their relative order
+ * and are renumbered densely: new index = old index minus the number of
+ * removed indices below it (numpy.delete); sbo_get_order, sbo_evidence's LOO
+ * arrays and sbo_sample's eps counter use the new numbering, and a later
+ * sbo_append numbers its points from the new n.
+ *
+ * SBO_E_STATE before a fit or on an imported state; SBO_E_INVAL for a NULL idx
+ * with b > 0, b < 0, an index outside [0, n) or a duplicate; SBO_E_EMPTY for
+ * b == n (a model needs a point); b == 0 is SBO_OK and nothing happens.
+ * Rejected arguments leave the context exactly as it was; any error after
+ * validation (SBO_E_NOT_SPD of a pivot the chain meets that is not positive
+ * and finite included) leaves it unfitted, as a failed sbo_append does.
+ *
+ * sbo_get_bounds is unchanged by a removal.  A removal starts a new fit epoch:
+ * the next sbo_tick_stream runs the full sweep (reason REFIT), and sbo_whatif
+ * and sbo_sample return SBO_E_STATE until that tick.
+ *
+ * The rotations run unless (reason): there is no current f64 inverse and z
+ * (SBO_OPT_INVERSE_BITS 32: NO_INVERSE); b > SBO_OPT_REMOVE_MAX (OVER_CAP); or,
+ * with spatial order on, the points appended plus the points removed since the
+ * last k-d sort would exceed SBO_OPT_RESORT percent of the sorted points still
+ * stored (RESORT; sbo_append counts removals the same way).  Then the
+ * remaining points are staged again in k-d order and factored from scratch
+ * (path 0), the renumbered indices kept.  info may be NULL; the caller sets
+ * info->struct_size to sizeof(sbo_remove_info) and no more than that many
+ * bytes are written.  SBO_ASYNC as sbo_append (the refresh's own
+ * synchronisations stay). */
+typedef enum sbo_remove_reason { SBO_REMOVE_DOWNDATED = 0, SBO_REMOVE_NO_INVERSE = 1,
+                                 SBO_REMOVE_OVER_CAP = 2, SBO_REMOVE_RESORT = 3 } sbo_remove_reason;
+typedef struct sbo_remove_info {
+    uint32_t struct_size; int32_t path;      /* 1 rotations, 0 refit of the remaining points */
+    int32_t reason, reserved;
+    int64_t removed, n;                      /* n: points left */
+    int64_t first_row;                       /* smallest stored position removed (-1: b == 0) */
+    int64_t rotations;                       /* sum over removed points of the columns their chain crossed (0 on path 0) */
+    double ms;                               /* device time from the call's first kernel to its last */
+} sbo_remove_info;
+SBO_API sbo_status sbo_remove(sbo_ctx *ctx, const int64_t *idx, int64_t b, sbo_remove_info *info, uint32_t flags);
+/* Test accessor: the current f64 inverse L^-1 as a dense n x n ROW-major host
+ * array (cap >= n * n doubles), the upper triangle zeroed.  SBO_E_STATE without
+ * a current f64 inverse. */
+SBO_API sbo_status sbo_debug_inverse64(sbo_ctx *ctx, double *X, int64_t cap);
+/* Test accessor, host only, no context: sbo_remove's bookkeeping
+ * (csrc/remove_map.hpp).  order (n, as sbo_get_order) and idx (b) give pos,
+ * the b stored positions in ascending order, and new_order, the renumbered
+ * order of the n - b rows left (either may be NULL).  SBO_E_INVAL / SBO_E_EMPTY
+ * as sbo_remove. */
+SBO_API sbo_status sbo_debug_remove_map(const int64_t *order, int64_t n, const int64_t *idx, int64_t b, int64_t *pos,
+                                        int64_t *new_order);
+
 /* Number of training points currently fitted (0 before sbo_fit). */
 SBO_API int64_t sbo_num_train(const sbo_ctx *ctx);
 
@@ -525,7 +582,9 @@ SBO_API int sbo_project_subgoal(const double *rx, const double *ry, int64_t n, d
 /* Bounding box of the fitted training points (x0, x1, y0, y1), widened by
  * every sbo_append and carried through sbo_export_state / sbo_import_state:
  * the extent the service grid spans by default (mapper side of :583-586).
- * SBO_E_STATE before the first fit. */
+ * Unchanged by sbo_remove, on either of its paths: it remains a box that
+ * contains the points, and the probe lattice and the centre sbo_sample uses
+ * stay put.  SBO_E_STATE before the first fit. */
 SBO_API sbo_status sbo_get_bounds(const sbo_ctx *ctx, double *bounds);
 
 /* The diagonal jitter added by SBO_OPT_JITTER_RETRIES to the current fit
@@ -854,6 +913,17 @@ SBO_API sbo_status sbo_debug_inverse_plan(int64_t n, int64_t ld, int64_t base, i
  * half (1: twice the arithmetic, rocBLAS's general kernels; measured slower at
  * N = 16384 for p = 16 .. 256, 3.5-4.1 against 2.5-3.5 ms). */
 #define SBO_OPT_WHATIF_GEMM 33
+/* SBO_OPT_REMOVE_MAX (b in [0, 65536], default 2): an sbo_remove of more
+ * points than this refits the remaining ones instead of rotating them out one
+ * chain after another (reason OVER_CAP; 0: always).  The default is the
+ * largest power of two whose removal at uniformly random stored positions
+ * takes at most 0.8 of the warm refit of the points left (the refit also
+ * restores k-d-compact tiles): at N = 16384, b = 2 takes 13.9 ms against
+ * 32.2 ms (0.43), b = 4 35.3 ms against 30.5 ms (1.16).  One point at the
+ * first stored position, the worst case, takes 25.5 ms [25.4, 26.5] against
+ * 32.3 ms [32.1, 32.5]: it wins by more than the run's spread, so the
+ * rotations are not capped by their count (profiles/remove.log). */
+#define SBO_OPT_REMOVE_MAX 34
 SBO_API sbo_status sbo_set_option(sbo_ctx *ctx, int option, int64_t value);
 
 /* The last inverse check (SBO_OPT_INV_CHECK) of the current fit, on m = 31

@@ -39,7 +39,10 @@ EXPORTS = (
     "sbo_evidence", "sbo_debug_evidence_pairs", "sbo_debug_inverse_plan",
     "sbo_whatif", "sbo_debug_whatif_cutoff",
     "sbo_sample", "sbo_debug_sample_cutoff", "sbo_debug_sample_draws",
+    "sbo_remove", "sbo_debug_inverse64", "sbo_debug_remove_map",
 )
+# sbo_remove_reason (include/sbo.h, sbo_remove)
+REMOVE_REASONS = ("DOWNDATED", "NO_INVERSE", "OVER_CAP", "RESORT")
 # sbo_stream_reason (include/sbo.h, sbo_get_stream)
 STREAM_REASONS = ("FIRST", "UPDATED", "QUERIES_CHANGED", "REFIT", "NO_INVERSE", "ROWS_OVER_CAP", "BUDGET", "RESET")
 # the sliced GEMM's flags (include/sbo.h, sbo_debug_gz_gemm)
@@ -84,6 +87,7 @@ SBO_OPT_STREAM_SHARE = 30
 SBO_OPT_STREAM_MAX_ROWS = 31
 SBO_OPT_EVIDENCE_BUDGET = 32
 SBO_OPT_WHATIF_GEMM = 33
+SBO_OPT_REMOVE_MAX = 34
 
 
 class SboError(RuntimeError):
@@ -150,6 +154,12 @@ class sbo_sample_info(ctypes.Structure):
                 ("kernel_err", ctypes.c_double), ("w_l1_max", ctypes.c_double), ("ms", ctypes.c_double)]
 
 
+class sbo_remove_info(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("path", ctypes.c_int32), ("reason", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("removed", ctypes.c_int64), ("n", ctypes.c_int64),
+                ("first_row", ctypes.c_int64), ("rotations", ctypes.c_int64), ("ms", ctypes.c_double)]
+
+
 _lib = None
 
 
@@ -187,6 +197,12 @@ def lib():
     L.sbo_fit.restype = st
     L.sbo_append.argtypes = [vp, vp, vp, vp, i64, u32]
     L.sbo_append.restype = st
+    L.sbo_remove.argtypes = [vp, vp, i64, ctypes.POINTER(sbo_remove_info), u32]
+    L.sbo_remove.restype = st
+    L.sbo_debug_inverse64.argtypes = [vp, vp, i64]
+    L.sbo_debug_inverse64.restype = st
+    L.sbo_debug_remove_map.argtypes = [vp, i64, vp, i64, vp, vp]
+    L.sbo_debug_remove_map.restype = st
     L.sbo_num_train.argtypes = [vp]
     L.sbo_num_train.restype = i64
     L.sbo_predict.argtypes = [vp, vp, vp, i64, vp, vp, u32]

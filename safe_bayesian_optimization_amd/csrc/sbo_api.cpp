@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "inverse.hpp"
+#include "remove_map.hpp"
 #include "sbo_host.hpp"
 
 using sbo::DevBuf;
@@ -411,10 +412,10 @@ sbo_status run_tick(sbo_ctx *ctx, const TickRequest &rq, TickPlan *plan_out = nu
 sbo_status probe_precision(sbo_ctx *ctx, int precision);
 // the precision probe runs on this refresh (probe_precision): on a fresh fit,
 // and on appends once N has grown by SBO_OPT_REPROBE percent (default 25)
-// since the last probe
+// since the last probe -- or shrunk by as much (sbo_remove)
 bool probe_due(const sbo_ctx *ctx) {
-    return ctx->probe_n == 0 || ctx->n < ctx->probe_n ||
-           (ctx->n - ctx->probe_n) * 100 >= ctx->probe_n * (int64_t)ctx->opt.reprobe_pct;
+    return ctx->probe_n == 0 ||
+           std::llabs((long long)(ctx->n - ctx->probe_n)) * 100 >= ctx->probe_n * (int64_t)ctx->opt.reprobe_pct;
 }
 
 // Wait (host) for an accuracy guard still running on chk_stream: it reads L,
@@ -438,6 +439,7 @@ void unfit(sbo_ctx *ctx) {
     ctx->probe_n = 0;
     ctx->precise = false;
     ctx->n_sorted = 0;
+    ctx->removed_since_sort = 0;
     ctx->order.clear();
     ctx->chk_res = sbo_inv_check{};
     ctx->split.all_changed();
@@ -655,7 +657,8 @@ struct RefreshPlan {
     double sf2;
     bool f64;            // SBO_OPT_INVERSE_BITS 64 (else the f32 strtri path, refresh_f32)
     bool incr;           // an append with the leading block's f64 inverse kept: only rows n_old.. are new
-    int64_t n_old, I0;   // (I0: first row block holding new rows)
+    bool removed;        // sbo_remove's rotations: rows from first_row on changed, the f64 inverse is already current, n went down
+    int64_t n_old, I0;   // (I0: first row block holding new or changed rows)
     size_t old_tiles;    // packed tiles of the row blocks below I0, kept
     bool half_done;      // the inverse's first half ran beside the Cholesky (blocked_potrf) ...
     int half_slots;      // ... its info slots 1 .. half_slots stay, the rest are cleared
@@ -670,7 +673,8 @@ struct RefreshPlan {
     int x3_layout;
     bool fused_norms;    // the tile norms ran with the pack (SBO_FUSED_TN)
 };
-RefreshPlan plan_refresh(const sbo_ctx *ctx, int64_t n_old, const FactorHandover &ho, InvAttempt attempt) {
+RefreshPlan plan_refresh(const sbo_ctx *ctx, int64_t n_old, const FactorHandover &ho, InvAttempt attempt,
+                         int64_t removed_from = -1) {
     const sbo_options &o = ctx->opt;
     RefreshPlan p{};
     p.n = ctx->n;
@@ -680,21 +684,23 @@ RefreshPlan plan_refresh(const sbo_ctx *ctx, int64_t n_old, const FactorHandover
     p.sf2 = ctx->hyper.sigma_f * ctx->hyper.sigma_f;
     p.f64 = o.inverse_bits == 64;
     p.incr = n_old > 0 && inverse_current(ctx, n_old) && ctx->npad > 0;
+    p.removed = removed_from >= 0 && n_old == 0 && inverse_current(ctx, p.n) && ctx->npad > 0;
     p.n_old = p.incr ? n_old : 0;
-    p.I0 = p.n_old / sbo::kBM;
+    // (a removal that ends on a row block's edge still repacks the last block: no stage meets an empty range)
+    p.I0 = p.removed ? std::min(removed_from / sbo::kBM, p.nI - 1) : p.n_old / sbo::kBM;
     p.old_tiles = (size_t)sbo::total_tiles(p.I0);
-    p.half_done = p.f64 && o.inverse_rec && !p.incr && ho.half_n == p.n;
+    p.half_done = p.f64 && o.inverse_rec && !p.incr && !p.removed && ho.half_n == p.n;
     p.widened = ho.widened_n == p.n;
     const int want = attempt == kInvDgemm ? 0 : attempt == kInvFullDigits ? o.inv_oz : inv_digits(ctx);
     if (p.half_done)
         p.inv = ho.half;
-    else if (p.f64 && !p.incr && o.inverse_rec)
+    else if (p.f64 && !p.incr && !p.removed && o.inverse_rec)
         p.inv = sbo::plan_inverse(inv_config(ctx, want), p.n, p.ld);
     p.half_slots = p.half_done ? p.inv.half_slots() : 0;
     p.info_slots = sbo::inv_info(p.n).total;
     const bool sliced = p.inv.sliced();
     p.digits = sliced ? want : 0;
-    p.guard = p.f64 && !p.incr &&
+    p.guard = p.f64 && !p.incr && !p.removed &&
               (o.inv_check == 2 || attempt == kInvDgemm || (o.inv_check == 1 && sliced));
     p.inc_alpha = p.incr && ctx->z_n == n_old && p.n - n_old <= kAppendInvGemm;
     p.aux = p.f64 && aux_ready(ctx);
@@ -747,7 +753,7 @@ sbo_status refresh_inverse(sbo_ctx *ctx, const RefreshPlan &p) {
 
 // the inverse's accuracy guard, on its own stream beside what follows
 sbo_status refresh_guard_launch(sbo_ctx *ctx, const RefreshPlan &p) {
-    if (p.incr) return SBO_OK;
+    if (p.incr || p.removed) return SBO_OK;
     ctx->chk_res = sbo_inv_check{};
     if (!p.guard) return SBO_OK;
     ctx->chk_res.digits = p.digits;
@@ -936,7 +942,7 @@ sbo_status refresh_skip_budget(sbo_ctx *ctx, const RefreshPlan &p) {
     SBO_HIP(hipMemcpyAsync(ha.data(), ctx->alpha.as<float>(), sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
     SBO_HIP(hipStreamSynchronize(ctx->stream));
     double mx = *std::max_element(rl1.begin(), rl1.end());
-    if (p.incr) mx = std::max(mx, ctx->max_row_l1);
+    if (p.incr || p.removed) mx = std::max(mx, ctx->max_row_l1);   // (the rows below I0 are the ones it was taken over)
     ctx->max_row_l1 = mx;
     double al1 = 0.0;
     for (float v : ha) al1 += std::fabs((double)v);
@@ -993,20 +999,26 @@ sbo_status refresh_guard_verdict(sbo_ctx *ctx, InvAttempt attempt, bool &redo) {
 // (and a six-digit redo that misses tol goes on to dgemm products) -- and
 // reported as fired with the kept inverse's readings.
 // The caller's FitCommit waits for a guard still in flight when a stage fails.
-sbo_status refresh_operand(sbo_ctx *ctx, int64_t n_old = 0, FactorHandover ho = {}) {
+// removed_from >= 0: sbo_remove's rotations left L and the f64 inverse current
+// for the n points that remain; rows from removed_from on changed, so the
+// packs of the row blocks from removed_from / kBM on are redone for the new
+// npad (which may have lost a row block), alpha and z are solved in full and
+// the guard does not run, as on appends.
+sbo_status refresh_operand(sbo_ctx *ctx, int64_t n_old = 0, FactorHandover ho = {}, int64_t removed_from = -1) {
     sbo_inv_check first{};   // the reading that fired, and the rejected attempts' guard time
     bool fired = false;
     float ms_rejected = 0.0f;
     for (InvAttempt attempt = kInvChosen;;) {
         if (sbo_status st = ctx->pop.drain(ctx)) return st;
-        const RefreshPlan p = plan_refresh(ctx, n_old, ho, attempt);
+        const RefreshPlan p = plan_refresh(ctx, n_old, ho, attempt, removed_from);
         // what this refresh rewrites, for the derived operands: the row blocks from
         // I0 on (a full refresh: I0 = 0, everything); refresh_packs or the tick derives them
         ctx->split.rows_changed(p.I0);
         ctx->pop.rows_changed(p.I0);
         if (sbo_status st = refresh_begin(ctx, p)) return st;
         if (p.f64) {
-            if (sbo_status st = refresh_inverse(ctx, p)) return st;
+            if (!p.removed)
+                if (sbo_status st = refresh_inverse(ctx, p)) return st;
             if (sbo_status st = refresh_guard_launch(ctx, p)) return st;
             if (sbo_status st = refresh_alpha(ctx, p)) return st;
             if (sbo_status st = refresh_packs(ctx, p)) return st;
@@ -1039,6 +1051,7 @@ sbo_status refresh_operand(sbo_ctx *ctx, int64_t n_old = 0, FactorHandover ho = 
         }
         ctx->probe_n = 0;   // the probe above read the rejected inverse: measure the kept one
         n_old = 0;          // the redo is a full refresh, with nothing handed over
+        removed_from = -1;
         ho = FactorHandover{};
     }
     if (fired) {
@@ -2299,12 +2312,20 @@ sbo_status fill_and_factor(sbo_ctx *ctx, double base_noise) {
         if (st == SBO_OK) {
             ctx->jitter = jit;
             ctx->n_sorted = n;
+            ctx->removed_since_sort = 0;
             return SBO_OK;
         }
         ctx->hyper.noise_level = base_noise;
         if (st != SBO_E_NOT_SPD || r >= ctx->opt.jitter_retries) return st;
         drain_guard(ctx);   // (the retry rewrites L)
     }
+}
+
+// SBO_OPT_RESORT: the points appended since the last k-d sort (n - n_sorted)
+// and those removed since then exceed resort_pct % of the sorted ones
+bool resort_due(const sbo_ctx *ctx, int64_t n, int64_t n_sorted, int64_t removed) {
+    return ctx->opt.resort_pct > 0 && ctx->opt.spatial_order != 0 &&
+           (n - n_sorted + removed) * 100 > n_sorted * ctx->opt.resort_pct;
 }
 
 // sbo_append's re-sort (SBO_OPT_RESORT): all n0 + b points staged again in
@@ -2507,7 +2528,8 @@ SBO_API sbo_status sbo_append(sbo_ctx *ctx, const float *x, const float *y, cons
     FitCommit fc(ctx);
     // SBO_OPT_RESORT: once the points appended since the last k-d sort exceed
     // resort_pct % of the sorted ones, re-sort and refactor all of them
-    if (ctx->opt.resort_pct > 0 && ctx->opt.spatial_order != 0 && (n1 - ctx->n_sorted) * 100 > ctx->n_sorted * ctx->opt.resort_pct) {
+    // (points sbo_remove rotated out since then count as well: resort_due)
+    if (resort_due(ctx, n1, ctx->n_sorted, ctx->removed_since_sort)) {
         if (sbo_status st = resort_append(ctx, x, y, obs, b, flags)) return st;
         return fc.commit(finish(ctx, flags));
     }
@@ -2525,6 +2547,200 @@ SBO_API sbo_status sbo_append(sbo_ctx *ctx, const float *x, const float *y, cons
     ctx->n = n1;
     if (sbo_status st = refresh_operand(ctx, n0)) return st;
     return fc.commit(finish(ctx, flags));
+}
+
+namespace {
+// sbo_remove's rotation path, beside the append_* stages: per removed point
+// (ascending stored position, no compaction in between -- a later chain only
+// touches columns to the right of its own position, the dead rows and columns
+// of earlier ones are to its left or harmless to rotate) remove_chain over L
+// and remove_rows over the f64 inverse, then one remove_compact, then
+// refresh_operand.  One point rotates the f32 factor in place; a batch
+// rotates an f64 copy of its columns from the first removed one on, so that
+// the factor is rounded to f32 once per call.
+struct RemoveRun {
+    sbo::RemoveMap map;
+    int64_t n0 = 0, n1 = 0, first = 0;
+    sbo::RemoveWork wk;
+    double *W = nullptr;          // the batch's f64 columns of L (null: one point, in place)
+    std::vector<int> keep32;      // (lives until the stream has taken it)
+};
+
+// the workspaces, the kept positions on the device, the flag cleared, and the batch's f64 columns
+sbo_status remove_begin(sbo_ctx *ctx, RemoveRun &run) {
+    const int64_t n0 = run.n0, ld = ctx->cap, f = run.first;
+    SBO_HIP(ctx->ws.rmws.reserve(sbo::remove_work_bytes(n0)));
+    run.wk = sbo::remove_work(ctx->ws.rmws.as<void>(), n0);
+    run.keep32.assign(run.map.keep.begin(), run.map.keep.end());
+    SBO_HIP(hipMemsetAsync(run.wk.flag, 0, sizeof(int), ctx->stream));
+    SBO_HIP(hipMemcpyAsync(run.wk.keep, run.keep32.data(), sizeof(int) * run.keep32.size(), hipMemcpyHostToDevice,
+                           ctx->stream));
+    if (run.map.pos.size() > 1) {
+        SBO_HIP(ctx->ws.rmw64.reserve(sizeof(double) * (size_t)ld * (size_t)(n0 - f)));
+        run.W = ctx->ws.rmw64.as<double>();
+        SBO_HIP(sbo::launch_widen(ctx->stream, ctx->L.as<float>() + f + f * ld, ld, n0 - f, n0 - f, true, run.W + f, ld));
+    }
+    return SBO_OK;
+}
+sbo_status remove_chain(sbo_ctx *ctx, const RemoveRun &run, int64_t i) {
+    SBO_HIP(sbo::launch_remove_chain(ctx->stream, ctx->L.as<float>(), run.W, ctx->cap, run.first, run.n0, i, run.wk));
+    return SBO_OK;
+}
+sbo_status remove_rows(sbo_ctx *ctx, const RemoveRun &run, int64_t i) {
+    SBO_HIP(sbo::launch_remove_rows(ctx->stream, ctx->Linv.as<double>(), ctx->cap, run.n0, i, run.wk));
+    return SBO_OK;
+}
+// The rows and columns left move up (only positions >= the first removed one
+// move), and the chains' pivots are read: one that was not positive and finite
+// is NOT_SPD.
+sbo_status remove_compact(sbo_ctx *ctx, const RemoveRun &run) {
+    SBO_HIP(ctx->ws.rmmove.reserve(sbo::remove_compact_bytes(run.n1, run.first)));
+    SBO_HIP(sbo::launch_remove_compact(ctx->stream, ctx->L.as<float>(), run.W, run.first, ctx->Linv.as<double>(),
+                                       ctx->cap, ctx->x.as<float>(), ctx->y.as<float>(), ctx->obs.as<float>(), run.n1,
+                                       run.first, run.wk, ctx->ws.rmmove.as<void>()));
+    int flag = 0;
+    SBO_HIP(hipMemcpyAsync(&flag, run.wk.flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    SBO_HIP(hipStreamSynchronize(ctx->stream));
+    SBO_CHECK(flag == 0, SBO_E_NOT_SPD, "sbo_remove: a rotation met a pivot that is not positive and finite");
+    return SBO_OK;
+}
+
+// sbo_remove's refit of the remaining points: staged again in k-d order and
+// factored from scratch, the way resort_append does, the caller's (renumbered)
+// indices kept.  The bounding box stays the one of every point seen.
+sbo_status remove_refit(sbo_ctx *ctx, const RemoveRun &run) {
+    const int64_t n0 = run.n0, n1 = run.n1;
+    std::vector<float> h[3], p[3];
+    const float *src[3] = {ctx->x.as<float>(), ctx->y.as<float>(), ctx->obs.as<float>()};
+    for (int a = 0; a < 3; ++a) {
+        h[a].resize((size_t)n0);
+        SBO_HIP(hipMemcpyAsync(h[a].data(), src[a], sizeof(float) * n0, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    SBO_HIP(hipStreamSynchronize(ctx->stream));
+    for (int a = 0; a < 3; ++a) {
+        p[a].resize((size_t)n1);
+        for (int64_t r = 0; r < n1; ++r) p[a][(size_t)r] = h[a][(size_t)run.map.keep[(size_t)r]];
+    }
+    float bbox[4];
+    std::copy(ctx->bbox, ctx->bbox + 4, bbox);
+    ctx->n = n1;
+    ctx->linv_n = 0;
+    if (sbo_status st = stage_training(ctx, p[0].data(), p[1].data(), p[2].data(), n1, 0, 0, 0)) return st;
+    std::copy(bbox, bbox + 4, ctx->bbox);
+    for (int64_t r = 0; r < n1; ++r) ctx->order[(size_t)r] = run.map.new_order[(size_t)ctx->order[(size_t)r]];
+    return fill_and_factor(ctx, ctx->hyper.noise_level - ctx->jitter);
+}
+}  // namespace
+
+SBO_API sbo_status sbo_remove(sbo_ctx *ctx, const int64_t *idx, int64_t b, sbo_remove_info *info, uint32_t flags) {
+    if (!ctx) return SBO_E_INVAL;
+    SBO_CHECK(ctx->fitted, SBO_E_STATE, "sbo_remove: call sbo_fit first");
+    SBO_CHECK(ctx->has_factor, SBO_E_STATE, "sbo_remove: imported predict-only state has no factor; refit");
+    SBO_CHECK(b >= 0, SBO_E_INVAL, "sbo_remove: b must be >= 0");
+    SBO_CHECK(idx || b == 0, SBO_E_INVAL, "sbo_remove: null idx");
+    sbo_remove_info r{};
+    r.path = 1;
+    r.reason = SBO_REMOVE_DOWNDATED;
+    r.n = ctx->n;
+    r.first_row = -1;
+    if (b == 0) {
+        if (info) copy_info(info, r);
+        return SBO_OK;
+    }
+    RemoveRun run;
+    run.n0 = ctx->n;
+    const sbo::RemoveMapStatus ms = sbo::remove_map(ctx->order.data(), run.n0, idx, b, run.map);
+    SBO_CHECK(ms != sbo::RemoveMapStatus::kInval, SBO_E_INVAL, "sbo_remove: an index outside [0, n) or a duplicate");
+    SBO_CHECK(ms != sbo::RemoveMapStatus::kEmpty, SBO_E_EMPTY, "sbo_remove: a model needs at least one point");
+    run.n1 = run.n0 - b;
+    run.first = run.map.pos.front();
+    SBO_HIP(hipSetDevice(ctx->device));
+    if (sbo_status st = ctx->pop.drain(ctx)) return st;   // (a precise pack may still read x, y, L^-1, alpha64)
+    hipEvent_t ev0 = take_event(ctx), ev1 = take_event(ctx);
+    struct Back {   // the events go back to the pool on every path
+        sbo_ctx *c;
+        hipEvent_t a, b;
+        ~Back() {
+            if (a) c->ev_pool.push_back(a);
+            if (b) c->ev_pool.push_back(b);
+        }
+    } back{ctx, ev0, ev1};
+    SBO_CHECK(ev0 && ev1, SBO_E_DEVICE, "sbo_remove: hipEventCreate failed");
+    FitCommit fc(ctx);
+    drain_guard(ctx);
+    // rotations, or a refit of the remaining points
+    const int64_t sorted_left = ctx->n_sorted - run.map.below(ctx->n_sorted);
+    if (!fit_state_complete(ctx, run.n0)) {
+        r.path = 0;
+        r.reason = SBO_REMOVE_NO_INVERSE;
+    } else if (b > ctx->opt.remove_max) {
+        r.path = 0;
+        r.reason = SBO_REMOVE_OVER_CAP;
+    } else if (resort_due(ctx, run.n1, sorted_left, ctx->removed_since_sort + b)) {
+        r.path = 0;
+        r.reason = SBO_REMOVE_RESORT;
+    }
+    r.removed = b;
+    r.n = run.n1;
+    r.first_row = run.first;
+    r.rotations = r.path ? run.map.rotations : 0;
+    SBO_HIP(hipEventRecord(ev0, ctx->stream));
+    if (r.path == 0) {
+        if (sbo_status st = remove_refit(ctx, run)) return st;
+    } else {
+        if (sbo_status st = remove_begin(ctx, run)) return st;
+        for (int64_t i : run.map.pos) {
+            if (sbo_status st = remove_chain(ctx, run, i)) return st;
+            if (sbo_status st = remove_rows(ctx, run, i)) return st;
+        }
+        if (sbo_status st = remove_compact(ctx, run)) return st;
+        ++ctx->fit_epoch;   // another model: a kept posterior is not updated into it
+        ctx->n = run.n1;
+        ctx->linv_n = run.n1;
+        ctx->z_n = 0;
+        ctx->order = run.map.new_order;
+        ctx->n_sorted = sorted_left;
+        ctx->removed_since_sort += b;
+        if (sbo_status st = refresh_operand(ctx, 0, {}, run.first)) return st;
+    }
+    SBO_HIP(hipEventRecord(ev1, ctx->stream));
+    SBO_HIP(hipEventSynchronize(ev1));
+    float msf = 0.0f;
+    SBO_HIP(hipEventElapsedTime(&msf, ev0, ev1));
+    r.ms = msf;
+    if (info) copy_info(info, r);
+    return fc.commit(finish(ctx, flags));
+}
+
+SBO_API sbo_status sbo_debug_inverse64(sbo_ctx *ctx, double *X, int64_t cap) {
+    if (!ctx) return SBO_E_INVAL;
+    SBO_CHECK(ctx->fitted && inverse_current(ctx, ctx->n), SBO_E_STATE, "sbo_debug_inverse64: no current f64 inverse");
+    const int64_t n = ctx->n;
+    SBO_CHECK(X && cap >= n * n, SBO_E_INVAL, "sbo_debug_inverse64: X must hold n * n doubles");
+    SBO_HIP(hipSetDevice(ctx->device));
+    std::vector<double> cm((size_t)n * (size_t)n);
+    SBO_HIP(hipMemcpy2DAsync(cm.data(), sizeof(double) * n, ctx->Linv.as<double>(), sizeof(double) * ctx->cap,
+                             sizeof(double) * n, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    SBO_HIP(hipStreamSynchronize(ctx->stream));
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t j = 0; j < n; ++j) X[i * n + j] = j <= i ? cm[(size_t)(j * n + i)] : 0.0;
+    return SBO_OK;
+}
+
+SBO_API sbo_status sbo_debug_remove_map(const int64_t *order, int64_t n, const int64_t *idx, int64_t b, int64_t *pos,
+                                        int64_t *new_order) {
+    if (n <= 0 || !order) return SBO_E_INVAL;
+    try {
+        sbo::RemoveMap m;
+        const sbo::RemoveMapStatus st = sbo::remove_map(order, n, idx, b, m);
+        if (st == sbo::RemoveMapStatus::kInval) return SBO_E_INVAL;
+        if (st == sbo::RemoveMapStatus::kEmpty) return SBO_E_EMPTY;
+        if (pos) std::copy(m.pos.begin(), m.pos.end(), pos);
+        if (new_order) std::copy(m.new_order.begin(), m.new_order.end(), new_order);
+    } catch (...) {
+        return SBO_E_OOM;
+    }
+    return SBO_OK;
 }
 
 SBO_API sbo_status sbo_predict(sbo_ctx *ctx, const float *qx, const float *qy, int64_t m, float *mu, float *sd,
@@ -3219,6 +3435,10 @@ SBO_API sbo_status sbo_set_option(sbo_ctx *ctx, int option, int64_t value) {
         case SBO_OPT_WHATIF_GEMM:
             SBO_CHECK(value == 0 || value == 1, SBO_E_INVAL, "SBO_OPT_WHATIF_GEMM must be 0 (dtrmm) or 1 (dgemm)");
             ctx->opt.whatif_gemm = (int)value;
+            return SBO_OK;
+        case SBO_OPT_REMOVE_MAX:
+            SBO_CHECK(value >= 0 && value <= 65536, SBO_E_INVAL, "SBO_OPT_REMOVE_MAX must be in [0, 65536]");
+            ctx->opt.remove_max = value;
             return SBO_OK;
         case SBO_OPT_TILE_SKIP:
             SBO_CHECK(value == -1 || value == 0 || (value >= 16 && value <= 1000), SBO_E_INVAL,

@@ -49,6 +49,7 @@ struct sbo_options {
     int64_t stream_max_rows = 64;   // SBO_OPT_STREAM_MAX_ROWS: more appended rows than this take the full sweep
     int evidence_budget = 20;    // SBO_OPT_EVIDENCE_BUDGET: the pair cutoff may move grad[0] by 2^-B n (0: dense)
     int whatif_gemm = 0;         // SBO_OPT_WHATIF_GEMM: the candidate weights' two products by 0 dtrmm, 1 dgemm over the zero half
+    int64_t remove_max = 2;      // SBO_OPT_REMOVE_MAX: sbo_remove refits the remaining points above this many removed ones
 };
 
 // --------------------------------------------------------- derived operands
@@ -126,9 +127,10 @@ struct Workspaces {
     sbo::DevBuf wiws;            // sbo_whatif: K_c^T / W^T, U^T, the candidates' sums and factors, counts, host staging
     sbo::DevBuf smws;            // sbo_sample: T^T / W^T, U^T, Theta^T, the frequencies, the sums, counts, keys, host staging
     sbo::DevBuf cholx3[2];       // the Cholesky's outer panels split into bf16 planes (SBO_OPT_CHOL_GEMM 3), alternating
+    sbo::DevBuf rmws, rmw64, rmmove;   // sbo_remove: the chain's carry, coefficients and kept positions; a batch's f64 columns of L; the compaction's staging
     void release() {
         for (sbo::DevBuf *b : {&scratch, &gzws, &gzws_aux, &chk, &restage, &kzt, &qcost, &awork, &evws, &evitems, &wiws,
-                               &smws, &cholx3[0], &cholx3[1]})
+                               &smws, &cholx3[0], &cholx3[1], &rmws, &rmw64, &rmmove})
             b->release();
     }
 };
@@ -190,7 +192,8 @@ struct sbo_ctx {
     sbo::DevBuf aug;             // packed sf2 * L^-1 tiles
     sbo::DevBuf kcoord;          // per k-tile: x[BK], y[BK], sf2*alpha[BK]
     int64_t npad = 0;            // rows/cols of the packed operand (multiple of BM)
-    int64_t n_sorted = 0;        // points of the last k-d sort (fit / re-sort)
+    int64_t n_sorted = 0;        // points of the last k-d sort (fit / re-sort) still stored
+    int64_t removed_since_sort = 0;   // points sbo_remove rotated out since then (SBO_OPT_RESORT counts them with the appended ones)
     sbo::DevBuf alpha64;         // alpha from the f64 solve (length cap)
     sbo::DevBuf zvec, rvec;      // z = L^-1 (y - m0) (f64, valid for z_n points: appends update alpha from it), r scratch
     int64_t z_n = 0;

@@ -285,6 +285,32 @@ hipError_t launch_chol_update_x3(hipStream_t s, const char *planes, int64_t m, i
 // The panel below it (csrc/chol_chain.hip): A21 (m2 x kb, lda ld) := A21 L11^-T (forward substitution, f32);
 // version as launch_chol_diag's
 hipError_t launch_chol_trsm(hipStream_t s, const float *L11, int64_t ld, int kb, float *A21, int64_t m2, int version = 1);
+// sbo_remove (csrc/remove.hip): a point leaves the factor and the f64 inverse
+// by Givens rotations.  The chain's workspace for n points: the f64 carry
+// column w, the rotations' (c_k, s_k) at coef[2k], the failed-pivot flag
+// (zeroed by the caller), and the kept stored positions (n1 of them,
+// ascending) for the compaction.
+struct RemoveWork {
+    double *w = nullptr, *coef = nullptr;
+    int *flag = nullptr, *keep = nullptr;
+};
+size_t remove_work_bytes(int64_t n);
+RemoveWork remove_work(void *base, int64_t n);
+// the compaction's staging of the elements that move (n1 points left, f the smallest removed position)
+size_t remove_compact_bytes(int64_t n1, int64_t f);
+// Stored position i (of n, dead rows and columns of earlier chains included)
+// out of the factor: the f32 L in place (W null), or the f64 copy W of its
+// columns from wcol0 on (same ld; column c at W + (c - wcol0) ld).  One
+// diagonal and one panel launch per 128 columns right of i.
+hipError_t launch_remove_chain(hipStream_t s, float *L, double *W, int64_t ld, int64_t wcol0, int64_t n, int64_t i,
+                               const RemoveWork &wk);
+// The same rotations (wk.coef) applied to rows i+1 .. n-1 of X with row i as the carry
+hipError_t launch_remove_rows(hipStream_t s, double *X, int64_t ld, int64_t n, int64_t i, const RemoveWork &wk);
+// The kept rows and columns (wk.keep) of L (columns from wcol0 on rounded from
+// W when there is one), X and the points moved to positions 0 .. n1-1; only
+// positions >= f move, through ws (remove_compact_bytes)
+hipError_t launch_remove_compact(hipStream_t s, float *L, const double *W, int64_t wcol0, double *X, int64_t ld,
+                                 float *x, float *y, float *obs, int64_t n1, int64_t f, const RemoveWork &wk, void *ws);
 // d = (double)in - v;  out = (float)d
 hipError_t launch_widen_sub(hipStream_t s, const float *in, double v, int64_t n, double *d);
 // alpha = X^T X (obs - m0) from the f64 inverse X (lower, lda ld), z = X (obs -

@@ -190,6 +190,33 @@ class TerrainMapper:
         b = int(x.numel() if _is_dev(x) else x.size)
         self.ctx.check(self._lib.sbo_append(self.ctx.handle, _ptr(x), _ptr(y), _ptr(obs), b, fl))
 
+    def remove(self, indices) -> dict:
+        """Drop training points without a refit (sbo_remove).  ``indices`` are
+        caller indices in ``order()``'s numbering; afterwards the remaining
+        points are renumbered densely, as ``numpy.delete`` would.  Returns
+        ``path`` (1 rotations, 0 refit of the remaining points), ``reason`` as
+        its name, ``removed``, ``n`` (points left), ``first_row``,
+        ``rotations`` and ``ms``."""
+        idx = _host(list(indices), np.int64).reshape(-1)
+        r = N.sbo_remove_info()
+        r.struct_size = ctypes.sizeof(r)
+        self.ctx.check(self._lib.sbo_remove(self.ctx.handle, _ptr(idx) if idx.size else None, int(idx.size),
+                                            ctypes.byref(r), 0))
+        d = {f: getattr(r, f) for f, _ in N.sbo_remove_info._fields_ if f not in ("struct_size", "reserved")}
+        d["reason"] = N.REMOVE_REASONS[d["reason"]]
+        return d
+
+    def forget_oldest(self, k: int) -> dict:
+        """The sliding window: ``remove(range(k))``."""
+        return self.remove(range(int(k)))
+
+    def inverse64(self) -> np.ndarray:
+        """Test access: the current f64 inverse L^-1, dense lower, row-major (sbo_debug_inverse64)."""
+        n = self.n
+        X = np.empty((n, n), np.float64)
+        self.ctx.check(self._lib.sbo_debug_inverse64(self.ctx.handle, _ptr(X), n * n))
+        return X
+
     @property
     def n(self) -> int:
         return int(self._lib.sbo_num_train(self.ctx.handle))
