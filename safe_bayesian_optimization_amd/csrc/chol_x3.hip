@@ -32,14 +32,15 @@
 //     or rocBLAS: the factor differs from theirs at the f32 rounding level).
 #include <cstdint>
 
+#include "bf16_split.hpp"
 #include "sbo_internal.hpp"
 
 namespace sbo {
 namespace {
 
+using bf16s::split3;
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) char lds_char;
@@ -54,13 +55,6 @@ constexpr int kCxWaves = 8;
 constexpr int kCxPieces = kCxStage / 1024 / kCxWaves; // 9 LDS-DMA pieces per wave per chunk
 static_assert(kCxPieces * 1024 * kCxWaves == kCxStage, "whole pieces per wave");
 static_assert(2 * kCxStage <= 160 * 1024, "two stages in the LDS");
-
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float lo_f32(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float hi_f32(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
 
 __global__ __launch_bounds__(256) void chol_split_kernel(const float *__restrict__ P, int64_t ld, int m, int nb,
                                                          int64_t units, char *__restrict__ out) {
@@ -77,12 +71,11 @@ __global__ __launch_bounds__(256) void chol_split_kernel(const float *__restrict
     for (int j = 0; j < 4; ++j) {
         const float a = in ? p[(int64_t)(2 * j) * ld] : 0.0f;
         const float bb = in ? p[(int64_t)(2 * j + 1) * ld] : 0.0f;
-        const uint32_t h = pk_bf16(a, bb);
-        const float ra = a - lo_f32(h), rb = bb - hi_f32(h);
-        const uint32_t md = pk_bf16(ra, rb);
+        uint32_t h, md, lw;
+        split3(a, bb, h, md, lw);
         w0[j] = h;
         w1[j] = md;
-        w2[j] = pk_bf16(ra - lo_f32(md), rb - hi_f32(md));
+        w2[j] = lw;
     }
     char *o = out + (size_t)u * kCxBlk + lane * 16;
     *reinterpret_cast<u32x4 *>(o) = w0;

@@ -1,7 +1,8 @@
 // kernels.hip -- CDNA4 (gfx950) kernels of the planning-tick hot path.
 //
 //   rbf_fill      a1  K = sf2 exp(-|xi-xj|^2 / 2l^2) + sn2 I      (HBM-write bound)
-//   pack_operand      A = sf2 L^-1 into [BK][BM] tiles, lower triangle only
+//   (operand.hip)     A = sf2 L^-1 into [BK][BM] tiles, the per-k-tile coordinates and the
+//                     per-tile gain bounds the plan reads
 //   predict       a3+a4  V = A K*^T on f32 MFMA with K* generated in registers;
 //                    per row block: sum_rows V^2 (-> variance), sf2 alpha^T K* (-> mean)
 //   acquire       a6+a7+a10  sum partials, sd, ComputeSets in f64, masked argmax
@@ -93,30 +94,6 @@ __global__ void copy_lower_kernel(const float *__restrict__ src, int64_t lds, in
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     for (int64_t j = blockIdx.y; j < n; j += gridDim.y) dst[i + j * ldd] = i >= j ? src[i + j * lds] : 0.0f;
-}
-
-// ------------------------------------------------------------ operand pack
-// grid.x = k-tiles of the longest row block, grid.y = row block I.
-template <class T>
-__global__ __launch_bounds__(256) void pack_operand_kernel(const T *__restrict__ Linv,
-                                                           int64_t ld, int64_t n, T sf2, int64_t I0,
-                                                           float *__restrict__ aug) {
-    const int64_t I = I0 + blockIdx.y;
-    const int64_t kb = blockIdx.x;
-    if (kb >= (I + 1) * kTilesPerRowBlockStep) return;
-    float *tile = aug + (tile_start(I) + kb) * kTileFloats;
-    // (unrolled: 16 independent loads in flight per thread -- the kernel is a
-    // pure stream, 1 GiB of f64 in, 0.5 GiB of f32 out at C4)
-#pragma unroll 16
-    for (int e = threadIdx.x; e < kTileFloats; e += 256) {
-        // inverse of tile_offset: e = ((jj*BK + k)*16 + r)*4 + j3, row = 64 jj + 16 j3 + r
-        const int j3 = e & 3, r16 = (e >> 2) & 15, k = (e >> 6) & (kBK - 1), jj = e >> 12;
-        const int r = jj * 64 + j3 * 16 + r16;
-        const int64_t row = I * kBM + r, col = kb * kBK + k;
-        float v = 0.0f;
-        if (row < n && col < n && col <= row) v = (float)(sf2 * Linv[row + col * ld]);
-        tile[e] = v;
-    }
 }
 
 // dst[i + j*ldd] = src[i + j*lds] (f32 -> f64), i < m, j < n; lower: zero above the diagonal.
@@ -231,525 +208,6 @@ __global__ void widen_kernel(const float *__restrict__ src, int64_t lds, int64_t
         dst[i + j * ldd] = (!lower || i >= j) ? (double)src[i + j * lds] : 0.0;
 }
 
-// Per k-tile coordinates, step-major per lane group: k = 4p + g is stored at
-// g*16 + p (x, then y, then sf2*alpha), so lane group g reads the values of
-// consecutive k steps p, p+1 as one 8-byte pair.
-__device__ __forceinline__ int kcoord_slot(int o) { return (o & 3) * 16 + (o >> 2); }
-
-__global__ void pack_kcoord_kernel(const float *__restrict__ x, const float *__restrict__ y,
-                                   const float *__restrict__ alpha, int64_t n, int64_t npad,
-                                   float sf2, float *__restrict__ kcoord) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= npad) return;
-    const int64_t t = k / kBK;
-    const int o = kcoord_slot((int)(k % kBK));
-    float *c = kcoord + t * (3 * kBK);
-    const bool in = k < n;
-    c[o] = in ? x[k] : x[0];
-    c[kBK + o] = in ? y[k] : y[0];
-    c[2 * kBK + o] = in ? sf2 * alpha[k] : 0.0f;
-}
-
-// Row 1-norms of the packed operand, |A[I*BM + r][:]|_1: block (c, I)
-// sums row r over k-tiles [c*kRowL1Tiles, (c+1)*kRowL1Tiles) of row block I
-// and adds into row_l1 (zeroed by the launcher).
-constexpr int kRowL1Tiles = 4;
-__global__ __launch_bounds__(kBM) void row_l1_kernel(const float *__restrict__ aug, int64_t I0,
-                                                     double *__restrict__ row_l1) {
-    const int64_t I = I0 + blockIdx.y;
-    const int64_t kb0 = (int64_t)blockIdx.x * kRowL1Tiles;
-    const int64_t nkb = (I + 1) * kTilesPerRowBlockStep;
-    if (kb0 >= nkb) return;
-    const int r = threadIdx.x;
-    const float *t = aug + (tile_start(I) + kb0) * kTileFloats;
-    double s = 0.0;
-    for (int64_t kb = 0; kb < kRowL1Tiles && kb0 + kb < nkb; ++kb)
-        for (int k = 0; k < kBK; ++k) s += fabs((double)t[kb * kTileFloats + tile_offset(k, r)]);
-    atomicAdd(row_l1 + I * kBM + r, s);
-}
-
-// The split of an f32 value into three bf16 pieces, v = v0 + v1 + v2 (+ a
-// remainder below 2^-24 |v|), exactly as pack_x3_kernel splits the operand
-// (the same round-to-nearest-even conversion instruction).
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float bf16_rn(float a) {
-    const f32x2_t v = {a, 0.0f};
-    const uint32_t w = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-    return __uint_as_float(w << 16);
-}
-
-// Per packed tile, gain bounds (log2, rounded up), two float4 per tile:
-// lgn[2T]   .x = log2(16 max_r |A_r|_1)  (|A k|_2 <= sqrt(256) |A k|_inf <= 16 max_r |A_r|_1 max|k|)
-//           .y = log2 of a bound on the spectral norm ||A_It||_2  (|A k|_2 <= ||A||_2 |k|_2):
-//                with the 64x64 Gram matrix G = A^T A (PSD, f64), ||A||_2^2 = lambda_max(G)
-//                <= ||G^16||_inf^(1/16) (any induced norm bounds the spectral radius;
-//                at most 64^(1/32) = 1.14x over ||A||_2 for a 64 x 64 G),
-//                also <= |A|_F^2 = trace G; the smaller of the two;
-//           .z = log2(|A_It|_F), which also bounds || |A_It| ||_2;
-// lgn[2T+1] the same two bounds for the bf16 pieces the split sweep
-//           multiplies (A = A0 + A1 + A2, pack_x3_kernel): .x, .y of A1 and
-//           .z, .w of A2 (16 max row 1-norm, spectral) -- the products a
-//           tile's lower precision levels leave out are A2 K0 + A1 K1 + A0 K2
-//           (three products) and also A1 K0 + A0 K1 (one product), bounded
-//           plane by plane in tile_increments.
-// The plan pairs the row-sum bounds with the largest K* of the tile and the
-// spectral ones with a bound on |k|_2 from the tile's points.  One workgroup
-// per tile; the three matrices one after the other.  The Gram matrices and
-// their squarings are bf16 MFMA products of split operands (below); wave w
-// owns two or three of the ten lower 16 x 16 blocks of each 64 x 64 product.
-// LDS row stride (floats) of the powers of G: 68 puts the row-sum pass's
-// 16-B reads and the mirrored stores on distinct banks
-constexpr int kTnGmLd = kBK + 4;
-// Round 6: the Gram matrices from the tile's bf16 pieces on the bf16 matrix
-// cores.  A = A0 + A1 + A2 (+ r, |r| < 2^-24 |A|) exactly as pack_x3_kernel
-// splits it, so G1 = A1^T A1 and G2 = A2^T A2 are products of bf16 values --
-// exact products, f32 accumulation -- and G = A^T A is taken as A0^T A0 + A0^T
-// A1 + A1^T A0 + A0^T A2 + A2^T A0 + G1 (the dropped A1^T A2 + A2^T A1 + A2^T
-// A2 and r's terms are < 2^-22 |A|^T|A|).  One v_mfma_f32_16x16x32_bf16 covers
-// 16 x 16 x 32 where the f64 16x16x4 form needed eight at four times the
-// cycles each.  Rigour: the stored G_c is symmetrised (lower blocks mirrored)
-// and |G_c - G| <= delta |A|^T |A| entrywise with delta = 2^-16 (<= 80 f32
-// roundings of partial sums of |A|^T |A|, 4.8e-6, plus the dropped terms),
-// so ||G_c - G||_2 <= delta |A|_F^2 and, by Weyl, lambda_max(G) <=
-// lambda_max(G_c) + delta |A|_F^2: the spectral bound below adds that term
-// (at most 64 delta = 1e-3 relative, since ||A||_2^2 >= |A|_F^2 / 64).  The
-// squarings run on the bf16 matrix cores too (their bound: in the kernel).  Row sums and |A|_F^2 come from the pieces in f64 (A0 +
-// A1 + A2 = A to 2^-24: inside the outputs' 1e-5 log2 margin).  The pieces are
-// those pack_x3_kernel cuts (the same instructions on the unscaled values),
-// each scaled by its own power of two 2^s_p (exact) so that the piece's
-// largest |entry| is in [1, 2): f32 products and sums then stay far above
-// f32's underflow (unscaled, A2^T A2 of a tile of 2^-60 entries underflowed
-// and the bound lost its rigour -- caught by comparing against the f64
-// kernel's bounds).  The cross terms of G go to accumulators of their own
-// and are combined in f64 with the exact scale factors.  What underflow
-// remains is bounded by an absolute term: 2^-110 of each accumulator's own
-// scale in ||G_c - G||_2 (64 x 264 operations below 2^-126 each).
-// The tile is staged a quarter (64 rows) at a time: the quarter's floats are
-// one contiguous 64 x 64 block in k-major order (tile_offset), and the Gram's
-// contraction runs over that storage order (any order of the rows serves).
-constexpr int kTnPq = kBK + 8;                 // bf16 per staged k row: 144 B, conflict-free b128 reads
-constexpr double kTnDelta = 1.0 / 65536.0;     // 2^-16
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ f32x4_t mfma_bf16(uint4 a, uint4 b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b),
-                                                   c, 0, 0, 0);
-}
-// a 16 x 16 block (bi >= bj) of plane pi's symmetric 64 x 64 Gram matrix,
-// scaled 2^(2 sp[pi]), from the f32 MFMA accumulators (lane l, element v:
-// row 16 bi + 4 (l>>4) + v, column 16 bj + (l&15)): G_A = a00 + 2^(s0 - s1)
-// a01 + 2^(s0 - s2) a02 + 2^(2 (s0 - s1)) a1 in f64 (exact scalings); the
-// entries above the diagonal of a diagonal block are left 0 (the stores
-// mirror the lower ones)
-__device__ __forceinline__ void gram_values(double (&x)[4], int bi, int bj, int lane, int pi, f32x4_t a00,
-                                            f32x4_t a01, f32x4_t a02, f32x4_t a1, f32x4_t a2,
-                                            const int (&sp)[3]) {
-    const double c01 = ldexp(1.0, sp[0] - sp[1]), c02 = ldexp(1.0, sp[0] - sp[2]), c11 = c01 * c01;
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-        const int i = 16 * bi + 4 * (lane >> 4) + v, j = 16 * bj + (lane & 15);
-        x[v] = (bi != bj || i >= j)
-                   ? (pi == 0 ? (((double)a00[v] + c01 * (double)a01[v]) + c02 * (double)a02[v]) + c11 * (double)a1[v]
-                              : (pi == 1 ? (double)a1[v] : (double)a2[v]))
-                   : 0.0;
-    }
-}
-// an f32 block (bi >= bj) of a symmetric matrix into gf (stride kTnGmLd):
-// the lower entries and their mirror (a diagonal block's upper entries from
-// its lower ones, so the stored matrix is exactly symmetric); the mirror of
-// a lane's four rows is one 16-B store
-__device__ __forceinline__ void store_sym_f32(float *gf, int bi, int bj, int lane, const float (&x)[4]) {
-    const int i0 = 16 * bi + 4 * (lane >> 4), j = 16 * bj + (lane & 15);
-    if (bi != bj) {
-#pragma unroll
-        for (int v = 0; v < 4; ++v) gf[(i0 + v) * kTnGmLd + j] = x[v];
-        *reinterpret_cast<float4 *>(gf + j * kTnGmLd + i0) = make_float4(x[0], x[1], x[2], x[3]);
-    } else {
-#pragma unroll
-        for (int v = 0; v < 4; ++v)
-            if (i0 + v >= j) {
-                gf[(i0 + v) * kTnGmLd + j] = x[v];
-                gf[j * kTnGmLd + i0 + v] = x[v];
-            }
-    }
-}
-// FUSED (round 6): the tile is first packed here from the f64 inverse --
-// pack_operand_kernel's values, (float)(sf2 L^-1), written to aug -- so the
-// pack and the norms are one pass over L^-1 (the staging pass re-reads the
-// thread's own stores from L2).
-template <bool FUSED>
-__global__ __launch_bounds__(kBM, 2) void tile_norm_kernel(const float *__restrict__ aug, int64_t t0,
-                                                           float4 *__restrict__ lgn, const double *__restrict__ Linv,
-                                                           int64_t ld, int64_t n, double sf2, float *augw) {
-    __shared__ __attribute__((aligned(16))) unsigned short pq[3][kBK * kTnPq];   // a quarter's pieces [k][c] (27 KiB)
-    __shared__ __attribute__((aligned(16))) float gm[kBK * kTnGmLd];   // G, then its powers, normalised f32 (17 KiB)
-    __shared__ double rpart[3][4][kBK];        // row-sum partials of a quarter (6 KiB)
-    __shared__ double red[2][kBM / 64];
-    __shared__ double fred[3][kBM / 64], rwm[3][kBM / 64];   // per wave: |.|_F^2 sums, row-sum maxima
-    const int64_t tile = t0 + blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    __shared__ float out[6];                     // (rows, spectral) of A; of A1; of A2 (LDS: a plane-indexed array)
-    double lg_fro_a = -1000.0;
-    // this wave's lower blocks of the 4 x 4 block grid of G: (0,0) (1,0) (1,1) |
-    // (2,0) (2,1) (2,2) | (3,0) (3,1) | (3,2) (3,3)
-    const int nb = wave < 2 ? 3 : 2;
-    const int tbi[3] = {wave < 2 ? 2 * wave : 3, wave < 2 ? 2 * wave + (wave == 0 ? 1 : 0) : 3, wave == 0 ? 1 : 2};
-    const int tbj[3] = {wave < 3 ? 0 : 2, wave == 0 ? 0 : (wave == 1 ? 1 : (wave == 2 ? 1 : 3)), wave == 0 ? 1 : 2};
-    // the Gram accumulators: A (its five cross terms), A1, A2
-    // G_A's terms A0^T A0, A1^T A0 + A0^T A1, A2^T A0 + A0^T A2 (scaled 2^(s0 + s_p)), then G1, G2
-    f32x4_t acc00[3], acc01[3], acc02[3], acc1[3], acc2[3];
-#pragma unroll
-    for (int b = 0; b < 3; ++b) acc00[b] = acc01[b] = acc02[b] = acc1[b] = acc2[b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    double rmax[3] = {0.0, 0.0, 0.0}, fro[3] = {0.0, 0.0, 0.0};
-    const int sk = tid >> 2, sc = 16 * (tid & 3);   // staging: k row sk, storage columns sc .. sc + 15
-    const int rc = tid & 63, rk = tid >> 6;         // row sums: column rc, k in [16 rk, 16 rk + 16)
-    // the thread's 16 floats of each quarter (a quarter is one contiguous
-    // 64 x 64 block), all in flight at once; the tile's largest |entry| sets
-    // the scale 2^sc
-    // (the tile is read twice, the second time from L2: a pass for the
-    // pieces' maxima, then the staging)
-    auto load16 = [&](int q, float (&v)[16]) {
-        const float4 *src = FUSED ? reinterpret_cast<const float4 *>(augw + tile * kTileFloats + q * 64 * kBK + 16 * tid)
-                                  : reinterpret_cast<const float4 *>(aug + tile * kTileFloats + q * 64 * kBK + 16 * tid);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float4 f = src[j];
-            v[4 * j] = f.x;
-            v[4 * j + 1] = f.y;
-            v[4 * j + 2] = f.z;
-            v[4 * j + 3] = f.w;
-        }
-    };
-    __shared__ float pmax[3][kBM / 64];
-    {
-        float amax[3] = {0.0f, 0.0f, 0.0f};
-        // FUSED: the tile's row block and k-tile (tile = tile_start(I) + kb)
-        int64_t fI = 0, fkb = 0;
-        if (FUSED) {
-            fI = (int64_t)((sqrt(1.0 + 2.0 * (double)tile) - 1.0) * 0.5);
-            while (fI > 0 && tile_start(fI) > tile) --fI;
-            while (tile_start(fI + 1) <= tile) ++fI;
-            fkb = tile - tile_start(fI);
-        }
-#pragma unroll
-        for (int q = 0; q < kBM / 64; ++q) {
-            float tv[16];
-            if (FUSED) {
-                // element 16 tid + j of quarter q (tile_offset): k = tid / 4, row
-                // 64 q + 16 (j & 3) + 4 (tid & 3) + j / 4 -- pack_operand_kernel's value
-                const int64_t col = fkb * kBK + (tid >> 2);
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const int64_t row = fI * kBM + 64 * q + 16 * (j & 3) + 4 * (tid & 3) + (j >> 2);
-                    tv[j] = (row < n && col < n && col <= row) ? (float)(sf2 * Linv[row + col * ld]) : 0.0f;
-                }
-                float4 *dst = reinterpret_cast<float4 *>(augw + tile * kTileFloats + q * 64 * kBK + 16 * tid);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) dst[j] = make_float4(tv[4 * j], tv[4 * j + 1], tv[4 * j + 2], tv[4 * j + 3]);
-            } else {
-                load16(q, tv);
-            }
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const float x = tv[j];
-                const float a0 = bf16_rn(x), r1 = x - a0, a1 = bf16_rn(r1), a2 = bf16_rn(r1 - a1);
-                amax[0] = fmaxf(amax[0], fabsf(a0));
-                amax[1] = fmaxf(amax[1], fabsf(a1));
-                amax[2] = fmaxf(amax[2], fabsf(a2));
-            }
-        }
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc) {
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) amax[pc] = fmaxf(amax[pc], __shfl_xor(amax[pc], o));
-            if (lane == 0) pmax[pc][wave] = amax[pc];
-        }
-    }
-    __syncthreads();
-    int sp[3];           // the pieces' scales: 2^sp max |piece| in [1, 2)
-    float up[3];
-    double dn[3];
-#pragma unroll
-    for (int pc = 0; pc < 3; ++pc) {
-        const float m = fmaxf(fmaxf(pmax[pc][0], pmax[pc][1]), fmaxf(pmax[pc][2], pmax[pc][3]));
-        sp[pc] = m > 0.0f ? -ilogbf(m) : 0;
-        up[pc] = ldexpf(1.0f, sp[pc]);
-        dn[pc] = ldexp(1.0, -sp[pc]);
-    }
-#pragma unroll 1
-    for (int q = 0; q < kBM / 64; ++q) {
-        // stage: split (as pack_x3_kernel does, unscaled), scale each piece by 2^sp (exact), store
-        {
-            float tv[16];
-            load16(q, tv);
-            uint32_t w[3][8];
-#pragma unroll
-            for (int j = 0; j < 16; j += 2) {
-                uint32_t h[3][2];
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const float x = tv[j + e];
-                    const float a0 = bf16_rn(x), r1 = x - a0, a1 = bf16_rn(r1), a2 = bf16_rn(r1 - a1);
-                    h[0][e] = __float_as_uint(a0 * up[0]) >> 16;
-                    h[1][e] = __float_as_uint(a1 * up[1]) >> 16;
-                    h[2][e] = __float_as_uint(a2 * up[2]) >> 16;
-                }
-#pragma unroll
-                for (int pc = 0; pc < 3; ++pc) w[pc][j / 2] = h[pc][0] | (h[pc][1] << 16);
-            }
-#pragma unroll
-            for (int pc = 0; pc < 3; ++pc) {
-                uint4 *dst = reinterpret_cast<uint4 *>(pq[pc] + sk * kTnPq + sc);
-                dst[0] = make_uint4(w[pc][0], w[pc][1], w[pc][2], w[pc][3]);
-                dst[1] = make_uint4(w[pc][4], w[pc][5], w[pc][6], w[pc][7]);
-            }
-        }
-        __syncthreads();
-        // Gram: two 32-deep contraction steps over the quarter's 64 storage columns
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int co = 32 * ks + 8 * (lane >> 4);
-            uint4 fa[3][3], fb[3][3];   // [piece][block]
-#pragma unroll
-            for (int b = 0; b < 3; ++b)
-                if (b < nb)
-#pragma unroll
-                    for (int pc = 0; pc < 3; ++pc) {
-                        fa[pc][b] = *reinterpret_cast<const uint4 *>(pq[pc] + (16 * tbi[b] + (lane & 15)) * kTnPq + co);
-                        fb[pc][b] = *reinterpret_cast<const uint4 *>(pq[pc] + (16 * tbj[b] + (lane & 15)) * kTnPq + co);
-                    }
-#pragma unroll
-            for (int b = 0; b < 3; ++b)
-                if (b < nb) {
-                    acc02[b] = mfma_bf16(fa[0][b], fb[2][b], mfma_bf16(fa[2][b], fb[0][b], acc02[b]));
-                    acc01[b] = mfma_bf16(fa[0][b], fb[1][b], mfma_bf16(fa[1][b], fb[0][b], acc01[b]));
-                    acc00[b] = mfma_bf16(fa[0][b], fb[0][b], acc00[b]);
-                    acc1[b] = mfma_bf16(fa[1][b], fb[1][b], acc1[b]);
-                    acc2[b] = mfma_bf16(fa[2][b], fb[2][b], acc2[b]);
-                }
-        }
-        // row sums (the quarter's 64 rows = its 64 storage columns) and |.|_F^2,
-        // in f64 from the pieces (A = A0 + A1 + A2 to 2^-24)
-        {
-            double s[3] = {0.0, 0.0, 0.0};
-#pragma unroll 4
-            for (int k = 16 * rk; k < 16 * rk + 16; ++k) {
-                // (unscaled: exact powers of two)
-                const double b0 = (double)__uint_as_float((uint32_t)pq[0][k * kTnPq + rc] << 16) * dn[0];
-                const double b1 = (double)__uint_as_float((uint32_t)pq[1][k * kTnPq + rc] << 16) * dn[1];
-                const double b2 = (double)__uint_as_float((uint32_t)pq[2][k * kTnPq + rc] << 16) * dn[2];
-                const double a = b0 + b1 + b2;     // exact (three bf16 values of one f32's split)
-                s[0] += fabs(a);
-                s[1] += fabs(b1);
-                s[2] += fabs(b2);
-                fro[0] = fma(a, a, fro[0]);
-                fro[1] = fma(b1, b1, fro[1]);
-                fro[2] = fma(b2, b2, fro[2]);
-            }
-#pragma unroll
-            for (int pc = 0; pc < 3; ++pc) rpart[pc][rk][rc] = s[pc];
-        }
-        __syncthreads();   // (pq restaged next quarter; rpart complete)
-        if (rk == 0)
-#pragma unroll
-            for (int pc = 0; pc < 3; ++pc)
-                rmax[pc] = fmax(rmax[pc], ((rpart[pc][0][rc] + rpart[pc][1][rc]) + rpart[pc][2][rc]) + rpart[pc][3][rc]);
-    }
-    // the block maxima of the row sums and the sums of |.|_F^2 (fixed-order
-    // trees), unscaled (exact: powers of two)
-#pragma unroll
-    for (int pc = 0; pc < 3; ++pc) {
-        double rs = rmax[pc], fs = fro[pc];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            rs = fmax(rs, __shfl_xor(rs, o));
-            fs += __shfl_xor(fs, o);
-        }
-        if (lane == 0) {
-            red[0][wave] = 0.0;
-            fred[pc][wave] = fs;
-            rwm[pc][wave] = rs;
-        }
-    }
-    __syncthreads();
-    double rowmax_all[3];
-#pragma unroll
-    for (int pc = 0; pc < 3; ++pc)
-        rowmax_all[pc] = fmax(fmax(rwm[pc][0], rwm[pc][1]), fmax(rwm[pc][2], rwm[pc][3]));
-#pragma unroll 1
-    for (int pi = 0; pi < 3; ++pi) {
-        const int plane = pi == 0 ? -1 : pi;     // -1: A itself, then A1, A2
-        // the plane's Gram matrix G_c (f64, registers), normalised by its
-        // largest entry's power of two 2^e0 and rounded to f32: M0, symmetric
-        double gv[3][4];
-        double gmx = 0.0;
-#pragma unroll
-        for (int b = 0; b < 3; ++b)
-            if (b < nb) {
-                gram_values(gv[b], tbi[b], tbj[b], lane, pi, acc00[b], acc01[b], acc02[b], acc1[b], acc2[b], sp);
-#pragma unroll
-                for (int v = 0; v < 4; ++v) gmx = fmax(gmx, fabs(gv[b][v]));
-            }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) gmx = fmax(gmx, __shfl_xor(gmx, o));
-        if (lane == 0) red[1][wave] = gmx;
-        __syncthreads();
-        const double mx0 = fmax(fmax(red[1][0], red[1][1]), fmax(red[1][2], red[1][3]));
-        const int e0 = mx0 > 0.0 ? ilogb(mx0) : 0;
-#pragma unroll
-        for (int b = 0; b < 3; ++b)
-            if (b < nb) {
-                float xf[4];
-#pragma unroll
-                for (int v = 0; v < 4; ++v) xf[v] = (float)ldexp(gv[b][v], -e0);
-                store_sym_f32(gm, tbi[b], tbj[b], lane, xf);
-            }
-        const double fro2 = ((fred[pi][0] + fred[pi][1]) + fred[pi][2]) + fred[pi][3];
-        double s = rowmax_all[pi];
-        // Four squarings on the bf16 matrix cores (round 6; f64 MFMA before,
-        // 2.1 ms of the C4 fit's critical path): M_k is split into three bf16
-        // planes as pack_x3_kernel splits (pq, free after the Gram), S_k =
-        // M_k M_k is taken as the six products a2 b0 + a1 b1 + a0 b2 + a1 b0 + a0
-        // b1 + a0 b0 (exact products, f32 accumulation) on the ten lower
-        // blocks, and M_(k+1) = 2^-e S_k (e: S_k's largest entry's exponent,
-        // exact) is stored mirrored, so every M_k is exactly symmetric.
-        // Rigour: |S_k - M_k^2| <= eps |M_k| |M_k| entrywise with eps = 2^-15
-        // (the dropped a1 b2 + a2 b1 + a2 b2 and the split's remainder < 2^-22,
-        // <= 396 f32 roundings of partial sums of the |terms| < 2.4e-5), so
-        // ||S_k - M_k^2||_2 <= eta ||M_k||_2^2 with eta = 64 eps (||
-        // |M| |M| ||_2 <= |M|_F^2 <= 64 ||M||_2^2) and ||M_k||_2^2 <=
-        // ||S_k||_2 / (1 - eta); M0 is G_c 2^-e0 rounded to f32, ||G_c||_2 <=
-        // 2^e0 ||M0||_2 / (1 - 2^-21).  Chained: log2 ||G_c||_2 <= e0 + (T +
-        // log2 ||M4||_inf + 15 log2(1 / (1 - eta))) / 16 + log2(1 / (1 - 2^-21)),
-        // T = 8 e1 + 4 e2 + 2 e3 + e4 (||M4||_2 <= ||M4||_inf: symmetric).
-        // Underflow (entries below 2^-110 of the largest) costs < 2^-90 of
-        // ||S_k||_2 >= 1, inside eps's slack.
-        constexpr int kGramSquarings = 4;
-        constexpr double kSqEta = 64.0 / 32768.0;   // 64 eps, eps = 2^-15
-        int T = 0;
-        bool live = mx0 > 0.0;
-        for (int it = 0; it < kGramSquarings && live; ++it) {
-            __syncthreads();   // M_k stored (and every read of pq by the last products done)
-            {
-                // split M_k into the planes: row sk, columns sc .. sc + 15
-                const float4 *src = reinterpret_cast<const float4 *>(gm + sk * kTnGmLd + sc);
-                uint32_t w[3][8];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 f = src[q];
-                    const float xv[4] = {f.x, f.y, f.z, f.w};
-#pragma unroll
-                    for (int e = 0; e < 4; e += 2) {
-                        uint32_t h[3][2];
-#pragma unroll
-                        for (int u = 0; u < 2; ++u) {
-                            const float x = xv[e + u];
-                            const float a0 = bf16_rn(x), r1 = x - a0, a1 = bf16_rn(r1), a2 = bf16_rn(r1 - a1);
-                            h[0][u] = __float_as_uint(a0) >> 16;
-                            h[1][u] = __float_as_uint(a1) >> 16;
-                            h[2][u] = __float_as_uint(a2) >> 16;
-                        }
-#pragma unroll
-                        for (int pc = 0; pc < 3; ++pc) w[pc][(4 * q + e) / 2] = h[pc][0] | (h[pc][1] << 16);
-                    }
-                }
-#pragma unroll
-                for (int pc = 0; pc < 3; ++pc) {
-                    uint4 *dst = reinterpret_cast<uint4 *>(pq[pc] + sk * kTnPq + sc);
-                    dst[0] = make_uint4(w[pc][0], w[pc][1], w[pc][2], w[pc][3]);
-                    dst[1] = make_uint4(w[pc][4], w[pc][5], w[pc][6], w[pc][7]);
-                }
-            }
-            __syncthreads();
-            f32x4_t sq[3];
-#pragma unroll
-            for (int b = 0; b < 3; ++b) sq[b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const int co = 32 * ks + 8 * (lane >> 4);
-                uint4 fa[3][3], fb[3][3];   // [piece][block]
-#pragma unroll
-                for (int b = 0; b < 3; ++b)
-                    if (b < nb)
-#pragma unroll
-                        for (int pc = 0; pc < 3; ++pc) {
-                            fa[pc][b] = *reinterpret_cast<const uint4 *>(pq[pc] + (16 * tbi[b] + (lane & 15)) * kTnPq + co);
-                            fb[pc][b] = *reinterpret_cast<const uint4 *>(pq[pc] + (16 * tbj[b] + (lane & 15)) * kTnPq + co);
-                        }
-#pragma unroll
-                for (int b = 0; b < 3; ++b)
-                    if (b < nb) {
-                        sq[b] = mfma_bf16(fa[2][b], fb[0][b], sq[b]);
-                        sq[b] = mfma_bf16(fa[1][b], fb[1][b], sq[b]);
-                        sq[b] = mfma_bf16(fa[0][b], fb[2][b], sq[b]);
-                        sq[b] = mfma_bf16(fa[1][b], fb[0][b], sq[b]);
-                        sq[b] = mfma_bf16(fa[0][b], fb[1][b], sq[b]);
-                        sq[b] = mfma_bf16(fa[0][b], fb[0][b], sq[b]);
-                    }
-            }
-            float qmx = 0.0f;
-#pragma unroll
-            for (int b = 0; b < 3; ++b)
-                if (b < nb)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) qmx = fmaxf(qmx, fabsf(sq[b][v]));
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) qmx = fmaxf(qmx, __shfl_xor(qmx, o));
-            if (lane == 0) red[0][wave] = (double)qmx;
-            __syncthreads();   // every wave's maximum (and every read of gm by the split is done)
-            const double mk = fmax(fmax(red[0][0], red[0][1]), fmax(red[0][2], red[0][3]));
-            live = mk > 0.0;
-            const int ek = live ? ilogb(mk) : 0;
-            T = 2 * T + ek;
-#pragma unroll
-            for (int b = 0; b < 3; ++b)
-                if (b < nb) {
-                    // (the diagonal block's upper entries are computed too; only the lower are kept)
-                    const float xf[4] = {ldexpf(sq[b][0], -ek), ldexpf(sq[b][1], -ek), ldexpf(sq[b][2], -ek),
-                                         ldexpf(sq[b][3], -ek)};
-                    store_sym_f32(gm, tbi[b], tbj[b], lane, xf);
-                }
-        }
-        __syncthreads();   // the last power stored
-        // ||M4||_inf: largest absolute row sum (f64)
-        double rs = 0.0;
-        if (tid < kBK)
-            for (int j = 0; j < kBK; ++j) rs += fabs((double)gm[tid * kTnGmLd + j]);
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) rs = fmax(rs, __shfl_xor(rs, o));
-        if (lane == 0) red[1][wave] = rs;
-        __syncthreads();
-        rs = fmax(fmax(red[1][0], red[1][1]), fmax(red[1][2], red[1][3]));
-        if (!live) rs = 0.0;   // (a zero Gram matrix)
-        // log2 ||A||_2 (the plane scaled by 2^sp: G_c = 2^(2 sp) G) from the
-        // chain above, 1e-6 for the f64 row sums and logs; then ||A||_2^2 <=
-        // that^2 + delta |A|_F^2 (G_c's own error) + the absolute underflow
-        // term: 2^-110 per accumulator at its own scale, five for G_A, all at
-        // most 2^(-2 sp) unscaled
-        const int spl = sp[pi];
-        const double lg_g = (double)e0 +
-                            ((double)T + log2(rs) - (double)((1 << kGramSquarings) - 1) * log2(1.0 - kSqEta)) /
-                                (double)(1 << kGramSquarings) -
-                            log2(1.0 - 0x1p-21);
-        const double lg_pow = rs > 0.0 ? 0.5 * lg_g + 1e-6 - spl : -1000.0;
-        const double spec2 = (rs > 0.0 ? exp2(2.0 * lg_pow) : 0.0) + kTnDelta * fro2 + ldexp(5.0, -110 - 2 * spl);
-        const double lg_spec = spec2 > 0.0 ? 0.5 * log2(spec2) : -1000.0;
-        const double lg_fro = fro2 > 0.0 ? 0.5 * log2(fro2) : -1000.0;
-        const int o = 2 * pi;                    // A: 0, A1: 2, A2: 4
-        if (tid == 0) {
-            out[o] = s > 0.0 ? (float)log2(16.0 * s) + 1e-5f : -1000.0f;
-            out[o + 1] = (float)fmin(lg_spec, lg_fro) + 1e-5f;
-        }
-        if (plane < 0) lg_fro_a = lg_fro;
-        __syncthreads();   // gm / red / rsum / at are rewritten for the next matrix
-    }
-    if (tid == 0) {
-        lgn[2 * tile] = make_float4(out[0], out[1], (float)lg_fro_a + 1e-5f, 0.0f);
-        lgn[2 * tile + 1] = make_float4(out[2], out[3], out[4], out[5]);
-    }
-}
-
 // d[i] = (double)in[i] - v
 __global__ void widen_sub_kernel(const float *__restrict__ in, double v, int64_t n, double *__restrict__ d) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -759,20 +217,6 @@ __global__ void widen_sub_kernel(const float *__restrict__ in, double v, int64_t
 __global__ void narrow_kernel(const double *__restrict__ d, int64_t n, float *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = (float)d[i];
-}
-
-// Bounding box of each k-tile's valid training points: (xmin, xmax, ymin, ymax);
-// a tile with no valid point gets an empty box (+inf, -inf, +inf, -inf).
-__global__ void tile_box_kernel(const float *__restrict__ x, const float *__restrict__ y, int64_t n,
-                                int64_t ntiles, float4 *__restrict__ kbox) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= ntiles) return;
-    float x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
-    for (int64_t k = t * kBK; k < (t + 1) * kBK && k < n; ++k) {
-        x0 = fminf(x0, x[k]); x1 = fmaxf(x1, x[k]);
-        y0 = fminf(y0, y[k]); y1 = fmaxf(y1, y[k]);
-    }
-    kbox[t] = make_float4(x0, x1, y0, y1);
 }
 
 // ---------------------------------------------------------- a3+a4 predict
@@ -884,7 +328,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // evaluates K* of steps p+2, p+3 as one packed pair (v_pk_add/mul/fma_f32,
 // then two v_exp_f32) beside the sixteen MFMAs of step p.  No MFMA or exp
 // waits on a read issued in its own step.  pc = this lane group's
-// coordinate row (kcoord_slot layout: step p of x at pc[p], y at
+// coordinate row (operand.hip's kcoord_slot layout: step p of x at pc[p], y at
 // pc[kBK + p], sf2*alpha at pc[2*kBK + p]).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -2201,86 +1645,11 @@ hipError_t launch_copy_lower(hipStream_t s, const float *src, int64_t ld_src, in
     return hipGetLastError();
 }
 
-hipError_t launch_pack_tiles(hipStream_t s, const double *Linv, int64_t ld, int64_t n, int64_t npad, int64_t I0,
-                             double sf2, float *aug) {
-    const int64_t nI = npad / kBM;
-    if (I0 >= nI) return hipSuccess;
-    hipLaunchKernelGGL(pack_operand_kernel<double>, dim3((unsigned)(nI * kTilesPerRowBlockStep), (unsigned)(nI - I0)),
-                       dim3(256), 0, s, Linv, ld, n, sf2, I0, aug);
-    return hipGetLastError();
-}
-
-hipError_t launch_pack_kcoord(hipStream_t s, const float *x, const float *y, const float *alpha, int64_t n,
-                              int64_t npad, double sf2, float *kcoord) {
-    hipLaunchKernelGGL(pack_kcoord_kernel, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, s, x, y, alpha, n, npad,
-                       (float)sf2, kcoord);
-    return hipGetLastError();
-}
-
-template <class T>
-hipError_t launch_pack_operand_t(hipStream_t s, const T *Linv, int64_t ld, int64_t n, int64_t npad, int64_t I0,
-                                 double sf2, const float *x, const float *y, const float *alpha, float *aug,
-                                 float *kcoord) {
-    const int64_t nI = npad / kBM;
-    if (I0 < nI) {
-        hipLaunchKernelGGL(pack_operand_kernel<T>, dim3((unsigned)(nI * kTilesPerRowBlockStep), (unsigned)(nI - I0)),
-                           dim3(256), 0, s, Linv, ld, n, (T)sf2, I0, aug);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(pack_kcoord_kernel, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, s, x, y,
-                       alpha, n, npad, (float)sf2, kcoord);
-    return hipGetLastError();
-}
-
-hipError_t launch_pack_operand(hipStream_t s, const float *Linv, int64_t ld, int64_t n, int64_t npad, int64_t I0,
-                               double sf2, const float *x, const float *y, const float *alpha, float *aug,
-                               float *kcoord) {
-    return launch_pack_operand_t<float>(s, Linv, ld, n, npad, I0, sf2, x, y, alpha, aug, kcoord);
-}
-
-hipError_t launch_pack_operand(hipStream_t s, const double *Linv, int64_t ld, int64_t n, int64_t npad, int64_t I0,
-                               double sf2, const float *x, const float *y, const float *alpha, float *aug,
-                               float *kcoord) {
-    return launch_pack_operand_t<double>(s, Linv, ld, n, npad, I0, sf2, x, y, alpha, aug, kcoord);
-}
-
 hipError_t launch_widen(hipStream_t s, const float *src, int64_t ld_src, int64_t m, int64_t n, bool lower,
                         double *dst, int64_t ld_dst) {
     if (m <= 0 || n <= 0) return hipSuccess;
     hipLaunchKernelGGL(widen_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)std::min<int64_t>(n, kMaxGridY)),
                        dim3(256), 0, s, src, ld_src, m, n, lower ? 1 : 0, dst, ld_dst);
-    return hipGetLastError();
-}
-
-hipError_t launch_row_l1(hipStream_t s, const float *aug, int64_t npad, int64_t I0, double *row_l1) {
-    const int64_t nI = npad / kBM;
-    if (I0 >= nI) return hipSuccess;
-    hipError_t e = hipMemsetAsync(row_l1 + I0 * kBM, 0, sizeof(double) * (size_t)((nI - I0) * kBM), s);
-    if (e != hipSuccess) return e;
-    const int64_t chunks = (nI * kTilesPerRowBlockStep + kRowL1Tiles - 1) / kRowL1Tiles;
-    hipLaunchKernelGGL(row_l1_kernel, dim3((unsigned)chunks, (unsigned)(nI - I0)), dim3(kBM), 0, s, aug, I0, row_l1);
-    return hipGetLastError();
-}
-
-hipError_t launch_pack_tile_norms(hipStream_t s, const double *Linv, int64_t ld, int64_t n, int64_t npad, int64_t I0,
-                                  double sf2, float *aug, float4 *lgn) {
-    const int64_t nI = npad / kBM;
-    const int64_t t0 = tile_start(I0), t1 = tile_start(nI);
-    if (t1 <= t0) return hipSuccess;
-    // (the fused kernel writes the tile and reads it back through augw alone: no second, const __restrict__
-    // alias of the buffer)
-    hipLaunchKernelGGL(tile_norm_kernel<true>, dim3((unsigned)(t1 - t0)), dim3(kBM), 0, s,
-                       static_cast<const float *>(nullptr), t0, lgn, Linv, ld, n, sf2, aug);
-    return hipGetLastError();
-}
-
-hipError_t launch_tile_norms(hipStream_t s, const float *aug, int64_t npad, int64_t I0, float4 *lgn) {
-    const int64_t nI = npad / kBM;
-    const int64_t t0 = tile_start(I0), t1 = tile_start(nI);
-    if (t1 <= t0) return hipSuccess;
-    hipLaunchKernelGGL(tile_norm_kernel<false>, dim3((unsigned)(t1 - t0)), dim3(kBM), 0, s, aug, t0, lgn, nullptr,
-                       (int64_t)0, (int64_t)0, 0.0, nullptr);
     return hipGetLastError();
 }
 
@@ -2327,12 +1696,6 @@ hipError_t launch_narrow_2d(hipStream_t s, const double *d, int64_t ldd, int64_t
 hipError_t launch_narrow_strided(hipStream_t s, const double *d, int64_t n, float *out, int64_t stride) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(narrow_strided_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, n, out, stride);
-    return hipGetLastError();
-}
-
-hipError_t launch_tile_boxes(hipStream_t s, const float *x, const float *y, int64_t n, int64_t npad, float4 *kbox) {
-    const int64_t nt = npad / kBK;
-    hipLaunchKernelGGL(tile_box_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, x, y, n, nt, kbox);
     return hipGetLastError();
 }
 
@@ -2533,29 +1896,6 @@ void plan_item_views(int64_t npad, int64_t m, int P, const void *work, const uns
     *scan = reinterpret_cast<const unsigned long long *>(w + L.scan);
     *thr = reinterpret_cast<const unsigned char *>(w + L.thr);
     if (nonempty) *nonempty = reinterpret_cast<const unsigned long long *>(w + L.nemask);
-}
-
-namespace {
-// colmax[t] = max over the row blocks I that hold k-tile t of lgn[2 (tile_start(I) + t)].x
-// (+inf if one is NaN: such a pair is never far)
-__global__ void tile_colmax_kernel(const float4 *__restrict__ lgn, int nI, float *__restrict__ colmax) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= kTilesPerRowBlockStep * nI) return;
-    float mx = -INFINITY;
-    for (int I = t / kTilesPerRowBlockStep; I < nI; ++I) {
-        const float v = lgn[2 * (tile_start(I) + t)].x;
-        mx = v != v ? INFINITY : fmaxf(mx, v);
-    }
-    colmax[t] = mx;
-}
-}  // namespace
-
-hipError_t launch_tile_colmax(hipStream_t s, const float4 *lgn, int64_t npad, float *colmax) {
-    const int nI = (int)(npad / kBM);
-    if (nI <= 0) return hipSuccess;
-    hipLaunchKernelGGL(tile_colmax_kernel, dim3((unsigned)((kTilesPerRowBlockStep * nI + 255) / 256)), dim3(256), 0, s,
-                       lgn, nI, colmax);
-    return hipGetLastError();
 }
 
 float exp2_coef_f(float ell) { return (float)exp2_coef(ell); }

@@ -28,15 +28,19 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "bf16_split.hpp"
 #include "sbo_internal.hpp"
 
 namespace sbo {
 namespace x3r {
 namespace {
 
+using bf16s::hi_f32;
+using bf16s::lo_f32;
+using bf16s::pk_bf16;
+using bf16s::split3;
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -69,22 +73,6 @@ static_assert(kPieces == 6, "the end-of-step wait below counts 2, 4 or 6 pieces"
 static_assert(kXPlane == 16 * 1024 && kBM == 256 && kBK == 64 && kBN == 128, "the stage is 64 k x 128 rows");
 
 __device__ __forceinline__ float fast_exp2(float v) { return __builtin_amdgcn_exp2f(v); }
-__device__ __forceinline__ float lo_f32(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float hi_f32(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-
-// two f32 -> one dword of two bf16 (element 0 low), round to nearest even
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-
-// v = v0 + v1 + v2 for a pair of values (element 0 in the low halves)
-__device__ __forceinline__ void split3(float a, float b, uint32_t &w0, uint32_t &w1, uint32_t &w2) {
-    w0 = pk_bf16(a, b);
-    const float ra = a - lo_f32(w0), rb = b - hi_f32(w0);
-    w1 = pk_bf16(ra, rb);
-    w2 = pk_bf16(ra - lo_f32(w1), rb - hi_f32(w1));
-}
 
 __device__ __forceinline__ bf16x8 as_bf16x8(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
 

@@ -2,8 +2,8 @@
 //
 // Host orchestration of the GP mapper (fit / append / predict) and the
 // node's acquisition (ComputeSets, grid argmax).  Device work runs on the
-// context's stream: HIP kernels from kernels.hip, rocSOLVER for the
-// factorisation.  No exception crosses the C boundary.
+// context's stream: HIP kernels (the tick's from kernels.hip, the operand
+// build's from operand.hip), rocSOLVER for the factorisation.  No exception crosses the C boundary.
 #include <rocsolver/rocsolver.h>
 
 #include <algorithm>
@@ -33,10 +33,6 @@ sbo_status finish(sbo_ctx *ctx, uint32_t flags) {
     SBO_HIP(hipStreamSynchronize(ctx->stream));
     return SBO_OK;
 }
-
-#ifndef SBO_FUSED_TN
-#define SBO_FUSED_TN 1
-#endif
 
 // The guard's policy for the f64 inverse (inverse.cpp runs the inverse itself).
 // The digits of the current fit's sliced products (SBO_OPT_INV_OZ_ADAPT:
@@ -671,7 +667,6 @@ struct RefreshPlan {
     bool aux;            // alpha and the derived operands go to aux_stream
     bool eager_x3, eager_f64;   // the derived operands brought up to date on aux_stream beside the packs
     int x3_layout;
-    bool fused_norms;    // the tile norms ran with the pack (SBO_FUSED_TN)
 };
 RefreshPlan plan_refresh(const sbo_ctx *ctx, int64_t n_old, const FactorHandover &ho, InvAttempt attempt,
                          int64_t removed_from = -1) {
@@ -708,7 +703,6 @@ RefreshPlan plan_refresh(const sbo_ctx *ctx, int64_t n_old, const FactorHandover
     p.eager_f64 =
         p.aux && o.precision_opt != 0 && (probe_due(ctx) || ctx->precise || o.precision_opt == 1);
     p.x3_layout = sbo::x3_layout(o.kernel_variant);
-    p.fused_norms = p.f64 && SBO_FUSED_TN;
     return p;
 }
 
@@ -824,15 +818,11 @@ sbo_status refresh_packs(sbo_ctx *ctx, const RefreshPlan &p) {
         if (sbo_status st = ctx->split.reserve(ctx, npad, p.x3_layout)) return st;
     if (p.eager_f64)
         if (sbo_status st = ctx->pop.reserve(ctx, npad)) return st;
-#if SBO_FUSED_TN
     // the pack and the tile norms in one pass over L^-1 (tile_norm_kernel<true>)
     SBO_HIP(grow_keep(ctx, ctx->tile_lgn, 2 * sizeof(float4) * (size_t)sbo::total_tiles(p.nI),
                       2 * sizeof(float4) * p.old_tiles));
     SBO_HIP(sbo::launch_pack_tile_norms(ctx->stream, Li, ld, n, npad, I0, p.sf2, ctx->aug.as<float>(),
                                         ctx->tile_lgn.as<float4>()));
-#else
-    SBO_HIP(sbo::launch_pack_tiles(ctx->stream, Li, ld, n, npad, I0, p.sf2, ctx->aug.as<float>()));
-#endif
     if (!p.eager_x3 && !p.eager_f64) return SBO_OK;
     SBO_HIP(hipEventRecord(ctx->ev_panel, ctx->stream));
     SBO_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_panel, 0));
@@ -888,7 +878,7 @@ sbo_status refresh_join(sbo_ctx *ctx, const RefreshPlan &p) {
         SBO_HIP(ctx->ws.scratch.reserve(sizeof(double) * (size_t)npad));
         SBO_HIP(sbo::launch_row_l1(ctx->stream, ctx->aug.as<float>(), npad, p.I0, ctx->ws.scratch.as<double>()));
     }
-    if (!p.fused_norms) {
+    if (!p.f64) {   // (the f64 inverse's tile norms ran with its pack, refresh_packs)
         SBO_HIP(grow_keep(ctx, ctx->tile_lgn, 2 * sizeof(float4) * (size_t)sbo::total_tiles(p.nI),
                           2 * sizeof(float4) * p.old_tiles));
         SBO_HIP(sbo::launch_tile_norms(ctx->stream, ctx->aug.as<float>(), npad, p.I0, ctx->tile_lgn.as<float4>()));

@@ -127,21 +127,30 @@ hipError_t launch_rbf_fill(hipStream_t s, const float *xa, const float *ya, int6
 hipError_t launch_sub_scalar(hipStream_t s, const float *in, float v, int64_t n, float *out);
 hipError_t launch_copy_lower(hipStream_t s, const float *src, int64_t ld_src, int64_t n,
                              float *dst, int64_t ld_dst);
-// Pack A = sf2 * L^-1 (from an f32 or f64 inverse, lower, column-major) into
-// [BK][BM] tiles for row blocks I >= I0 (earlier row blocks are left as they
-// are), plus per-k coordinates and sf2 * alpha for all k.
-// the two halves of launch_pack_operand (f64 inverse): the operand tiles, and the
-// per-k-tile coordinates + sf2 alpha (which waits for alpha)
-hipError_t launch_pack_tiles(hipStream_t s, const double *Linv, int64_t ld, int64_t n, int64_t npad, int64_t I0,
-                             double sf2, float *aug);
+// The fit-side operand build (csrc/operand.hip): what a refresh derives from
+// L^-1 (lower, column-major) and the points; per row block for the row blocks
+// I >= I0 (earlier row blocks are left as they are), per k-tile whole.
+// The per-k-tile coordinates and sf2 * alpha for all k
 hipError_t launch_pack_kcoord(hipStream_t s, const float *x, const float *y, const float *alpha, int64_t n,
                               int64_t npad, double sf2, float *kcoord);
+// The f32 inverse: A = sf2 * L^-1 into [BK][BM] tiles, and the coordinates
 hipError_t launch_pack_operand(hipStream_t s, const float *Linv, int64_t ld, int64_t n, int64_t npad, int64_t I0,
                                double sf2, const float *x, const float *y, const float *alpha, float *aug,
                                float *kcoord);
-hipError_t launch_pack_operand(hipStream_t s, const double *Linv, int64_t ld, int64_t n, int64_t npad, int64_t I0,
-                               double sf2, const float *x, const float *y, const float *alpha, float *aug,
-                               float *kcoord);
+// lgn[2 (tile_start(I) + t)] = log2 bounds (16 max row 1-norm, spectral,
+// Frobenius) of A_It, lgn[2 (..) + 1] = (16 max row 1-norm, spectral) of its
+// bf16 pieces A1 and A2 (f64 sums, rounded up; -1000 for an all-zero matrix).
+hipError_t launch_tile_norms(hipStream_t s, const float *aug, int64_t npad, int64_t I0, float4 *lgn);
+// The f64 inverse: its tiles packed and their norms taken in one pass over L^-1
+hipError_t launch_pack_tile_norms(hipStream_t s, const double *Linv, int64_t ld, int64_t n, int64_t npad, int64_t I0,
+                                  double sf2, float *aug, float4 *lgn);
+// row_l1[i] = sum_j |A_ij| over the packed operand (f64)
+hipError_t launch_row_l1(hipStream_t s, const float *aug, int64_t npad, int64_t I0, double *row_l1);
+// Per k-tile bounding boxes of the (internally ordered) training points
+hipError_t launch_tile_boxes(hipStream_t s, const float *x, const float *y, int64_t n, int64_t npad,
+                             float4 *kbox);
+// colmax[t], t < npad / kBK: the largest lgn[2 (tile_start(I) + t)].x over the row blocks I that hold k-tile t
+hipError_t launch_tile_colmax(hipStream_t s, const float4 *lgn, int64_t npad, float *colmax);
 // dst (m x n, f64, ld_dst) = src (f32, ld_src); lower: zero above the diagonal.
 hipError_t launch_widen(hipStream_t s, const float *src, int64_t ld_src, int64_t m, int64_t n, bool lower,
                         double *dst, int64_t ld_dst);
@@ -212,8 +221,6 @@ void plan_views(int64_t npad, int64_t m, int P, const void *work, const int4 **d
 void plan_item_views(int64_t npad, int64_t m, int P, const void *work, const unsigned long long **key,
                      const unsigned long long **scan, const unsigned char **thr,
                      const unsigned long long **nonempty = nullptr);
-// colmax[t], t < npad / kBK: the largest lgn[2 (tile_start(I) + t)].x over the row blocks I that hold k-tile t
-hipError_t launch_tile_colmax(hipStream_t s, const float4 *lgn, int64_t npad, float *colmax);
 // Split-operand (bf16 x3) predictive sweep, predict_x3.hip: the packed
 // operand split into three bf16 planes per row half of a tile (48 KiB stages,
 // predict_x3_rowhalf.hpp) and the per-k-tile coordinates in natural order,
@@ -256,14 +263,6 @@ hipError_t read_x3_stamps(double *out, int n);
 hipError_t launch_predict_x3(hipStream_t s, const char *ax3, const float *kc3, const int4 *desc, const int4 *rec,
                              const int *seg, int P, int n_items, int nI, const float *qx, const float *qy, int64_t m,
                              int64_t ldp, float cexp, float m0, float *part, float *mean, int variant);
-// lgn[2 (tile_start(I) + t)] = log2 bounds (16 max row 1-norm, spectral,
-// Frobenius) of A_It, lgn[2 (..) + 1] = (16 max row 1-norm, spectral) of its
-// bf16 pieces A1 and A2 (f64 sums, rounded up) for row blocks I >= I0 (-1000
-// for an all-zero matrix).
-hipError_t launch_tile_norms(hipStream_t s, const float *aug, int64_t npad, int64_t I0, float4 *lgn);
-// the f64 operand's pack (launch_pack_tiles) and the tile norms in one pass
-hipError_t launch_pack_tile_norms(hipStream_t s, const double *Linv, int64_t ld, int64_t n, int64_t npad, int64_t I0,
-                                  double sf2, float *aug, float4 *lgn);
 // Blocked Cholesky, the chain (csrc/chol_chain.hip): factor the kb x kb
 // diagonal block at A (column-major, lda = ld) of step k0 in place (kb <=
 // kCholNB); info as rocSOLVER's.
@@ -327,11 +326,6 @@ hipError_t launch_narrow_2d(hipStream_t s, const double *d, int64_t ldd, int64_t
                             int64_t ldo);
 // out[j * stride] = (float)d[j], j < n
 hipError_t launch_narrow_strided(hipStream_t s, const double *d, int64_t n, float *out, int64_t stride);
-// row_l1[i] = sum_j |A_ij| over the packed operand (f64), rows of row blocks >= I0.
-hipError_t launch_row_l1(hipStream_t s, const float *aug, int64_t npad, int64_t I0, double *row_l1);
-// Per k-tile bounding boxes of the (internally ordered) training points.
-hipError_t launch_tile_boxes(hipStream_t s, const float *x, const float *y, int64_t n, int64_t npad,
-                             float4 *kbox);
 // Acquisition over predictive partials (fused reduce + sets + block argmax).
 // perm (may be null): sweep position i holds caller query perm[i]; outputs and
 // key indices are written in the caller's order.  nonempty (may be null): the

@@ -5,8 +5,8 @@ with both operands cut into three bf16 pieces, a = a0 + a1 + a2 and
 k = kh + km + kl, and keeps six of the nine piece products.  The tick plan
 (csrc/kernels.hip: plan_count_kernel) runs each (row block I of 256 rows,
 k-tile t of 64 columns) pair of a 128-query block at one of three levels or
-not at all (x3_step, predict_x3_rowhalf.hpp:129-150 and the MFMA chain at
-:222-233):
+not at all (x3_step, predict_x3_rowhalf.hpp:117-138 and the MFMA chain at
+:210-221):
 
     level 0                   a2 kh + a1 km + a0 kl + a1 kh + a0 km + a0 kh
     level 1                                           a1 kh + a0 km + a0 kh
@@ -22,17 +22,18 @@ two nearly equal sums), in f64:
     dvar(q)      = |V6|^2 - |V_plan|^2 = sum_rows dV (2 V6 - dV)
     dmu(q)       the k-tiles of the last row block absent from the records,
                  sum_k (sf2 alpha_k) K*(k, q): the mean reads the f32 product
-                 (float)sf2 * alpha[k] (pack_kcoord_kernel, kernels.hip:250)
-                 against the f32 K* of the tile (x3_step :213-219, x3_kstar
-                 :275), whatever the tile's level.
+                 (float)sf2 * alpha[k] (pack_kcoord_kernel, operand.hip:72)
+                 against the f32 K* of the tile (x3_step :201-207, x3_kstar
+                 :263), whatever the tile's level.
 
 The pieces.  A's are the round-to-nearest-even split of the f32 operand
-(split3, predict_x3_rowhalf.hpp:82-87, applied by pack_x3_kernel :583), the
-split test_tile_gain_bounds_are_bounds uses.  K*'s are the same split3 of the
-f32 value the sweep forms in registers (kstar1, :119-122): dx = xk - xq,
-dy = yk - yq in f32, s = fmaf(dy, dy, dx * dx), e = exp2(s * cexp) with
-cexp = (float)(-1 / (2 (float)l^2 ln 2)) (exp2_coef, kernels.hip:2400); then
-split3(e) (:201-202, :271).  The device evaluates exp2 with v_exp_f32 (one ulp,
+(split3, bf16_split.hpp:36-41, applied by pack_x3_kernel,
+predict_x3_rowhalf.hpp:571), the split the tile norms take their bounds of
+(operand.hip) and test_tile_gain_bounds_are_bounds uses.  K*'s are the same
+split3 of the f32 value the sweep forms in registers (kstar1, :107-110):
+dx = xk - xq, dy = yk - yq in f32, s = fmaf(dy, dy, dx * dx), e = exp2(s * cexp) with
+cexp = (float)(-1 / (2 (float)l^2 ln 2)) (exp2_coef, kernels.hip:1763); then
+split3(e) (:189-190, :259).  The device evaluates exp2 with v_exp_f32 (one ulp,
 results below 2^-126 flushed to zero); here it is the correctly rounded f32 of
 the f64 exp2, flushed the same way.  That difference enters reference and plan
 alike and moves an omitted product by 2^-23 of itself.

@@ -806,19 +806,12 @@ def test_plan_beyond_the_bin_cache(mapper):
         gm.set_option(N.SBO_OPT_SKIP_BUDGET, 20)
 
 
-@pytest.mark.parametrize("n", [1100, 4100])
-def test_tile_gain_bounds_are_bounds(mapper, n):
-    """sbo_get_tile_bounds: every packed tile's log2 bounds are upper bounds
-    of the exact norms of A_It = (sf2 L^-1)_It and of its bf16 pieces A1, A2
-    (the same round-to-nearest split as the sweep's operand), and the
-    spectral bounds are within the ||G^8||^(1/16) slack (<= 64^(1/16) = 1.30x).
-    Round 6: the Gram matrices come from the bf16 pieces on the bf16 matrix
-    cores, each piece scaled to [1, 2) first; n = 4100 reaches tiles far
-    below the diagonal whose A2 pieces are 2^-80 and smaller, where an
-    unscaled f32 Gram underflowed and the bound fell below the norm."""
-    wl = synthetic(n, 8, seed=17)
-    gm = TerrainMapper(0, wl.hyper, ctx=mapper.ctx)
-    gm.fit(wl.x, wl.y, wl.obs)
+def _check_tile_bounds(gm):
+    """Every packed tile's log2 bounds (sbo_get_tile_bounds) against the exact
+    norms of A_It = (sf2 L^-1)_It (sbo_get_inverse: the packed operand) and of
+    its bf16 pieces A1, A2: upper bounds, and the spectral ones within the
+    ||G^8||^(1/16) slack (<= 64^(1/16) = 1.30x).  Returns the bounds (tiles x
+    8), the number of non-zero tiles checked and the all-zero tiles' indices."""
     n = gm.n
     A = np.zeros((n, n), np.float32)
     gm.ctx.check(N.lib().sbo_get_inverse(gm.ctx.handle, A.ctypes.data))
@@ -840,6 +833,7 @@ def test_tile_gain_bounds_are_bounds(mapper, n):
     print(f"n={n}: {tiles} tiles, smallest A2 spectral bound 2^{b[:, 7][b[:, 7] > -1000].min():.1f}")
     T0 = 0
     checked = 0
+    zero = []
     for I in range(nI):
         for t in range(4 * (I + 1)):
             Tpad = np.zeros((256, 64), np.float32)
@@ -860,8 +854,64 @@ def test_tile_gain_bounds_are_bounds(mapper, n):
             if np.any(Tpad):
                 assert b[T0, 2] >= np.log2(np.linalg.norm(Tpad.astype(np.float64))) - 1e-6
                 checked += 1
+            else:
+                zero.append(T0)
             T0 += 1
-    assert T0 == tiles and checked > 20
+    assert T0 == tiles
+    return b, checked, zero
+
+
+@pytest.mark.parametrize("n", [1100, 4100])
+def test_tile_gain_bounds_are_bounds(mapper, n):
+    """sbo_get_tile_bounds: every packed tile's log2 bounds are upper bounds
+    of the exact norms of A_It = (sf2 L^-1)_It and of its bf16 pieces A1, A2
+    (the same round-to-nearest split as the sweep's operand), and the
+    spectral bounds are within the ||G^8||^(1/16) slack (<= 64^(1/16) = 1.30x).
+    Round 6: the Gram matrices come from the bf16 pieces on the bf16 matrix
+    cores, each piece scaled to [1, 2) first; n = 4100 reaches tiles far
+    below the diagonal whose A2 pieces are 2^-80 and smaller, where an
+    unscaled f32 Gram underflowed and the bound fell below the norm."""
+    wl = synthetic(n, 8, seed=17)
+    gm = TerrainMapper(0, wl.hyper, ctx=mapper.ctx)
+    gm.fit(wl.x, wl.y, wl.obs)
+    _, checked, _ = _check_tile_bounds(gm)
+    assert checked > 20
+
+
+def test_tile_gain_bounds_small_shapes(mapper):
+    """The tile norms' other paths at the smallest shapes that reach them,
+    held to the same bounds.  An f64 fit of n = 300 (the fused pack and norms):
+    two row blocks, 12 tiles; row block 1 has 44 valid rows, its k-tile 4 is
+    partly filled and its k-tiles 5-7 are all zero -- every output of those is
+    -1000 and the squarings leave at once -- and the diagonal tiles have a
+    zero upper part.  Then 300 more points appended without a re-sort: three
+    row blocks, the fused kernel runs on row blocks 1 and 2 only (tiles 4 ..
+    23, the tile -> (row block, k-tile) decode), row block 0's bounds are kept,
+    and all 24 hold against the grown operand.  Then the f32 inverse
+    (SBO_OPT_INVERSE_BITS 32): the norms alone over the packed tiles."""
+    wl = synthetic(600, 8, seed=19)
+    gm = TerrainMapper(0, wl.hyper, ctx=mapper.ctx)
+    outputs = [0, 1, 2, 4, 5, 6, 7]
+    try:
+        gm.set_option(N.SBO_OPT_RESORT, 0)
+        gm.fit(wl.x[:300], wl.y[:300], wl.obs[:300])
+        b0, checked, zero = _check_tile_bounds(gm)
+        assert (len(b0), checked, zero) == (12, 9, [9, 10, 11])
+        assert np.all(b0[zero][:, outputs] == -1000.0)
+        gm.append(wl.x[300:], wl.y[300:], wl.obs[300:])
+        assert gm.n == 600
+        b1, checked, zero = _check_tile_bounds(gm)
+        assert (len(b1), checked, zero) == (24, 22, [22, 23])
+        assert np.all(b1[zero][:, outputs] == -1000.0)
+        assert np.array_equal(b1[:4], b0[:4])      # row block 0: kept
+        gm.set_option(N.SBO_OPT_INVERSE_BITS, 32)
+        gm.fit(wl.x[:300], wl.y[:300], wl.obs[:300])
+        b2, checked, zero = _check_tile_bounds(gm)
+        assert (len(b2), checked, zero) == (12, 9, [9, 10, 11])
+        assert np.all(b2[zero][:, outputs] == -1000.0)
+    finally:
+        gm.set_option(N.SBO_OPT_INVERSE_BITS, 64)
+        gm.set_option(N.SBO_OPT_RESORT, 25)
 
 
 def test_sweep_partition_and_outer_variant(mapper):

@@ -112,7 +112,8 @@ print("ok", N.LIB_PATH, len(out), "arrays")
 
 # --inverse-matrix: the f64 inverse's options at sizes that give its tree every shape (base 1024 and 2048: a
 # one-column block, two levels, the smallest sliced top, a split lower-right block, a sliced second level),
-# then the append paths.  Per case L, alpha, the f32 view of the inverse, mu and sd, as --factor-matrix.
+# then the append paths.  Per case L, alpha, the f32 view of the inverse, mu and sd, as --factor-matrix, and the
+# tile bounds (bits32: the norms alone over the packed tiles; the appends: the row blocks past the kept ones).
 INVERSE_CHILD = r'''
 import hashlib, sys, numpy as np
 sys.path.insert(0, {root!r})
@@ -135,7 +136,9 @@ def record(name, wl):
     A = np.zeros((gm.n, gm.n), np.float32)
     gm.ctx.check(N.lib().sbo_get_inverse(gm.ctx.handle, A.ctypes.data))
     mu, sd = gm.predict(wl.qx, wl.qy)
-    for k, v in (("L", L), ("alpha", alpha), ("inv", A), ("mu", mu), ("sd", sd)):
+    b = np.empty(8 * sum(4 * (I + 1) for I in range((gm.n + 255) // 256)), np.float32)   # the plan's tile bounds
+    gm.ctx.check(N.lib().sbo_get_tile_bounds(gm.ctx.handle, b.ctypes.data, b.size))
+    for k, v in (("L", L), ("alpha", alpha), ("inv", A), ("mu", mu), ("sd", sd), ("tile_bounds", b)):
         v = np.ascontiguousarray(v)     # (arrays past 1 MiB: their SHA-256)
         out[name + "_" + k] = v if v.nbytes <= 1 << 20 else np.frombuffer(hashlib.sha256(v).digest(), np.uint8)
 for n in (1025, 2049, 3000, 3073, 4100, 9000):
